@@ -13,12 +13,13 @@ timed region.  value = 2*B*64 * N * K / max-over-ranks(time).  Weak scaling: per
 
 `python bench.py --gpus N` with no launcher starts its own N ranks (one process per GPU, RCCL).
 
-Order of one run: auxiliary legs (other compute types, config 3/4; their buffers stay allocated) -> device spin-up (`spinup_ms`
-of scratch fp32 GEMMs: an MI355X needs ~25 ms of sustained load to reach its steady clock, tools/ramp_probe.py) -> W untimed
-warm-up steps -> K timed steps between barrier + synchronize -> profiler pass (roofline) -> CPU baseline -> ONE JSON line (the
-last line of stdout).
+A plain run does only what the headline needs: set-up -> W + K untimed steps -> device spin-up (`spinup_ms` of scratch fp32 GEMMs:
+an MI355X needs ~25 ms of sustained load to reach its steady clock, tools/ramp_probe.py) -> W untimed warm-up steps -> K timed
+steps between barrier + synchronize -> `--dump-outputs DIR` -> ONE JSON line (the last line of stdout).
 
-Extra objects on the JSON line:
+`--full` adds everything else: auxiliary legs (other compute types, config 3/4, fwd_only / as_loss; their buffers stay allocated)
+before the headline, the first W + K steps timed as `ms_per_step_cold`, and after the headline the profiler passes (roofline), the
+data-parallel report and the CPU baseline.  Extra objects on the JSON line of a `--full` run:
   roofline     -- the fp32 MFMA GEMM kernel family (gemm_rs_kernel<...> + the LDS-ring fallback): algorithmic flops of the GEMM
                   launches of a step / their summed duration, measured with hipEvent pairs recorded in-stream around each
                   launch (library profiler, separate pass of the same K steps); peak = 157.3 TFLOP/s fp32 MFMA.
@@ -379,6 +380,17 @@ def profiled_gemm_pass(L, tr, lab, warmup, steps):
     return best
 
 
+def dump_outputs(d, tr):
+    """--dump-outputs: what the timed step hands its caller after the last timed step -- the loss pair [loss_samples, loss_pred], the
+    predicted distances of both directions [2*B*N, 3] and the updated parameters (flat, ~19 MB at the decoder widths of this file) --
+    as float32 .npy files.  Inputs and initial weights are seeded, so the same arguments give the same arrays on any build."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    tr.join_optimizer()          # data-parallel steps: Adam may still run on the collectives' stream
+    for name, t in (("loss", tr.loss), ("pred", tr.pred), ("params", tr.P.flat)):
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start one rank per GPU ourselves (the reference picks its towers with a
     flag inside one process, train_multi_gpu_pc_compare_dist.py:122-126,237-302; here: one process per GPU over RCCL, the same
@@ -602,6 +614,10 @@ def main():
     ap.add_argument("--cfg4", action="store_true", help="with DPD_FORCE_DIST=1: also run the config-4 legs on one GPU")
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed PMC summary instead of two rocprofv3 child passes "
                                                                "(profiler runs of this file: a profiler cannot nest)")
+    ap.add_argument("--full", action="store_true", help="also the auxiliary legs, the cold timing, the profiler passes, the data-parallel report "
+                                                        "and the CPU baseline (the --no-* switches above trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss, predictions and updated parameters as DIR/<name>.npy (float32)")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -849,7 +865,7 @@ def main():
         return out2
 
     cfg34 = None
-    if not a.no_other_dtypes and a.dtype == "f32" and B == 32:
+    if a.full and not a.no_other_dtypes and a.dtype == "f32" and B == 32:
         try:
             if world > 1 or (use_dist and a.cfg4):   # (--cfg4: exercise this leg on one GPU)
                 # every rank takes part in both legs (the first has collectives)
@@ -898,7 +914,7 @@ def main():
             cfg34 = ("config4" if world > 1 else "config3", {"error": repr(e)})
 
     legs8d = None
-    if rank == 0 and world == 1 and not use_dist and not a.no_other_dtypes and B == 32:
+    if a.full and rank == 0 and world == 1 and not use_dist and not a.no_other_dtypes and B == 32:
         hb.beat("aux:forward-only and as-loss legs")
         try:
             legs8d = section8d_legs(L, tr, pcA, pcB, lab, dev, a.steps, a.warmup)
@@ -906,7 +922,7 @@ def main():
             legs8d = {"error": repr(e)}
     hb.beat("aux:other compute types")
     others = None
-    if rank == 0 and world == 1 and not use_dist and not a.no_other_dtypes:
+    if a.full and rank == 0 and world == 1 and not use_dist and not a.no_other_dtypes:
         # Same step, same batch, same K steps in the other compute types of the decoder GEMMs (include/dpdist_capi.h:
         # enum dpd_dtype).  Reported next to `value`, never as `value`: f32x3 is fp32-equivalent (tests prove it at
         # least as accurate as the exact-fp32 MFMA path), bf16 is the mixed-precision type of BASELINE configs 3-4.
@@ -950,8 +966,9 @@ def main():
     hb.beat("warmup:cold pass + spin-up")
     el_cold = None
     if spin_ms > 0:
-        # the number WITHOUT the spin-up, reported next to the headline as ms_per_step_cold: the same W untimed + K timed steps, run
-        # first (the chip comes out of the auxiliary legs above or out of idle: this times the clock ramp, see below)
+        # the number WITHOUT the spin-up, reported by --full next to the headline as ms_per_step_cold: the same W untimed + K timed steps,
+        # run first (the chip comes out of the auxiliary legs above or out of idle: this times the clock ramp, see below).  A plain run
+        # runs them untimed: they are part of its warm-up, and the headline's steps start from the same trainer state either way
         for _ in range(a.warmup):
             tr.step(pcA, pcB, lab, prefetch=nxt)
         sync()
@@ -959,8 +976,8 @@ def main():
         for i in range(a.steps):
             tr.step(pcA, pcB, lab, prefetch=nxt)
         sync()
-        el_cold = time.perf_counter() - t0c
-        if use_dist:
+        el_cold = time.perf_counter() - t0c if a.full else None
+        if use_dist and a.full:
             tc = torch.tensor([el_cold], device=dev, dtype=torch.float64)
             dist.all_reduce(tc, op=dist.ReduceOp.MAX)
             el_cold = float(tc.item())
@@ -994,13 +1011,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     loss = tr.loss.cpu().numpy()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr)
     hb.beat("profile:roofline + exposed communication")
-    dp = dp_report(tr, lambda: tr.step(pcA, pcB, lab)) if use_dist else None
+    dp = dp_report(tr, lambda: tr.step(pcA, pcB, lab)) if use_dist and a.full else None
     if dp is not None:
         dp["schedule"] = headline_sched
 
     roof = None
-    if a.no_roofline:
+    if a.no_roofline or not a.full:
         gc.enable()
     else:
         # Separate pass of the same K steps (forward + backward, no Adam) with the library's in-stream profiler on.
@@ -1085,7 +1104,7 @@ def main():
                                                "launches_per_step": n0 // a.steps, "avg_launch_us": round(ms0 * 1e3 / n0, 2),
                                                "achieved": round(ach_nn * mult, 2), "unit": "TFLOP/s"}
     roof_hbm = None
-    if not a.no_roofline and rank == 0 and not use_dist:
+    if a.full and not a.no_roofline and rank == 0 and not use_dist:
         try:
             sfx = {"f32": "", "f32x3": "_f32x3", "bf16": "_bf16"}[a.dtype] if B == 32 else ("_bf16_b64" if (a.dtype, B) == ("bf16", 64) else "_none")
             roof_hbm = hbm_roofline_pass(L, lambda: tr.step(pcA, pcB, lab), a.warmup, a.steps, sfx)
@@ -1102,10 +1121,14 @@ def main():
                                       "fwd both directions + bwd AB half + Adam), S2 ModelNet-shaped clouds",
                           "pairs_per_gpu": B, "global_batch": B * world, "num_point": N, "query_points_per_step": 2 * B * N * world,
                           "parallelism": "dp%d" % world, "loss_samples_last": round(float(loss[0]), 6)},
-               "roofline": roof, "roofline_hbm": roof_hbm, "spinup_ms": spin_ms,
-               "ms_per_step_cold": round(el_cold / a.steps * 1e3, 4) if el_cold else None,
-               "cold_note": "ms_per_step_cold = the same W + K steps timed BEFORE the %g ms device spin-up (scratch fp32 GEMMs, nothing of the "
-                            "model) that precedes the headline region; the difference is the GPU's clock ramp (DESIGN.md section 5)" % spin_ms}
+               "spinup_ms": spin_ms}
+        if use_dist and tr.reducer is not None:
+            out["dp_backend"], out["fallback"] = tr.reducer.backend, hb.fallback
+    if rank == 0 and a.full:
+        out.update({"roofline": roof, "roofline_hbm": roof_hbm,
+                    "ms_per_step_cold": round(el_cold / a.steps * 1e3, 4) if el_cold else None,
+                    "cold_note": "ms_per_step_cold = the same W + K steps timed BEFORE the %g ms device spin-up (scratch fp32 GEMMs, nothing of "
+                                 "the model) that precedes the headline region; the difference is the GPU's clock ramp (DESIGN.md section 5)" % spin_ms})
         if dp is not None:
             out["dp"] = dp
             out["dp_backend"], out["fallback"] = dp["backend"], dp["fallback"]

@@ -1183,7 +1183,8 @@ def test_bench_watchdog_falls_back_on_the_gpu(dev):
     env = dict(os.environ, DPD_FORCE_DIST="1", DPD_WD_INJECT_HANG="timed", DPD_WD_LIMITS="timed=6", MASTER_PORT="29651")
     for k in ("DPD_BENCH_CHILD", "DPD_DP_BACKEND", "DPD_DP_MODE", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-dtypes"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+           "--no-other-dtypes"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -2166,7 +2167,8 @@ def test_bench_ranks_share_the_gpu(dev, world):
               "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -2193,7 +2195,7 @@ def test_bench_ranks_share_the_gpu(dev, world):
 
 @pytest.mark.gpu
 def test_bench_line_on_one_gpu(dev):
-    """`python bench.py` as the driver runs it at N = 1 (short): ONE JSON line with the contract's keys, the roofline object measured by
+    """`python bench.py --full` at N = 1 (short): ONE JSON line with the contract's keys, the roofline object measured by
     hipEvents in this run, and -- SURVEY 8(d), VERDICT r5 #3 -- the forward-only and as-loss legs, config 3 and the data-parallel
     expectation (dp_model) in the same line."""
     import json
@@ -2201,8 +2203,8 @@ def test_bench_line_on_one_gpu(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DPD_FORCE_DIST", "DPD_TEST_SHARE_GPU")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--full",
+                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -2225,6 +2227,43 @@ def test_bench_line_on_one_gpu(dev):
         assert 0 < leg["fwd_bwd"]["gemm_share_of_eval"] <= 1.0 and leg["fwd_bwd"]["gemm_launches"] == 6, (key, leg)
     assert set(rec["dp_model"]["per_world"]) == {"2", "4", "8"}
     assert rec["config3"]["dtype"] == "bf16" and rec["config3"]["pairs_per_gpu"] == 64 and "dp_model" in rec["config3"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_dumps_the_outputs(dev, tmp_path):
+    """`python bench.py` without --full, as every change is measured: ONE JSON line with the contract's keys and none of --full's records,
+    and --dump-outputs writes the last timed step's loss, predictions and updated parameters as float32 -- the same arrays from two runs
+    with the same arguments (seeded inputs, bitwise reproducible f32 step), and the loss the line reports."""
+    import json
+    import subprocess
+    import sys
+    from dpdist_amd.model import DPDistParams
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DPD_FORCE_DIST", "DPD_TEST_SHARE_GPU")}
+    recs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs",
+                            str(tmp_path / d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert rec["metric"].startswith("query-points/sec") and rec["unit"] == "query-points/sec" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["n_gpus"] == 1 and rec["steps"] == 7 and rec["warmup"] == 2 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 2 * 32 * 64 / (rec["ms_per_step"] * 1e-3)) <= 1e-3 * rec["value"]
+    for k in ("roofline", "roofline_hbm", "ms_per_step_cold", "dp_model", "fwd_only", "as_loss", "config3", "other_compute_types", "cpu_baseline"):
+        assert k not in rec, k
+    assert recs[0]["config"]["loss_samples_last"] == recs[1]["config"]["loss_samples_last"]
+    numel = DPDistParams(k=5, mlp=(1024, 1024, 1024), device=dev).numel
+    total = 0
+    for name, shape in (("loss", (2,)), ("pred", (2 * 32 * 64, 3)), ("params", (numel,))):
+        x, y = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("a", "b"))
+        assert x.dtype == np.float32 and x.shape == shape and np.isfinite(x).all(), name
+        assert np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(str(tmp_path / "a" / "loss.npy"))[0]) - rec["config"]["loss_samples_last"]) <= 1e-6
 
 
 def _torchrun_shared_gpu(args, timeout=1500, env=None):

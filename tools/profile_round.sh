@@ -1,7 +1,7 @@
 #!/bin/bash
 # Regenerate the per-round evidence under gpurun_out/<tag>/ (run on the GPU box through gpurun); tools/summarize_profiles.py condenses it
 # into the tracked profiles/<tag>_* files (+ profiles/raw/<tag>_*: the raw rocprofv3 stats and a 200-row excerpt of every kernel trace).
-#   bench.json / bench_driver_flags.json   python bench.py                 (value, roofline, cpu_baseline, fwd_only / as_loss legs)
+#   bench.json / bench_driver_flags.json   python bench.py --full / plain  (value, roofline, cpu_baseline, fwd_only / as_loss legs)
 #   stats*/                                rocprofv3 --kernel-trace --stats (per-kernel average durations), per compute type
 #   pmc_*                                  separate --pmc passes            (FETCH_SIZE, WRITE_SIZE, MFMA busy; own runs, --kernel-trace only)
 #   asloss_* / registration_*              the as-loss evaluation and the registration step (config 5): benches + kernel stats
@@ -17,7 +17,7 @@ B="python $R/bench.py"
 NOCPU="--no-cpu-baseline --no-live-pmc"
 # the profiler passes must see the training step only: no spin-up GEMMs (bench.py: spinup_ms) in the traces
 SHORT="--steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-other-dtypes --spinup-ms 0 --no-live-pmc"
-LONG="--steps 20 --warmup 5 --no-cpu-baseline --no-other-dtypes --spinup-ms 0 --no-live-pmc"
+LONG="--steps 20 --warmup 5 --full --no-cpu-baseline --no-other-dtypes --spinup-ms 0 --no-live-pmc"
 export TMPDIR=/tmp
 cd /tmp
 stats() { rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$1 -o $TAG -- "${@:2}" > $OUT/$1.out 2>&1; }
@@ -31,28 +31,28 @@ stats stats $B $LONG
 pmc3 "" $B $SHORT
 # the PMC summary must exist in profiles/ BEFORE the bench line is emitted (bench.py reads roofline.traffic from it)
 python $R/tools/summarize_profiles.py $TAG > /dev/null
-$B > $OUT/bench.json 2> $OUT/bench.err
+$B --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 $B --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2>> $OUT/bench.err     # the command the driver runs
 [ -n "$QUICK" ] && { python $R/tools/summarize_profiles.py $TAG; exit 0; }
 # compute types on the bf16 matrix cores (same step, --dtype) and the B=64 configuration of BASELINE configs 3-4
 for dt in f32x3 bf16; do
-  $B --dtype $dt $NOCPU --no-other-dtypes > $OUT/bench_$dt.json 2>> $OUT/bench.err
+  $B --dtype $dt --full $NOCPU --no-other-dtypes > $OUT/bench_$dt.json 2>> $OUT/bench.err
   stats stats_$dt $B $LONG --dtype $dt
 done
-$B --dtype bf16 --batch 64 $NOCPU --no-other-dtypes > $OUT/bench_bf16_b64.json 2>> $OUT/bench.err
-$B --batch 64 $NOCPU --no-other-dtypes > $OUT/bench_f32_b64.json 2>> $OUT/bench.err
+$B --dtype bf16 --batch 64 --full $NOCPU --no-other-dtypes > $OUT/bench_bf16_b64.json 2>> $OUT/bench.err
+$B --batch 64 --full $NOCPU --no-other-dtypes > $OUT/bench_f32_b64.json 2>> $OUT/bench.err
 stats stats_bf16_b64 $B $LONG --dtype bf16 --batch 64
 pmc3 bf16_b64_ $B $SHORT --dtype bf16 --batch 64
 { for t in "stats f32_B32" "stats_f32x3 f32x3_B32" "stats_bf16_b64 bf16_B64"; do set -- $t; echo "== $2"; python $R/tools/step_timeline.py $OUT/$1/${TAG}_kernel_trace.csv; done; } > $OUT/step_timeline.txt 2>&1
 # the step's remaining forms (each line: form, ms/step, GEMM ms/step)
 line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-28s ms_per_step %.4f  gemm_ms_per_step %s  value %.0f' % ('$1', d['ms_per_step'], (d.get('roofline') or {}).get('gemm_ms_per_step'), d['value']))"; }
 {
-  $B --steps 200 --warmup 30 $NOCPU --no-other-dtypes 2>/dev/null | line default
-  $B --steps 200 --warmup 30 $NOCPU --no-other-dtypes 2>/dev/null | line default_again
-  $B --steps 200 --warmup 30 $NOCPU --no-other-dtypes --prefetch 2>/dev/null | line prefetch
-  $B --steps 200 --warmup 30 $NOCPU --no-other-dtypes --plan 4:33:0 2>/dev/null | line dw1_tail_split
-  $B --steps 200 --warmup 30 $NOCPU --no-other-dtypes --dtype bf16 --batch 64 2>/dev/null | line bf16_b64
+  $B --steps 200 --warmup 30 --full $NOCPU --no-other-dtypes 2>/dev/null | line default
+  $B --steps 200 --warmup 30 --full $NOCPU --no-other-dtypes 2>/dev/null | line default_again
+  $B --steps 200 --warmup 30 --full $NOCPU --no-other-dtypes --prefetch 2>/dev/null | line prefetch
+  $B --steps 200 --warmup 30 --full $NOCPU --no-other-dtypes --plan 4:33:0 2>/dev/null | line dw1_tail_split
+  $B --steps 200 --warmup 30 --full $NOCPU --no-other-dtypes --dtype bf16 --batch 64 2>/dev/null | line bf16_b64
 } > $OUT/variants.txt 2>&1
 python $R/tools/gemm_bench.py --tiles 8,9,30,31,32,33 --splits 1,3 > $OUT/gemm_bench.txt 2>&1
 python $R/tools/x3_bench.py 2 3 5 > $OUT/x3_bench.txt 2>&1
@@ -74,6 +74,6 @@ python $R/tools/ramp_probe.py > $OUT/ramp_probe.txt 2>/dev/null
 # the N > 1 skeleton on one GPU: every communication form on a single-rank group, the watchdog -> fallback path, the config-4 legs
 { for e in "DPD_FORCE_DIST=0" "DPD_FORCE_DIST=1" "DPD_FORCE_DIST=1 DPD_DP_BACKEND=torch" "DPD_FORCE_DIST=1 DPD_DP_SCHEDULE=late" "DPD_FORCE_DIST=1 DPD_DP_MODE=rs_ag" "DPD_FORCE_DIST=1 DPD_DP_WIRE=bf16" "DPD_FORCE_DIST=1 DPD_DP_MODE=zero1" "DPD_FORCE_DIST=1 DPD_DP_MODE=zero1 DPD_DP_BACKEND=torch"; do
     env $e MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 $B --steps 200 --warmup 30 $NOCPU --no-other-dtypes --no-roofline 2>/dev/null | tail -1 | line "$e" ; done; } > $OUT/dp_single_rank.txt 2>&1
-( cd $R; DPD_FORCE_DIST=1 DPD_WD_INJECT_HANG=timed DPD_WD_LIMITS=timed=8 MASTER_PORT=29531 $B --steps 20 --warmup 5 $NOCPU --no-other-dtypes 2> $OUT/watchdog_fallback.err | tail -1 > $OUT/watchdog_fallback.json
-  DPD_FORCE_DIST=1 MASTER_PORT=29533 $B --cfg4 --steps 50 --warmup 10 $NOCPU 2>/dev/null | tail -1 > $OUT/bench_forced_dist_cfg4.json )
+( cd $R; DPD_FORCE_DIST=1 DPD_WD_INJECT_HANG=timed DPD_WD_LIMITS=timed=8 MASTER_PORT=29531 $B --steps 20 --warmup 5 --full $NOCPU --no-other-dtypes 2> $OUT/watchdog_fallback.err | tail -1 > $OUT/watchdog_fallback.json
+  DPD_FORCE_DIST=1 MASTER_PORT=29533 $B --cfg4 --full --steps 50 --warmup 10 $NOCPU 2>/dev/null | tail -1 > $OUT/bench_forced_dist_cfg4.json )
 python $R/tools/summarize_profiles.py $TAG
