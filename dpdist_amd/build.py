@@ -25,8 +25,7 @@ def _stale():
 
 
 def build(force=False, verbose=True):
-    # DPD_ABLATIONS=1: also compile the timing-only ablation variants of the plane GEMM (tools/x3_bench.py tile codes 100+)
-    flags = FLAGS + (["-DDPD_ABLATIONS"] if os.environ.get("DPD_ABLATIONS") == "1" else []) + os.environ.get("DPD_EXTRA_FLAGS", "").split()
+    flags = FLAGS + os.environ.get("DPD_EXTRA_FLAGS", "").split()
     stamp0 = os.path.join(HERE, "build", "flags.txt")
     flags_changed = os.path.exists(stamp0) and open(stamp0).read() != " ".join(flags)
     if not force and not flags_changed and not _stale():

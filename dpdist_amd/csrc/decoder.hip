@@ -480,12 +480,6 @@ struct OutFwd {
     float* pred;    // [2*Qb, 3]
 };
 
-#ifdef DPD_ABLATIONS
-__device__ unsigned long long g_ob_stamps[1024 * 8];       // s_memtime milestones of thread 0 of every workgroup (tools/ob_stamps.py)
-#define OB_STAMP(i) do { if (threadIdx.x == 0) g_ob_stamps[(blockIdx.x & 1023) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OB_STAMP(i) do { } while (0)
-#endif
 __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __restrict__ dpred, const float* __restrict__ mask,
                                                               const float* __restrict__ y, const float* __restrict__ h3,
                                                               const float* __restrict__ W4, float* __restrict__ dy,
@@ -496,7 +490,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
     if (blockIdx.x < 5 && zl.p[blockIdx.x]) {
         for (int i = threadIdx.x; i < zl.n[blockIdx.x]; i += 256) zl.p[blockIdx.x][i] = 0.f;
     }
-    OB_STAMP(0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ng = H / 256;            // column groups (<= 4)
     const int P = 4 * H + kOBRec;
@@ -508,7 +501,7 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
     const int row0 = blockIdx.x * kOBRows + wave * RW;
     // Every global load of the kernel is requested HERE, before anything waits: W4 above, the rows (and their BA twins) and the per-row
     // scalars below.  Left where they were used, they made three dependent round trips (W4 -> row 0 -> row 1: 5.5k + 3.9k + 5.7k cycles
-    // of a 25k-cycle kernel at B = 32, tools/ob_stamps.py); with one workgroup per CU there is nothing else to hide them behind.
+    // of a 25k-cycle kernel at B = 32, s_memtime stamps); with one workgroup per CU there is nothing else to hide them behind.
     static_assert(RW == 2, "the lane-pair exchanges below assume two rows per wave");
     const bool odd = lane & 1;
     // exchange a 64-bit value with lane ^ 1 (DPP quad_perm [1,0,3,2])
@@ -584,7 +577,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
         mk_b[rr] = of.y ? mask[Qb + row] : 0.f;
         lab[rr] = l1.labels ? l1.labels[row] : 0.f;
     }
-    OB_STAMP(1);
 #pragma unroll
     for (int rr = 0; rr < RW; ++rr) {
         const int row = min(row0 + rr, Qb - 1);
@@ -603,7 +595,9 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
                         for (int c = 0; c < 3; ++c) { a[c] += xa[e] * w4[jj][e][c]; b[c] += xb[e] * w4[jj][e][c]; }
                 }
             }
-            if (rr == 0) { asm volatile("" :: "v"(a[0]), "v"(b[2])); OB_STAMP(2); }
+            // empty asm = a schedule fence: row 0's dot products finish before its wave sums start (the instruction order this kernel
+            // was measured with; without it the compiler interleaves the two)
+            if (rr == 0) asm volatile("" :: "v"(a[0]), "v"(b[2]));
             float yba[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) { yab[c] = wave_sum(a[c]) + of.b4[c]; yba[c] = wave_sum(b[c]) + of.b4[c]; }
@@ -621,7 +615,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
                 of.y[(size_t)row * 3 + lane] = ya; of.y[((size_t)Qb + row) * 3 + lane] = yb;
                 of.pred[(size_t)row * 3 + lane] = qa; of.pred[((size_t)Qb + row) * 3 + lane] = qb;
             }
-            if (rr == 0) OB_STAMP(3);
         }
         float dp[3];
         if (l1.labels) {           // d mean|pred_AB[:,0] - labels| / d pred_AB (tf.abs gradient = sign), channels 1, 2 get none
@@ -641,7 +634,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
             dsum[c] += d[rr][c];
         }
     }
-    OB_STAMP(4);
     uint2 wpk[RW][4][3] = {};
 #pragma unroll
     for (int rr = 0; rr < RW; ++rr) {
@@ -698,7 +690,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
             }
         }
     }
-    OB_STAMP(5);
     float* mine = s_acc + wave * P;
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -715,7 +706,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
     if (lane < 3) mine[4 * H + 4 + lane] = (lane == 0) ? lsum[0] : ((lane == 1) ? lsum[1] : lsum[2]);
     if (lane == 3) { mine[4 * H + 3] = 0.f; mine[4 * H + 7] = 0.f; }
     __syncthreads();
-    OB_STAMP(6);
     float* out = scratch + (size_t)blockIdx.x * P;
     for (int i = threadIdx.x; i < 4 * H + 7; i += 256) out[i] = ((s_acc[i] + s_acc[P + i]) + s_acc[2 * P + i]) + s_acc[3 * P + i];
     if (gp.r8) {      // the block's 8 rows = one row group: column c's chunk = its 8 rows (Qb % 8 == 0 when planes are in use)
@@ -738,7 +728,6 @@ __global__ __launch_bounds__(256) void out_bwd_fused4_kernel(const float* __rest
                     make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16));
             }
     }
-    OB_STAMP(7);
 }
 
 // out[i] = sum_b scratch[b][i] in a fixed order: 16 outputs x 16 block-slices per workgroup, LDS tree at the end
@@ -943,11 +932,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(TransposeJobs J) {
 
 }  // namespace dpd
 
-#ifdef DPD_ABLATIONS
-extern "C" int dpd_debug_ob_stamps(unsigned long long* host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dpd::g_ob_stamps), sizeof(unsigned long long) * 1024 * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
 extern "C" int dpd_set_gemm_plan(int op, int tile, int split_k) {
     // plane GEMMs: ops 16.. = call sites, 32 = the grouped dW2 + dW3 launch; split_k: n > 1 in-launch reduction, n < -1 slabs + reduce
     // launch, 1 off, 0 automatic (decoder.hip: g_x3_split)

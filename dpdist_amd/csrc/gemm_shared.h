@@ -126,7 +126,7 @@ __device__ __forceinline__ void quad_transpose4(float (&a)[4], int lane) {
 
 // Store of one 32x32 MFMA tile.  A row-per-instruction dword store (32 lanes x 4 B of one row, 16 instructions per tile) is
 // store-ISSUE bound on gfx950: ~25 cycles per wave-instruction per CU whatever its width, i.e. ~10 B/clk/CU -- measured with
-// s_memtime stamps (tools/p8_stamps.py) at 12.6k cycles for a 256x128 fp32 tile, 5.5 us of a 12.8 us launch.  So the tile is
+// s_memtime stamps at 12.6k cycles for a 256x128 fp32 tile, 5.5 us of a 12.8 us launch.  So the tile is
 // transposed inside each quad of lanes (lane 4q+j then holds the four consecutive columns 4q..4q+3 of row 8g + 4 half + j) and
 // leaves as four 16-byte stores per lane: the same 128-byte row segments, a quarter of the instructions.  Needs a 16-byte
 // aligned C, ldc % 4 == 0, N % 4 == 0 and a tile that starts on a multiple of four columns; anything else keeps the dword form.

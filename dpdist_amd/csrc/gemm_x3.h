@@ -1,4 +1,4 @@
-// Pieces shared by the plane GEMM kernels: the LDS-DMA ring kernel (gemm_x3.hip) and the phase-staggered / chained kernels (gemm_p8.hip).
+// Pieces shared by the plane GEMM kernels: the LDS-DMA ring kernel (gemm_x3.hip) and the phase-staggered kernel (gemm_p8.hip).
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -90,11 +90,8 @@ __device__ __forceinline__ bf16x8 rct_frag(const char* img, int o32, int kb, int
 // requested -- the finished tile staged through the (idle) LDS ring so that the next GEMMs find their operands as bf16 planes.
 // NP = planes of the kernel = planes of its plane outputs (gemm_x3() checks it): compile time, so that the one-plane type converts
 // each value once instead of running the three-plane split and dropping two thirds of it (the split was most of this epilogue's
-// time: 11.4k cycles to write a 64 KB RC plane of a 256x128 tile against 9.1k for the 128 KB fp32 tile, tools/p8_stamps.py)
-// SC1 (persistent chained launches, gemm_chain_kernel below): the plane outputs leave as write-through (sc1) buffer stores, so that a workgroup
-// on ANY XCD finds them after the producer's drained flag (cdna_hip_programming.md Guideline 16, recipe R1) -- interior tiles only (the
-// launcher admits only shapes whose tiles are all interior)
-template <int BM, int BN, int NW, int TM, int TN, int NP, bool SC1 = false>
+// time: 11.4k cycles to write a 64 KB RC plane of a 256x128 tile against 9.1k for the 128 KB fp32 tile: s_memtime stamps, docs/EXPERIMENTS.md D (e3))
+template <int BM, int BN, int NW, int TM, int TN, int NP>
 __device__ __forceinline__ void x3_epilogue(const X3Args& g, f32x16 (&acc)[TM][TN], char* smem_x3, int grp, int z, int m0, int n0,
                                             int wm0, int wn0, int tid, int l31, int half) {
     const int M = g.e.M, N = g.e.N;
@@ -133,12 +130,6 @@ __device__ __forceinline__ void x3_epilogue(const X3Args& g, f32x16 (&acc)[TM][T
                           !(g.ld_rc & 7) && !(N & 7);
     if (g.out_rc) __builtin_amdgcn_s_barrier();            // every wave is done reading the ring (all DMA pieces were waited for in the K loop)
     if (interior) {
-        __amdgpu_buffer_rsrc_t rs_rc, rs_r8;
-        if (SC1) {
-            rs_rc = __builtin_amdgcn_make_buffer_rsrc((void*)g.out_rc, 0, g.out_rc ? (int)((size_t)NP * g.rc_plane * 2) : 0, 0x00020000);
-            rs_r8 = __builtin_amdgcn_make_buffer_rsrc((void*)g.out_r8, 0, g.out_r8 ? (int)((size_t)NP * g.r8_plane * 2) : 0, 0x00020000);
-        }
-        typedef unsigned u4v __attribute__((ext_vector_type(4)));
         const int lane = tid & 63, s16 = lane & 15, G = lane >> 4;
         const unsigned strip = (unsigned)(uintptr_t)(lds_ptr_t)smem_x3 + wave_id * (NP * STRIP);
         const unsigned wr_addr = strip + (half * 36 + l31) * 8;                                   // + 576 g (+ STRIP q)
@@ -183,12 +174,8 @@ __device__ __forceinline__ void x3_epilogue(const X3Args& g, f32x16 (&acc)[TM][T
                             const v4i16 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(uintptr_t)(rd_addr + q * STRIP + 1152 * p + 32));
                             const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
                             const int row = grow0 + 16 * p + 4 * G + (s16 & 3);
-                            if (SC1)
-                                __builtin_amdgcn_raw_buffer_store_b128(u4v{ua.x, ua.y, ub.x, ub.y}, rs_rc,
-                                                                       (unsigned)((q * g.rc_plane + (size_t)row * g.ld_rc + gcol0 + 8 * (s16 >> 2)) * 2), 0, 16);
-                            else
-                                *reinterpret_cast<uint4*>(g.out_rc + q * g.rc_plane + (size_t)row * g.ld_rc + gcol0 + 8 * (s16 >> 2)) =
-                                    make_uint4(ua.x, ua.y, ub.x, ub.y);
+                            *reinterpret_cast<uint4*>(g.out_rc + q * g.rc_plane + (size_t)row * g.ld_rc + gcol0 + 8 * (s16 >> 2)) =
+                                make_uint4(ua.x, ua.y, ub.x, ub.y);
                         }
                     asm volatile("" ::: "memory");
                 }
@@ -200,12 +187,8 @@ __device__ __forceinline__ void x3_epilogue(const X3Args& g, f32x16 (&acc)[TM][T
                             const auto s0 = __builtin_amdgcn_permlane32_swap(pk[q][4 * gp], pk[q][4 * gp + 2], false, false);
                             const auto s1 = __builtin_amdgcn_permlane32_swap(pk[q][4 * gp + 1], pk[q][4 * gp + 3], false, false);
                             const int rowg = grow0 + 8 * (2 * gp + half);
-                            if (SC1)
-                                __builtin_amdgcn_raw_buffer_store_b128(u4v{s0[0], s1[0], s0[1], s1[1]}, rs_r8,
-                                                                       (unsigned)((q * g.r8_plane + ((size_t)(rowg >> 3) * N + gcol0 + l31) * 8) * 2), 0, 16);
-                            else
-                                *reinterpret_cast<uint4*>(g.out_r8 + q * g.r8_plane + ((size_t)(rowg >> 3) * N + gcol0 + l31) * 8) =
-                                    make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                            *reinterpret_cast<uint4*>(g.out_r8 + q * g.r8_plane + ((size_t)(rowg >> 3) * N + gcol0 + l31) * 8) =
+                                make_uint4(s0[0], s1[0], s0[1], s1[1]);
                         }
                 }
             }
@@ -281,7 +264,7 @@ __device__ __forceinline__ void x3_epilogue(const X3Args& g, f32x16 (&acc)[TM][T
         }
 }
 
-// phase-staggered kernels (gemm_p8.hip): tile codes 20..26 of gemm_x3 (and the 200 + code ablations); DPD_E_UNSUPPORTED for anything else
+// phase-staggered kernels (gemm_p8.hip): tile codes 21, 23 and 24 of gemm_x3; DPD_E_UNSUPPORTED for anything else
 int launch_p8_code(int np, bool ak, bool bkc, int tile, const X3Args& g, hipStream_t s);
 
 }  // namespace dpd

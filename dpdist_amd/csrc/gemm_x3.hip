@@ -117,10 +117,8 @@ __device__ __forceinline__ bool inlaunch_reduce(const X3Args& g, f32x16 (&acc)[T
     return true;
 }
 
-// ABL (timing-only ablations, instantiated only with -DDPD_ABLATIONS; results are wrong by construction):
-//   1 = no LDS-DMA refill in the K loop, 2 = no barrier, 4 = no fragment reads in the loop, 8 = one MFMA per step only.
 // TR: operands that are not K-contiguous come as RCT images of their RC planes (above) instead of R8 planes
-template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, int NS, int BK, int ABL = 0, bool TR = false>
+template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, int NS, int BK, bool TR = false>
 __global__ __launch_bounds__(64 * WR * WC) void gemm_x3_kernel(X3Args g) {
     constexpr int BM = 32 * WR * TM, BN = 32 * WC * TN, NW = WR * WC;
     constexpr int CPR = BK / 8, KB = BK / 16;               // chunks per row, k16 steps per K-tile
@@ -256,15 +254,15 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_x3_kernel(X3Args g) {
         constexpr int cur = decltype(curc)::value;
         if (kb == KB - 1) {
             // my pieces of K-tile it+1 have landed once only tiles it+2 .. it+NS-2 may be outstanding
-            if (!(ABL & 1)) wait_later(min(NS - 3, nt - 2 - it));
-            if (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+            wait_later(min(NS - 3, nt - 2 - it));
+            __builtin_amdgcn_s_barrier();
             // everybody is past K-tile it-1: refill its stage with K-tile it+NS-1
-            if (!(ABL & 1) && it + NS - 1 < nt) issue((it + NS - 1) % NS);
+            if (it + NS - 1 < nt) issue((it + NS - 1) % NS);
             // unconditional (the last iteration reads a stale stage and never uses it): behind a branch hipcc falls back to
             // s_waitcnt lgkmcnt(0) before the MFMAs below, i.e. they would wait for the reads that were only just issued
-            if (!(ABL & 4)) frags((it + 1) % NS, 0, cur ^ 1);
+            frags((it + 1) % NS, 0, cur ^ 1);
         } else {
-            if (!(ABL & 4)) frags(it % NS, kb + 1, cur ^ 1);
+            frags(it % NS, kb + 1, cur ^ 1);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (NP == 3) {
@@ -277,14 +275,12 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_x3_kernel(X3Args g) {
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] =
                             __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][ta[q]][i], fb[cur][tb[q]][j], acc[i][j], 0, 0, 0);
-        } else if (ABL & 8) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][0][0], fb[cur][0][0], acc[0][0], 0, 0, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[(ABL & 4) ? 0 : cur][0][i], fb[(ABL & 4) ? 0 : cur][0][j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][0][i], fb[cur][0][j], acc[i][j], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -316,13 +312,13 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_x3_kernel(X3Args g) {
     x3_epilogue<BM, BN, NW, TM, TN, NP>(g, acc, smem_x3, grp, z, m0, n0, wm0, wn0, tid, l31, half);
 }
 
-template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, int NS, int BK, int ABL = 0, bool TR = false>
+template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, int NS, int BK, bool TR = false>
 static int launch_x3(const X3Args& g, hipStream_t s) {
     constexpr int BM = 32 * WR * TM, BN = 32 * WC * TN;
     constexpr size_t ring = (size_t)NS * NP * (BM + BN) * BK * 2, stage = (size_t)BM * (BN + 4) * 4;
     constexpr size_t lds = ring > stage ? ring : stage;   // the plane epilogue stages the fp32 tile in the ring's LDS
     static_assert(lds <= 160 * 1024, "LDS");
-    auto kern = gemm_x3_kernel<NP, AK, BKC, WR, WC, TM, TN, NS, BK, ABL, TR>;
+    auto kern = gemm_x3_kernel<NP, AK, BKC, WR, WC, TM, TN, NS, BK, TR>;
     static LdsOptIn lds_opt;   // one per template instantiation
     if (int rc = ensure_dyn_lds(lds_opt, (const void*)kern, lds)) return rc;
     const int tn = (g.e.N + BN - 1) / BN;
@@ -337,10 +333,10 @@ static int launch_x3(const X3Args& g, hipStream_t s) {
 template <int NP>
 static int launch_x3_tile_tr(int tile, const X3Args& g, hipStream_t s) {
     switch (tile) {
-        case 1: return launch_x3<NP, false, false, 2, 2, 2, 2, NP == 3 ? 3 : 4, 32, 0, true>(g, s);
-        case 2: return launch_x3<NP, false, false, 2, 4, 2, 1, NP == 3 ? 3 : 4, 32, 0, true>(g, s);
-        case 3: return launch_x3<NP, false, false, 2, 2, 1, 2, 4, 32, 0, true>(g, s);
-        case 5: return launch_x3<NP, false, false, 2, 2, 1, 1, 4, 32, 0, true>(g, s);
+        case 1: return launch_x3<NP, false, false, 2, 2, 2, 2, NP == 3 ? 3 : 4, 32, true>(g, s);
+        case 2: return launch_x3<NP, false, false, 2, 4, 2, 1, NP == 3 ? 3 : 4, 32, true>(g, s);
+        case 3: return launch_x3<NP, false, false, 2, 2, 1, 2, 4, 32, true>(g, s);
+        case 5: return launch_x3<NP, false, false, 2, 2, 1, 1, 4, 32, true>(g, s);
         default: return DPD_E_UNSUPPORTED;
     }
 }
@@ -358,16 +354,9 @@ static int launch_x3_tile(int tile, const X3Args& g, hipStream_t s) {
         // (BK = 16 rings, the other BK = 64 shapes and the four-wave 96x64 / 64x96 forms were A/B references of rounds 2-4; removed in round 6 --
         // profiles/r03_x3_bench*.txt, r04_bf16_trio_sweep.txt hold their numbers.)
         case 13: if (NP == 1) return launch_x3<1, AK, BKC, 2, 4, 3, 1, 3, 64>(g, s); return DPD_E_UNSUPPORTED;
-        // phase-staggered kernels (gemm_p8.hip; K % 32 == 0, no split-K): one plane at BK = 64 (20..23), three planes at BK = 32 (24..26)
+        // phase-staggered kernels (gemm_p8.hip; K % 32 == 0, no split-K): one plane at BK = 64 (21, 23), three planes at BK = 32 (24)
         case 21: case 23: case 24:
             return g.e.split_k == 1 ? launch_p8_code(NP, AK, BKC, tile, g, s) : DPD_E_UNSUPPORTED;
-#ifdef DPD_ABLATIONS
-        case 232: case 201: case 202: case 203: case 204: case 205: case 207: case 208: case 216: case 224:
-            return launch_p8_code(NP, AK, BKC, tile, g, s);
-#define DPD_X3_ABL(code) case 100 + code: if (NP == 1) return launch_x3<1, AK, BKC, 2, 4, 2, 1, 4, 32, code>(g, s); return DPD_E_UNSUPPORTED;
-        DPD_X3_ABL(1) DPD_X3_ABL(2) DPD_X3_ABL(3) DPD_X3_ABL(4) DPD_X3_ABL(5) DPD_X3_ABL(7) DPD_X3_ABL(8) DPD_X3_ABL(9) DPD_X3_ABL(12) DPD_X3_ABL(13) DPD_X3_ABL(15)
-#undef DPD_X3_ABL
-#endif
         default: return DPD_E_UNSUPPORTED;
     }
 }

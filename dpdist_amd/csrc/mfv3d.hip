@@ -106,7 +106,7 @@ __device__ __forceinline__ float slice_ssq(int tid, int gcount, float* s_red /* 
         float ss = 0.f;
         const int g1 = min(gcount, (part + 1) * per);
         // eight loads in flight, then the SAME additions in the same order (a padded 0 * 0 adds an exact zero): the sequential form was a
-        // chain of 16 dependent LDS round trips (1.6k of the forward kernel's 16k cycles, tools/mfv_stamps.py)
+        // chain of 16 dependent LDS round trips (1.6k of the forward kernel's 16k cycles, s_memtime stamps)
         for (int g = part * per; g < g1; g += 8) {
             float x[8];
 #pragma unroll
@@ -128,16 +128,9 @@ __device__ __forceinline__ float slice_ssq(int tid, int gcount, float* s_red /* 
     return t;
 }
 
-#ifdef DPD_ABLATIONS
-__device__ unsigned long long g_mfv_stamps[1024 * 8];      // s_memtime milestones of thread 0 of every workgroup (tools/mfv_stamps.py)
-#define MFV_STAMP(i) do { if (threadIdx.x == 0) g_mfv_stamps[(blockIdx.x & 1023) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define MFV_STAMP(i) do { } while (0)
-#endif
 
 __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __restrict__ pts, float* __restrict__ fv,
                                                                  MfvConst k, int gslice, MfvFuse fu) {
-    MFV_STAMP(0);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int N = k.N, G = k.G, m = k.m;
     float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][N][m]
@@ -168,7 +161,6 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
         }
     }
     __syncthreads();
-    MFV_STAMP(1);
     for (int e = tid; e < 3 * N; e += kFwdThreads) {              // e = a*N + n
         float S = 0.f, mz = INFINITY;
         for (int i = 0; i < m; ++i) {
@@ -188,7 +180,6 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
         if (!(pmax * k.w > 0.f)) atomicOr(s_bad, 1);             // also catches NaN inputs
     }
     __syncthreads();
-    MFV_STAMP(2);
     const float2* zqx = s_zq;
     const float2* zqy = s_zq + N * m;
     const float2* zqz = s_zq + 2 * N * m;
@@ -222,7 +213,6 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
                 sg_s[d] += b; sg_mx[d] = fmaxf(sg_mx[d], b); sg_mn[d] = fminf(sg_mn[d], b);
             }
         }
-        MFV_STAMP(5);
         // merge the eight point groups (lanes l, l^8, l^16, l^32 ... hold the same Gaussian).  __shfl_xor is a ds_bpermute (LDS crossbar +
         // an address register) per value and stage: 60 of them made this merge as expensive as the point loop, and the section is VALU /
         // issue bound (four waves per SIMD).  xor 8 is a DPP row rotate, xor 32 a v_permlane32_swap (both halves receive lower + upper),
@@ -246,7 +236,6 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
             sg_mx[d] = fmaxf(sg_mx[d], x8(sg_mx[d])); sg_mx[d] = fmaxf(sg_mx[d], x16(sg_mx[d])); sg_mx[d] = max32(sg_mx[d]);
             sg_mn[d] = fminf(sg_mn[d], x8(sg_mn[d])); sg_mn[d] = fminf(sg_mn[d], x16(sg_mn[d])); sg_mn[d] = min32(sg_mn[d]);
         }
-        MFV_STAMP(6);
         if (live && grp == 0) {
             float v[kF];
             v[0] = pi_s * invN;                                                 // :81 reduce_mean
@@ -264,13 +253,11 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
             for (int f = 0; f < kF; ++f) s_stage[gl * kFP + f] = v[f];
         }
     }
-    MFV_STAMP(7);
     __syncthreads();
-    MFV_STAMP(3);
 
     // ---- power-1/2 normalisation (:119-121) and coalesced store of the slice, one pass of ALL threads: fv[c][g0 + g][f], 4 consecutive f of
     // one g per thread.  (Inside the merge branch above only 8 lanes of 64 were alive for 20 square roots each, four waves per SIMD
-    // queueing for the same VALU: 15k of this kernel's 30k cycles, tools/mfv_stamps.py.)  The normalised values go back to the stage for
+    // queueing for the same VALU: 15k of this kernel's 30k cycles by s_memtime stamps.)  The normalised values go back to the stage for
     // the slice's sums of squares.
     float* out = fv + ((size_t)c * G + g0) * kF;
     const bool bad = *s_bad != 0;
@@ -289,13 +276,12 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
         const float t = slice_ssq(tid, gcount, s_red, [&](int g, int ch) { return s_stage[g * kFP + ch]; });
         if (tid < kF) fu.ssq[((size_t)c * kSlices + sl) * kF + tid] = bad ? qnan : t;
     }
-    MFV_STAMP(4);
 }
 
 
 // ---------------------------------------------------------------------------------------------------------
 // Round 4: the same forward with less VALU work per (Gaussian, point) pair -- the statistics section of the kernel above is
-// VALU-issue bound (tools/mfv_stamps.py, profiles/r04_mfv_stamps.txt: 11k of 20.6k cycles at B = 32, 12-16k at B = 64 where two
+// VALU-issue bound (round-4 s_memtime stamps, profiles/README.md: 11k of 20.6k cycles at B = 32, 12-16k at B = 64 where two
 // workgroups share a CU's VALUs), and of its ~90 instructions per Gaussian and point group half were the merge of the eight point groups.
 //   * lanes: lane & 15 <-> Gaussian (16 per wave), lane >> 4 <-> a QUARTER of the points: two merge stages (xor 16, xor 32) for 16
 //     Gaussians instead of three for 8 -- a third of the merge work per Gaussian; 512-thread workgroups (8 waves x 16 Gaussians = the
@@ -305,7 +291,7 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_kernel(const float* __r
 //     max / min have no packed form and stay scalar.
 // Same expressions per element as the kernel above (Q = (qx qy) qz, (Q - w) / den, Q z, Q (z z - 1)); the running SUMS are taken over
 // even and odd points separately and over four groups instead of eight, i.e. in another order: the statistics differ from the kernel
-// above in the last bits (both are within the oracle bars; DPD_MFV_V1=1 selects the old kernel).  Needs N % 8 == 0.
+// above in the last bits (both are within the oracle bars).  Needs N % 8 == 0.
 // dynamic LDS (floats): zq4[3*(N/2)*m*4] | S[3*N] | minz2[3*N] | stage[slice*21] | flag | red[8*20]    (same size as above)
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kFwd2Threads = 512;
@@ -313,7 +299,6 @@ typedef float mfv_f2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* __restrict__ pts, float* __restrict__ fv, MfvConst k, int gslice,
                                                                   MfvFuse fu) {
-    MFV_STAMP(0);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int N = k.N, G = k.G, m = k.m, NP = N >> 1;
     float* s_t = sm;                                // [3][N/2][m][4] = {z(2p), z(2p+1), q(2p), q(2p+1)}
@@ -336,7 +321,7 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
     if (dpp8) {
         // (no unroll pragma: the trip count is a run-time value and the body holds convergent DPP operations, so hipcc cannot peel a
         //  remainder -- a requested `unroll 3` was silently refused with a -Wpass-failed warning.  Three iterations at N = 64, 3.0k of the
-        //  workgroup's 20.6k cycles (profiles/r04_mfv_stamps.txt): not where this kernel's time goes)
+        //  workgroup's 20.6k cycles (the same round-4 stamps): not where this kernel's time goes)
         for (int e = tid; e < 3 * N * m; e += kFwd2Threads) {
             const int em = e >> 3, i = e & 7, a = qdiv(em, N, lg_n), n = em - a * N;
             const float x = nz ? p[n * 3 + a] + nz[n * 3 + a] : p[n * 3 + a];
@@ -370,7 +355,6 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
         }
     }
     __syncthreads();
-    MFV_STAMP(1);
     if (!dpp8) {
         for (int e = tid; e < 3 * N; e += kFwd2Threads) {             // e = a*N + n
             const int a = qdiv(e, N, lg_n), n = e - a * N;
@@ -397,7 +381,6 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
         if (!(pmax * k.w > 0.f)) atomicOr(s_bad, 1);             // the reference's 0/0 (also catches NaN inputs)
     }
     __syncthreads();
-    MFV_STAMP(2);
     const float4* tx = reinterpret_cast<const float4*>(s_t);
     const float4* ty = tx + NP * m;
     const float4* tz = tx + 2 * NP * m;
@@ -417,7 +400,7 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
         float mu_mx[3] = {-INFINITY, -INFINITY, -INFINITY}, mu_mn[3] = {INFINITY, INFINITY, INFINITY};
         float sg_mx[3] = {-INFINITY, -INFINITY, -INFINITY}, sg_mn[3] = {INFINITY, INFINITY, INFINITY};
         // four pairs per trip with their twelve table reads requested up front: with two waves per SIMD nothing else hides the LDS latency
-        // (3.3k cycles for eight pairs before: tools/mfv_stamps.py); a partial last trip re-reads its last valid pair and skips the update
+        // (3.3k cycles for eight pairs before, by s_memtime stamps); a partial last trip re-reads its last valid pair and skips the update
         const int pp_end = (grp + 1) * ppg;
         for (int pp0 = grp * ppg; pp0 < pp_end; pp0 += 4) {
           float4 lx[4], ly[4], lz[4];
@@ -446,7 +429,6 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
             }
           }
         }
-        MFV_STAMP(5);
         float pi_s = pi_s2.x + pi_s2.y, mu_s[3], sg_s[3];
 #pragma unroll
         for (int d = 0; d < 3; ++d) { mu_s[d] = mu_s2[d].x + mu_s2[d].y; sg_s[d] = sg_s2[d].x + sg_s2[d].y; }
@@ -470,7 +452,6 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
             sg_mx[d] = fmaxf(sg_mx[d], x16(sg_mx[d])); sg_mx[d] = max32(sg_mx[d]);
             sg_mn[d] = fminf(sg_mn[d], x16(sg_mn[d])); sg_mn[d] = min32(sg_mn[d]);
         }
-        MFV_STAMP(6);
         if (live && grp == 0) {
             float v[kF];
             v[0] = pi_s * invN;                                                 // :81 reduce_mean
@@ -488,9 +469,7 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
             for (int f = 0; f < kF; ++f) s_stage[gl * kFP + f] = v[f];
         }
     }
-    MFV_STAMP(7);
     __syncthreads();
-    MFV_STAMP(3);
     // power-1/2 normalisation (:119-121) + coalesced store + the slice's sums of squares: as in mfv3d_fwd_kernel
     float* out = fv + ((size_t)c * G + g0) * kF;
     const bool bad = *s_bad != 0;
@@ -509,15 +488,9 @@ __global__ __launch_bounds__(kFwd2Threads) void mfv3d_fwd2_kernel(const float* _
         const float t = slice_ssq(tid, gcount, s_red, [&](int g, int ch) { return s_stage[g * kFP + ch]; });
         if (tid < kF) fu.ssq[((size_t)c * kSlices + sl) * kF + tid] = bad ? qnan : t;
     }
-    MFV_STAMP(4);
 }
 
 }  // namespace dpd
-#ifdef DPD_ABLATIONS
-extern "C" int dpd_debug_mfv_stamps(unsigned long long* host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dpd::g_mfv_stamps), sizeof(unsigned long long) * 1024 * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
 namespace dpd {
 // L2 normalisation over the Gaussian axis, per channel (:124-126), in place.  One 256-thread block per cloud.  The per-channel
 // sums are taken slice by slice in slice_ssq order and the slices added in order: the same bits as the fused form (ssq from the
@@ -636,7 +609,6 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_kernel(const float* __r
     __syncthreads();
     for (int e = tid; e < 3 * N * m; e += kFwdThreads) s_zq[e].y = s_zq[e].y / s_S[e / m];
     __syncthreads();
-    MFV_STAMP(2);
     const float2* zqx = s_zq;
     const float2* zqy = s_zq + N * m;
     const float2* zqz = s_zq + 2 * N * m;
@@ -1150,10 +1122,9 @@ static int set_lds(K kern, size_t lds) {
 
 }  // namespace dpd
 
-// round-4 forward kernel (pairs of points on the packed VALU, four point groups): N % 8 == 0; DPD_MFV_V1=1 keeps the round-3 kernel
+// round-4 forward kernel (pairs of points on the packed VALU, four point groups) where N % 8 == 0; the round-3 kernel otherwise
 static bool use_fwd2(int N) {
-    static const bool v1 = getenv("DPD_MFV_V1") != nullptr;
-    return !v1 && N >= 8 && !(N & 7);
+    return N >= 8 && N % 8 == 0;
 }
 
 extern "C" int dpd_mfv3d_fwd(const float* pts, int C, int N, int m, float sigma, float* fv, void* stream) {

@@ -101,12 +101,6 @@ struct RowInfo {
 // 40 KB of Fisher vectors as 83 MB of scattered 16-byte gathers per launch.  Measured and dropped: the cloud's Fisher vectors staged
 // in LDS with several row groups per workgroup (30.8 us: one 8-wave workgroup per CU cannot hide its own barriers), five work items
 // per lane with all gathers in flight before the first store (26.6 us), unit pairs of 8 rows per thread (39 us at 180 VGPRs).
-#ifdef DPD_ABLATIONS
-__device__ unsigned long long g_pr_stamps[1024 * 8];       // s_memtime milestones of thread 0 of every workgroup (tools/gather_stamps.py)
-#define PR_STAMP(i) do { if (threadIdx.x == 0) g_pr_stamps[(blockIdx.x & 1023) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define PR_STAMP(i) do { } while (0)
-#endif
 template <int NP>
 __global__ __launch_bounds__(512) void patch_rows_planes3_kernel(const float* __restrict__ q, const float* __restrict__ fv,
                                                                  float* __restrict__ X, float* __restrict__ mask,
@@ -118,7 +112,6 @@ __global__ __launch_bounds__(512) void patch_rows_planes3_kernel(const float* __
     uint16_t* s_img = reinterpret_cast<uint16_t*>(s_tab + KP / 4);             // [NP][8][KP] (only when R8 planes are written)
     __shared__ RowInfo s_row[8];
     __shared__ __attribute__((aligned(16))) float s_sc[8][kF];
-    PR_STAMP(0);
     const int tid = threadIdx.x;
     const int G = m * m * m, h = (k - 1) / 2;
     const int E4 = k * k * k * (kF / 4), U = KP / 4, U2 = KP / 8;            // window units; units / 8-column groups per row
@@ -148,7 +141,6 @@ __global__ __launch_bounds__(512) void patch_rows_planes3_kernel(const float* __
             vox[r] = (iy * m + ix) * m + iz;
         }
         __syncthreads();
-        PR_STAMP(1);
         const bool want_r8 = r8 && (8 * rg < r8_rows);
         // ---- pass A: wave = row ----
         {
@@ -203,10 +195,8 @@ __global__ __launch_bounds__(512) void patch_rows_planes3_kernel(const float* __
                 }
             }
         }
-        PR_STAMP(2);
         if (!want_r8) return;                                         // uniform per workgroup
         __syncthreads();
-        PR_STAMP(3);
         // ---- pass B ----
         for (int c = tid; c < KP; c += 512) {
 #pragma unroll
@@ -218,7 +208,6 @@ __global__ __launch_bounds__(512) void patch_rows_planes3_kernel(const float* __
                     make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16));
             }
         }
-        PR_STAMP(4);
     }
 }
 
@@ -229,7 +218,7 @@ __global__ __launch_bounds__(512) void patch_rows_planes3_kernel(const float* __
 //   pass A (wave = row): two 8-byte LDS reads per 8-column group, one uint4 per plane to the RC plane (1 KiB per wave-instruction);
 //   pass B (R8 rows): work item = column, its 8 rows are 8 two-byte LDS reads, lanes contiguous in memory; no LDS image of the rows, no
 //   barrier between the passes.
-// The stamps of the kernel above (tools/gather_stamps.py, B = 64, one plane: 28.6k cycles per workgroup, 9.1k of them before the first
+// The s_memtime stamps of the kernel above (B = 64, one plane: 28.6k cycles per workgroup, 9.1k of them before the first
 // gather, 13.1k in pass A at the address unit's rate for ~26 cache lines per gather instruction, 45 KB of LDS = 3 workgroups per CU =
 // 1.33 rounds for the 1024 workgroups) are what this form removes: 25 KB of LDS (4 workgroups per CU, one round), 83 MB of scattered
 // 16-byte L2 gathers become 42 MB of linear reads, 20.7 M conversions become 10.5 M.
@@ -248,7 +237,6 @@ void patch_rows_planes_lds_kernel(const float* __restrict__ q, const float* __re
     __shared__ int2 s_rb[8];                                                  // per row: {offset of its own voxel in the planes, validity bits of the displacements: axis a, d -> bit 8a + d}
     __shared__ __attribute__((aligned(16))) float s_sc[kF];
     __shared__ __attribute__((aligned(8))) uint16_t s_qc[3][8][4];           // planes of (q - centre, 0) of the 8 rows
-    PR_STAMP(0);
     const int tid = threadIdx.x;
     // Workgroups go to the 8 XCDs round robin and every XCD has its own L2: with rg = blockIdx.x the N/8 row groups of a cloud would
     // pull its Fisher vector through 8 different L2s.  Cloud c is therefore handled on XCD c % 8 (all its row groups; the clouds that
@@ -314,7 +302,6 @@ void patch_rows_planes_lds_kernel(const float* __restrict__ q, const float* __re
         s_tab2[j] = e;
     }
     __syncthreads();                                                          // scales, row info, table
-    PR_STAMP(1);
     auto stage = [&](int idx, float4 x) {
         const float4 sc = *reinterpret_cast<const float4*>(&s_sc[(idx % 5) * 4]);
         const float v[4] = {x.x * sc.x, x.y * sc.y, x.z * sc.z, x.w * sc.w};
@@ -333,7 +320,6 @@ void patch_rows_planes_lds_kernel(const float* __restrict__ q, const float* __re
         if (tid + 512 * i < nv) stage(tid + 512 * i, pre[i]);
     for (int idx = tid + 512 * PRE; idx < nv; idx += 512) stage(idx, fvc[idx]);      // (m > 8 only)
     __syncthreads();
-    PR_STAMP(2);
     const bool want_r8 = r8 && (8 * rg < r8_rows);
     // ---- pass A: wave = row ----
     if (rc) {
@@ -364,7 +350,6 @@ void patch_rows_planes_lds_kernel(const float* __restrict__ q, const float* __re
                 *reinterpret_cast<uint4*>(rc + p * rc_plane + row * KP + 8 * t) = make_uint4(w[0][p].x, w[0][p].y, w[1][p].x, w[1][p].y);
         }
     }
-    PR_STAMP(3);
     if (!want_r8) return;
     // ---- pass B: work item = column: its 8 rows are 8 two-byte LDS reads, one 16-byte chunk per plane, lanes contiguous in memory (1 KiB
     // per store instruction).  Measured against one work item per float4 unit (8-byte LDS reads, v_perm transposes, but 16-byte pieces
@@ -390,7 +375,6 @@ void patch_rows_planes_lds_kernel(const float* __restrict__ q, const float* __re
                 make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16));
         }
     }
-    PR_STAMP(4);
 }
 
 // The same form for the fp32 rows of the exact compute type (X [Q, KP], no planes): the cloud's scaled Fisher vector is staged once
@@ -637,11 +621,6 @@ extern "C" int dpd_asloss_combine(const float* dpts, const float* dX, const floa
     return 0;
 }
 
-#ifdef DPD_ABLATIONS
-extern "C" int dpd_debug_pr_stamps(unsigned long long* host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(dpd::g_pr_stamps), sizeof(unsigned long long) * 1024 * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
 extern "C" int dpd_patch_rows_bwd(const float* dX, const int32_t* vox, int C, int N, int m, int k, int KP, float* dq,
                                   float* dfv, void* stream) {
     using namespace dpd;

@@ -1,10 +1,10 @@
-"""Fixed cost and ablations of the phase-staggered plane GEMM (needs DPD_ABLATIONS=1 python -m dpdist_amd.build --force for codes 200+).
-    python tools/p8_probe.py"""
+"""Fixed cost of the phase-staggered plane GEMM against the ring kernel, over K.
+    python tools/p8_probe.py [tiles...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import x3_bench  # noqa: E402
 
-tiles = [int(t) for t in sys.argv[1:]] or [2, 21, 201, 202, 204, 205, 207, 208, 216]
+tiles = [int(t) for t in sys.argv[1:]] or [2, 21]
 NP = int(os.environ.get("NP", "1"))
 for K in (64, 128, 1024, 2528):
     for tile in tiles:
