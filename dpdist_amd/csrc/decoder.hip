@@ -7,22 +7,11 @@
 // the 3-wide output layer and the bias gradients are small HBM-bound kernels in this file.
 // Algorithmic work per query row (H = 1024): 4 663 296 MAC forward.  Activations h1,h2,h3 [Q,H] stay in HBM
 // (16.8 MB each at Q = 4096, resident in the 256 MiB Infinity Cache) for the backward pass.
-#include "gemm_shared.h"
+#include <initializer_list>
+
+#include "gemm_x3.h"
 
 namespace dpd {
-
-int gemm_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-             int ldc, const float* bias, const float* gate, int epilogue, int split_k, int tile, void* ws,
-             size_t ws_bytes, hipStream_t s, float* colsum = nullptr, const float* A2 = nullptr, const float* B2 = nullptr,
-             float* C2 = nullptr, const ColsumTwoStep* cs2 = nullptr);
-
-int gemm_x3(int np, int a_fmt, int b_fmt, int M, int N, int K, const uint16_t* A, int lda, long a_plane, const uint16_t* B,
-            int ldb, long b_plane, float* C, int ldc, const float* bias, const float* gate, int epilogue, int tile,
-            hipStream_t s, float* colsum, const X3Out* out = nullptr, const X3Extra* ex = nullptr, int split_k = 1, void* ws = nullptr,
-            size_t ws_bytes = 0, const uint16_t* gate16 = nullptr, int gate16_r8 = 0, void* red_cnt = nullptr, int red_cnt_words = 0);
-int split_planes(const float* src, int R, int C, int ld, int np, uint16_t* rc, int ld_rc, long rc_plane, uint16_t* r8,
-                 long r8_plane, hipStream_t s);
-int split_planes_multi(SplitJobs jobs, hipStream_t s);
 
 // process-wide GEMM plan (tile, split_k) per call site; 0 = automatic.  The only global state of the library:
 // a tuning knob (dpd_set_gemm_plan), never needed for correctness.
@@ -63,67 +52,121 @@ static size_t plane_bytes(int dtype, int Q, int KP, int H) {
 
 // Automatic split-K of a plane weight-gradient GEMM: enough slices that the launch has about two 128x128 workgroups per CU (their
 // 64 KiB LDS rings let two co-reside: one wave of tiles alone cannot keep the LDS-DMA ring of a CU full), each with >= 1024 deep K.
-static int x3_auto_split(int np, int tile, int M, int N, int K) {
-    if (np != 1 || tile < 1 || tile > 5) return 1;
-    const int bm = (tile == 3 || tile == 5) ? 64 : 128, bn = (tile == 4 || tile == 5) ? 64 : 128;
-    const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+static int x3_auto_split(int np, X3Tile t, int M, int N, int K) {
+    if (np != 1 || !t.ring) return 1;
+    const long tiles = (long)((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
     int split = (int)(480 / (tiles > 0 ? tiles : 1));
     while (split > 1 && K / split < 1024) --split;
     return split < 1 ? 1 : (split > 4 ? 4 : split);
 }
 
-// In-launch split-K parks the raw accumulators of every slice in TILE-PADDED slabs (gemm_x3.hip: tiles * split * bm * bn floats): the largest
-// split <= `split` whose slabs fit `slab_bytes` for problems of rows[0 .. nprob) x N (with small H the base workspace holds
-// fewer slabs than the automatic split asked for, and the call failed with DPD_E_WORKSPACE instead of running unsplit)
-static int x3_fit_split(int tile, int split, const int* rows, int nprob, int N, size_t slab_bytes) {
-    if (split <= 1 || tile < 1 || tile > 5) return split;
-    const int bm = (tile == 3 || tile == 5) ? 64 : 128, bn = (tile == 4 || tile == 5) ? 64 : 128;
-    size_t tiles = 0;
-    for (int i = 0; i < nprob; ++i) tiles += (size_t)((rows[i] + bm - 1) / bm) * ((N + bn - 1) / bn);
-    while (split > 1 && (tiles * split * bm * bn * sizeof(float) > slab_bytes || tiles > kRedCntBytes / 8)) --split;
-    return split;
+// Split-K plan of the plane weight gradients (TN, plain products; 1-3 grouped problems of rows[0 .. nprob) x N, contraction K = query
+// rows): the ONE place that turns a requested split (g_x3_split: 0 automatic, n > 1 in-launch, n < -1 slabs + reduce launch, 1 off)
+// into what gemm_x3 gets.  `base` / `base_bytes` = the base workspace (base_ws_bytes), NULL / 0 when the caller's workspace does not
+// hold it: its last kRedCntBytes are the arrival words of the in-launch reduction, everything before them the slabs.
+struct X3SplitPlan {
+    int split = 1;
+    void* slab = nullptr;
+    size_t slab_bytes = 0;
+    void* cnt = nullptr;     // arrival words: the in-launch form
+};
+static X3SplitPlan x3_plan_split(int np, int tile, int request, const int* rows, int nprob, int N, int K, void* base, size_t base_bytes) {
+    X3SplitPlan p;
+    if (!base || base_bytes <= kRedCntBytes) return p;
+    const size_t slab_bytes = base_bytes - kRedCntBytes;
+    const X3Tile t = x3_tile(tile);
+    int split = request;
+    if (split == 0) {   // automatic: the grouped problems counted as one of the summed rows
+        int sum = 0;
+        for (int i = 0; i < nprob; ++i) sum += rows[i];
+        split = x3_auto_split(np, t, sum, N, K);
+    }
+    // In-launch split-K parks the raw accumulators of every slice in TILE-PADDED slabs (gemm_x3.hip: tiles * split * bm * bn floats):
+    // the largest split <= `split` whose slabs fit (with small H the base workspace holds fewer slabs than the automatic
+    // split asked for, and the call failed with DPD_E_WORKSPACE instead of running unsplit)
+    if (split > 1 && t.ring) {
+        const size_t tiles = x3_tile_count(t, rows, nprob, N);
+        while (split > 1 && (tiles * split * t.bm * t.bn * sizeof(float) > slab_bytes || tiles > kRedCntBytes / 8)) --split;
+    }
+    const bool inlaunch = split > 1 && t.ring;
+    if (!inlaunch) split = split < -1 ? -split : 1;   // the other tiles: only the round-2 form
+    if (split == 1 || x3_last_slice_empty(K, split)) return p;
+    p.split = split; p.slab = base; p.slab_bytes = slab_bytes;
+    if (inlaunch) p.cnt = (char*)base + slab_bytes;
+    return p;
+}
+static void set_split(X3Call& c, const X3SplitPlan& p) {
+    c.split_k = p.split; c.ws = p.slab; c.ws_bytes = p.slab_bytes; c.red_cnt = p.cnt; c.red_cnt_words = (int)(kRedCntBytes / 8);
 }
 
-// Apl / Bpl: operand planes that already exist (else the fp32 operand is split into `scr`); out: plane outputs.
-static int gemm_dt(int dtype, int op, int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,
-                   int ldb, float* C, int ldc, const float* bias, const float* gate, int epilogue, void* ws, size_t ws_bytes,
-                   Scratch scr, hipStream_t s, float* colsum = nullptr, const void* Apl = nullptr, const void* Bpl = nullptr,
-                   const X3Out* out = nullptr, const ColsumTwoStep* cs2 = nullptr, const void* gate16 = nullptr, int gate16_r8 = 0) {
-    const int ra = transA ? K : M, ca = transA ? M : K;   // stored shape of A, B
-    const int rb = transB ? N : K, cb = transB ? K : N;
-    const bool planes_ok = dtype != 0 && !(K % 32) && !(ra & 7) && !(ca & 7) && !(rb & 7) && !(cb & 7) && !(transA && transB);
+// One dense product of the decoder in the compute type `dtype`, with the tile / split of call site `op`
+struct GemmDtCall {
+    int dtype = 0, op = 0;
+    int transA = 0, transB = 0;
+    int M = 0, N = 0, K = 0;
+    const float* A = nullptr;
+    int lda = 0;
+    const float* B = nullptr;
+    int ldb = 0;
+    float* C = nullptr;
+    int ldc = 0;
+    const float* bias = nullptr;
+    const float* gate = nullptr;
+    int epilogue = EPI_NONE;
+    void* ws = nullptr;           // fp32: split-K slabs; plane types: the base workspace (x3_plan_split)
+    size_t ws_bytes = 0;
+    Scratch scr{nullptr, 0};
+    hipStream_t s = nullptr;
+    float* colsum = nullptr;
+    const void* Apl = nullptr;    // operand planes that already exist (else the fp32 operand is split into `scr`)
+    const void* Bpl = nullptr;
+    X3Out out;                    // plane outputs
+    const ColsumTwoStep* cs2 = nullptr;
+    const void* gate16 = nullptr;
+    int gate16_r8 = 0;
+};
+static int gemm_dt(const GemmDtCall& c) {
+    const int M = c.M, N = c.N, K = c.K;
+    const int ra = c.transA ? K : M, ca = c.transA ? M : K;   // stored shape of A, B
+    const int rb = c.transB ? N : K, cb = c.transB ? K : N;
+    const bool planes_out = c.out.rc || c.out.r8;
+    const bool planes_ok = c.dtype != 0 && !(K % 32) && !(ra & 7) && !(ca & 7) && !(rb & 7) && !(cb & 7) && !(c.transA && c.transB);
     if (!planes_ok) {   // exact fp32 (also for shapes the plane kernels do not take)
-        if (Apl || Bpl || out || (gate16 && !gate)) return DPD_E_UNSUPPORTED;   // callers only pass planes for shapes planes_shape_ok() accepts
-        const int split = (dtype == 0) ? g_plan_split[op] : 1;
-        int tile = g_plan_tile[op];
+        if (c.Apl || c.Bpl || planes_out || (c.gate16 && !c.gate)) return DPD_E_UNSUPPORTED;   // callers only pass planes for shapes planes_shape_ok() accepts
+        GemmF32Call f;
+        f.transA = c.transA; f.transB = c.transB; f.M = M; f.N = N; f.K = K;
+        f.A = c.A; f.lda = c.lda; f.B = c.B; f.ldb = c.ldb; f.C = c.C; f.ldc = c.ldc;
+        f.bias = c.bias; f.gate = c.gate; f.epilogue = c.epilogue;
+        f.split_k = (c.dtype == 0 && !c.colsum) ? g_plan_split[c.op] : 1;
+        f.tile = g_plan_tile[c.op];
         // the 128x128 one-workgroup-per-CU kernels need >= ~200 tiles to fill the chip (B = 32 forward); smaller batches
         // (as-loss mode at the PCRNet batch of 16: M = 2048 -> 128 tiles) run the 64x64 kernel, 3 workgroups per CU
         const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-        if (tile == 9 && tiles128 < 200) tile = 8;
+        if (f.tile == 9 && tiles128 < 200) f.tile = 8;
         // register-streamed NN products: once there are two 128x128 tiles per CU, 64x64 wave tiles (half the operand loads per
         // flop) keep two waves per SIMD as well -- measured at B = 64: family 0.75 -> 0.85 of peak, step 1.206 -> 1.081 ms
-        if (tile == 32 && tiles128 >= 512 && !transA && !transB) tile = 30;
-        return gemm_f32(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, gate, epilogue, colsum ? 1 : split, tile, ws, ws_bytes,
-                        s, colsum, nullptr, nullptr, nullptr, cs2);
+        if (f.tile == 32 && tiles128 >= 512 && !c.transA && !c.transB) f.tile = 30;
+        f.ws = c.ws; f.ws_bytes = c.ws_bytes; f.s = c.s; f.colsum = c.colsum; f.cs2 = c.cs2;
+        return gemm_f32(f);
     }
-    if (cs2) return DPD_E_UNSUPPORTED;
-    const int np = dtype == 1 ? 3 : 1;
+    if (c.cs2) return DPD_E_UNSUPPORTED;
+    const int np = c.dtype == 1 ? 3 : 1;
     const size_t ae = (size_t)M * K, be = (size_t)K * N;
-    const size_t need = (size_t)np * 2 * ((Apl ? 0 : ae) + (Bpl ? 0 : be));
-    if (need && (!scr.p || scr.bytes < need)) return DPD_E_WORKSPACE;
-    const uint16_t* Ap = (const uint16_t*)Apl;
-    const uint16_t* Bp = (const uint16_t*)Bpl;
-    uint16_t* cursor = (uint16_t*)scr.p;
+    const size_t need = (size_t)np * 2 * ((c.Apl ? 0 : ae) + (c.Bpl ? 0 : be));
+    if (need && (!c.scr.p || c.scr.bytes < need)) return DPD_E_WORKSPACE;
+    const uint16_t* Ap = (const uint16_t*)c.Apl;
+    const uint16_t* Bp = (const uint16_t*)c.Bpl;
+    uint16_t* cursor = (uint16_t*)c.scr.p;
     if (!Ap) {
-        if (!A) return DPD_E_NULL;
-        if (int rc = split_planes(A, ra, ca, lda, np, transA ? nullptr : cursor, ca, (long)ae, transA ? cursor : nullptr, (long)ae, s))
+        if (!c.A) return DPD_E_NULL;
+        if (int rc = split_planes(c.A, ra, ca, c.lda, np, c.transA ? nullptr : cursor, ca, (long)ae, c.transA ? cursor : nullptr, (long)ae, c.s))
             return rc;
         Ap = cursor;
         cursor += (size_t)np * ae;
     }
     if (!Bp) {
-        if (!B) return DPD_E_NULL;
-        if (int rc = split_planes(B, rb, cb, ldb, np, transB ? cursor : nullptr, cb, (long)be, transB ? nullptr : cursor, (long)be, s))
+        if (!c.B) return DPD_E_NULL;
+        if (int rc = split_planes(c.B, rb, cb, c.ldb, np, c.transB ? cursor : nullptr, cb, (long)be, c.transB ? nullptr : cursor, (long)be, c.s))
             return rc;
         Bp = cursor;
     }
@@ -135,29 +178,22 @@ static int gemm_dt(int dtype, int op, int transA, int transB, int M, int N, int 
     // one plane (bf16) and enough rows for one 256x128 workgroup per CU (B = 64: 8192 x 1024 -> 256 tiles): the phase-staggered
     // BK = 64 kernel (gemm_p8_kernel, tile 21).  Measured on the forward shapes, profiles/r03_x3_bench_p8.txt: layer 1 53.2 -> 48.8 us,
     // layers 2/3 28.1 -> 27.0 us; the backward shapes (M = 4096: 128 such tiles) stay on the 128x128 ring kernel
-    if (np == 1 && !transA && blocks(256, 128) >= 224) tile = 21;
+    if (np == 1 && !c.transA && blocks(256, 128) >= 224) tile = 21;
     // three planes: the same schedule at BK = 32 on 128x128 tiles (tile 24) wherever the ring kernel ran 128x128 tiles: layer 1 at
     // B = 32 132 -> 118 us, layers 2/3 52.6 -> 50.0 us, dW1 88 -> 79 us (tools/p8_probe.py, NP=3)
     if (np == 3 && tile == 2) tile = 24;
-    if (np == 1 && g_x3_tile[op] && (g_x3_tile[op] >= 20 || !(K % 64))) tile = g_x3_tile[op];   // tuning override (dpd_set_gemm_plan, ops 16..24)
-    if (np == 3 && g_x3_tile[op] >= 24 && g_x3_tile[op] <= 26) tile = g_x3_tile[op];
-    // plane weight gradients (TN, plain product): split-K with the reduction inside the launch when the tiles alone leave CUs idle
-    // (`ws` = the slab region of the base workspace, its last kRedCntBytes the arrival words)
-    int split = 1;
-    void* cnt = nullptr;
-    if (transA && !transB && epilogue == 0 && !colsum && !out && C && ws && ws_bytes > kRedCntBytes) {
-        split = g_x3_split[op];
-        if (split == 0) split = x3_auto_split(np, tile, M, N, K);
-        if (split > 1 && tile >= 1 && tile <= 5) split = x3_fit_split(tile, split, &M, 1, N, ws_bytes - kRedCntBytes);
-        if (split > 1 && tile >= 1 && tile <= 5) cnt = (char*)ws + ws_bytes - kRedCntBytes;
-        else if (split < -1) split = -split;
-        else split = 1;
-        const int chunk = (((K + split - 1) / split) + 63) / 64 * 64;
-        if (split > 1 && chunk * (split - 1) >= K) { split = 1; cnt = nullptr; }
-    }
-    return gemm_x3(np, transA, !transB, M, N, K, Ap, ca, (long)ae, Bp, cb, (long)be, C, ldc, bias, gate, epilogue, tile, s, colsum,
-                   out, nullptr, split, split > 1 ? ws : nullptr, split > 1 ? ws_bytes - kRedCntBytes : 0,
-                   (const uint16_t*)gate16, gate16_r8, cnt, (int)(kRedCntBytes / 8));
+    const int xt = g_x3_tile[c.op];   // tuning override (dpd_set_gemm_plan, ops 16..24)
+    if (np == 1 && xt && (xt >= 20 || !(K % 64))) tile = xt;
+    if (np == 3 && xt >= 24 && xt <= 26) tile = xt;
+    X3Call x;
+    x.np = np; x.a_fmt = c.transA; x.b_fmt = !c.transB; x.M = M; x.N = N; x.K = K;
+    x.A = Ap; x.lda = ca; x.a_plane = (long)ae; x.B = Bp; x.ldb = cb; x.b_plane = (long)be;
+    x.C = c.C; x.ldc = c.ldc; x.bias = c.bias; x.gate = c.gate; x.epilogue = c.epilogue; x.tile = tile; x.s = c.s;
+    x.colsum = c.colsum; x.out = c.out; x.gate16 = (const uint16_t*)c.gate16; x.gate16_r8 = c.gate16_r8;
+    // plane weight gradients (TN, plain product): split-K when the tiles alone leave CUs idle
+    if (c.transA && !c.transB && c.epilogue == EPI_NONE && !c.colsum && !planes_out && c.C)
+        set_split(x, x3_plan_split(np, tile, g_x3_split[c.op], &M, 1, N, K, c.ws, c.ws_bytes));
+    return gemm_x3(x);
 }
 
 // `pl` is honoured only for these shapes (everything the fused producers and the plane GEMMs assume)
@@ -953,6 +989,11 @@ static size_t base_ws_bytes(int KP, int H) {
     const size_t cols = dpd::colsum_ws_floats(H, 3) * sizeof(float);
     return (slabs + cols + 255) / 256 * 256 + dpd::kRedCntBytes;
 }
+// the base workspace when `ws` holds it, else 0
+static size_t base_ws_or_0(const void* ws, size_t ws_bytes, int KP, int H) {
+    const size_t base = base_ws_bytes(KP, H);
+    return (ws && ws_bytes >= base) ? base : 0;
+}
 // plane scratch = the tail of the workspace
 static dpd::Scratch scratch_of(void* ws, size_t ws_bytes, int KP, int H) {
     const size_t base = base_ws_bytes(KP, H);
@@ -1067,22 +1108,25 @@ extern "C" int dpd_decoder_fwd(const float* X, const float* mask, int Q, int KP,
     hipStream_t s = (hipStream_t)stream;
     const Scratch scr = scratch_of(ws, ws_bytes, KP, H);
     // layer 1..3: h = relu(in W + b)   (tf_util.conv2d: conv2d + bias_add + relu, utils/tf_util.py:213-227)
-    if (pl) {   // operands from / results to the persistent planes (no conversion passes)
-        X3Out o1 = make_out(pl, pl->h1_rc, Q, pl->h1_r8, pl->Qb, H), o2 = make_out(pl, pl->h2_rc, Q, pl->h2_r8, pl->Qb, H);
-        const bool w1 = o1.rc || o1.r8, w2 = o2.rc || o2.r8;
-        if (int rc = gemm_dt(dtype, OP_FWD_L1, 0, 0, Q, H, KP, X, KP, p->W1p, H, h1, H, p->b1, nullptr, 2, nullptr, 0, scr, s, nullptr,
-                             pl->X_rc, pl->W1_r8, w1 ? &o1 : nullptr)) return rc;
-        if (int rc = gemm_dt(dtype, OP_FWD_L23, 0, 0, Q, H, H, h1, H, p->W2, H, h2, H, p->b2, nullptr, 2, nullptr, 0, scr, s, nullptr,
-                             pl->h1_rc, pl->W2_r8, w2 ? &o2 : nullptr)) return rc;
-        X3Out o3 = make_out(pl, pl->h3_rc, Q, nullptr, 0, H);
-        if (int rc = gemm_dt(dtype, OP_FWD_L23, 0, 0, Q, H, H, h2, H, p->W3, H, h3, H, p->b3, nullptr, 2, nullptr, 0, scr, s, nullptr,
-                             pl->h2_rc, pl->W3_r8, h3_plane ? &o3 : nullptr)) return rc;
-    } else {
-        if (dtype != 0 && !scr.p) return DPD_E_WORKSPACE;
-        if (int rc = gemm_dt(dtype, OP_FWD_L1, 0, 0, Q, H, KP, X, KP, p->W1p, H, h1, H, p->b1, nullptr, 2, nullptr, 0, scr, s)) return rc;
-        if (int rc = gemm_dt(dtype, OP_FWD_L23, 0, 0, Q, H, H, h1, H, p->W2, H, h2, H, p->b2, nullptr, 2, nullptr, 0, scr, s)) return rc;
-        if (int rc = gemm_dt(dtype, OP_FWD_L23, 0, 0, Q, H, H, h2, H, p->W3, H, h3, H, p->b3, nullptr, 2, nullptr, 0, scr, s)) return rc;
+    GemmDtCall l1, l2, l3;
+    for (GemmDtCall* c : {&l1, &l2, &l3}) {
+        c->dtype = dtype; c->op = OP_FWD_L23; c->M = Q; c->N = H; c->K = H; c->lda = H; c->ldb = H; c->ldc = H;
+        c->epilogue = EPI_BIAS_RELU; c->scr = scr; c->s = s;
     }
+    l1.op = OP_FWD_L1; l1.K = KP; l1.lda = KP;
+    l1.A = X; l1.B = p->W1p; l1.bias = p->b1; l1.C = h1;
+    l2.A = h1; l2.B = p->W2; l2.bias = p->b2; l2.C = h2;
+    l3.A = h2; l3.B = p->W3; l3.bias = p->b3; l3.C = h3;
+    if (pl) {   // operands from / results to the persistent planes (no conversion passes)
+        l1.Apl = pl->X_rc; l1.Bpl = pl->W1_r8; l1.out = make_out(pl, pl->h1_rc, Q, pl->h1_r8, pl->Qb, H);
+        l2.Apl = pl->h1_rc; l2.Bpl = pl->W2_r8; l2.out = make_out(pl, pl->h2_rc, Q, pl->h2_r8, pl->Qb, H);
+        l3.Apl = pl->h2_rc; l3.Bpl = pl->W3_r8;
+        if (h3_plane) l3.out = make_out(pl, pl->h3_rc, Q, nullptr, 0, H);
+    } else if (dtype != 0 && !scr.p) {
+        return DPD_E_WORKSPACE;
+    }
+    for (const GemmDtCall* c : {&l1, &l2, &l3})
+        if (int rc = gemm_dt(*c)) return rc;
     if (!y) return 0;
     DPD_LAUNCH(out_fwd_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, h3, p->W4, p->b4, mask, y, pred, Q, H);
     DPD_CHECK_LAUNCH();
@@ -1140,7 +1184,6 @@ extern "C" int dpd_decoder_bwd_data(const float* dpred, const float* mask, const
     if (!p->W1p || !p->W2 || !p->W3 || !p->W4) return DPD_E_NULL;
     if (Qb <= 0 || KP <= 0 || H <= 0) return DPD_E_DIM;
     if ((H & 63) || (KP & 3) || dtype < 0 || dtype > 2) return DPD_E_UNSUPPORTED;
-    if (phases <= 0 || phases > 31) return DPD_E_DIM;
     hipStream_t s = (hipStream_t)stream;
     const Scratch scr = scratch_of(ws, ws_bytes, KP, H);
     pl = usable_planes(pl, dtype, pl ? pl->Q : 0, Qb, KP, H);
@@ -1222,7 +1265,18 @@ extern "C" int dpd_decoder_bwd_data(const float* dpred, const float* mask, const
             DPD_CHECK_LAUNCH();
         }
     }
-    // g2 = (g3 W3^T) * [h2 > 0] ;  g1 = (g2 W2^T) * [h1 > 0];  db2 / db1 = column sums, fused into the epilogue
+    // g2 = (g3 W3^T) * [h2 > 0] ;  g1 = (g2 W2^T) * [h1 > 0];  db2 / db1 = column sums, fused into the epilogue;
+    // as-loss mode: gradient w.r.t. the gathered rows, dX = g1 W1p^T  [Qb,KP]
+    GemmDtCall d3, d2, dx;
+    for (GemmDtCall* c : {&d3, &d2, &dx}) {
+        c->dtype = dtype; c->op = OP_BWD_DH; c->transB = 1; c->M = Qb; c->N = H; c->K = H; c->lda = H; c->ldb = H; c->ldc = H;
+        c->epilogue = EPI_GATE; c->scr = scr; c->s = s;
+    }
+    d3.A = g3; d3.B = p->W3; d3.C = g2; d3.gate = h2; d3.colsum = db2;
+    d2.A = g2; d2.B = p->W2; d2.C = g1; d2.gate = h1; d2.colsum = db1;
+    dx.op = OP_BWD_DX; dx.N = KP; dx.ldc = KP; dx.epilogue = EPI_NONE;
+    dx.A = g1; dx.B = p->W1p; dx.C = dX;
+    ColsumTwoStep c2{}, c1{};
     if (pl) {
         // g3 from a kernel that wrote no planes (this call's unfused output layer, or -- phases without 1 and an fp32 g3 given --
         // dpd_decoder_out_asloss): one conversion launch for the layouts the planes keep
@@ -1231,40 +1285,32 @@ extern "C" int dpd_decoder_bwd_data(const float* dpred, const float* mask, const
             if (int rc = split_planes(g3, Qb, H, H, pl->np, (uint16_t*)pl->g3_rc, H, (long)Qb * H, (uint16_t*)pl->g3_r8, (long)Qb * H, s))
                 return rc;
         }
-        X3Out o2 = make_out(pl, pl->g2_rc, Qb, pl->g2_r8, Qb, H), o1 = make_out(pl, dX ? pl->g1_rc : nullptr, Qb, pl->g1_r8, Qb, H);
-        const bool w2 = o2.rc || o2.r8, w1 = o1.rc || o1.r8;
-        if (phases & 2)
-            if (int rc = gemm_dt(dtype, OP_BWD_DH, 0, 1, Qb, H, H, g3, H, p->W3, H, g2, H, nullptr, h2, 3, nullptr, 0, scr, s, db2, pl->g3_rc,
-                                 pl->W3_rc, w2 ? &o2 : nullptr, nullptr, h2 ? nullptr : (pl->h2_r8 ? pl->h2_r8 : pl->h2_rc), pl->h2_r8 != nullptr)) return rc;
-        if (phases & 4)
-            if (int rc = gemm_dt(dtype, OP_BWD_DH, 0, 1, Qb, H, H, g2, H, p->W2, H, g1, H, nullptr, h1, 3, nullptr, 0, scr, s, db1, pl->g2_rc,
-                                 pl->W2_rc, w1 ? &o1 : nullptr, nullptr, h1 ? nullptr : (pl->h1_r8 ? pl->h1_r8 : pl->h1_rc), pl->h1_r8 != nullptr)) return rc;
-        if (dX && (phases & 4)) {
-            if (int rc = gemm_dt(dtype, OP_BWD_DX, 0, 1, Qb, KP, H, g1, H, p->W1p, H, dX, KP, nullptr, nullptr, 0, nullptr, 0, scr, s, nullptr,
-                                 pl->g1_rc, pl->W1_rc, nullptr)) return rc;
+        // the ReLU gate from the fp32 activation or, without one, from its bf16 plane
+        d3.Apl = pl->g3_rc; d3.Bpl = pl->W3_rc; d3.out = make_out(pl, pl->g2_rc, Qb, pl->g2_r8, Qb, H);
+        d3.gate16 = h2 ? nullptr : (pl->h2_r8 ? pl->h2_r8 : pl->h2_rc); d3.gate16_r8 = pl->h2_r8 != nullptr;
+        d2.Apl = pl->g2_rc; d2.Bpl = pl->W2_rc; d2.out = make_out(pl, dX ? pl->g1_rc : nullptr, Qb, pl->g1_r8, Qb, H);
+        d2.gate16 = h1 ? nullptr : (pl->h1_r8 ? pl->h1_r8 : pl->h1_rc); d2.gate16_r8 = pl->h1_r8 != nullptr;
+        dx.Apl = pl->g1_rc; dx.Bpl = pl->W1_rc;
+    } else {
+        // exact-fp32 path with transposed weight copies: the NT products become NN (weights read row-coalesced)
+        if (dtype == 0 && p->W3T) { d3.op = OP_BWD_DH_T; d3.transB = 0; d3.B = p->W3T; }
+        if (dtype == 0 && p->W2T) { d2.op = OP_BWD_DH_T; d2.transB = 0; d2.B = p->W2T; }
+        if (dtype == 0 && p->W1pT) { dx.op = OP_BWD_DX_T; dx.transB = 0; dx.B = p->W1pT; dx.ldb = KP; }
+        // deterministic db2 / db1: the dH GEMMs store 32-row partial column sums of g2 / g1 into sg->db_partials ([2][ceil(Qb/32)][H]);
+        // dpd_decoder_bwd_weights[_pair] called with the same pointer adds them up.  Needs the register-streamed kernels.
+        if (float* dbp = (sg && dtype == 0) ? sg->db_partials : nullptr) {
+            if (!(f32_tile_rs(g_plan_tile[d3.op]) && f32_tile_rs(g_plan_tile[d2.op]))) return DPD_E_UNSUPPORTED;
+            c2.part_out = dbp; c1.part_out = dbp + (size_t)((Qb + 31) / 32) * H;
+            d3.colsum = nullptr; d3.cs2 = &c2;
+            d2.colsum = nullptr; d2.cs2 = &c1;
         }
-        return 0;
     }
-    // exact-fp32 path with transposed weight copies: the NT products become NN (weights read row-coalesced)
-    const bool t3 = dtype == 0 && p->W3T, t2 = dtype == 0 && p->W2T, t1 = dtype == 0 && p->W1pT;
-    // deterministic db2 / db1: the dH GEMMs store 32-row partial column sums of g2 / g1 into sg->db_partials ([2][ceil(Qb/32)][H]);
-    // dpd_decoder_bwd_weights[_pair] called with the same pointer adds them up.  Needs the register-streamed kernels.
-    float* dbp = (sg && sg->db_partials && dtype == 0) ? sg->db_partials : nullptr;
-    const int nrb = (Qb + 31) / 32;
-    const int op3 = t3 ? OP_BWD_DH_T : OP_BWD_DH, op2 = t2 ? OP_BWD_DH_T : OP_BWD_DH;
-    if (dbp && !(g_plan_tile[op3] >= 30 && g_plan_tile[op2] >= 30)) return DPD_E_UNSUPPORTED;
-    ColsumTwoStep c2{}, c1{};
-    c2.part_out = dbp; c1.part_out = dbp ? dbp + (size_t)nrb * H : nullptr;
     if (phases & 2)
-        if (int rc = gemm_dt(dtype, op3, 0, t3 ? 0 : 1, Qb, H, H, g3, H, t3 ? p->W3T : p->W3, H, g2, H, nullptr, h2, 3,
-                             nullptr, 0, scr, s, dbp ? nullptr : db2, nullptr, nullptr, nullptr, dbp ? &c2 : nullptr)) return rc;
+        if (int rc = gemm_dt(d3)) return rc;
     if (phases & 4)
-        if (int rc = gemm_dt(dtype, op2, 0, t2 ? 0 : 1, Qb, H, H, g2, H, t2 ? p->W2T : p->W2, H, g1, H, nullptr, h1, 3,
-                             nullptr, 0, scr, s, dbp ? nullptr : db1, nullptr, nullptr, nullptr, dbp ? &c1 : nullptr)) return rc;
-    if (dX && (phases & 4)) {   // as-loss mode: gradient w.r.t. the gathered rows, dX = g1 W1p^T  [Qb,KP]
-        if (int rc = gemm_dt(dtype, t1 ? OP_BWD_DX_T : OP_BWD_DX, 0, t1 ? 0 : 1, Qb, KP, H, g1, H, t1 ? p->W1pT : p->W1p, t1 ? KP : H, dX, KP,
-                             nullptr, nullptr, 0, nullptr, 0, scr, s)) return rc;
-    }
+        if (int rc = gemm_dt(d2)) return rc;
+    if (dX && (phases & 4))
+        if (int rc = gemm_dt(dx)) return rc;
     return 0;
 }
 
@@ -1308,18 +1354,18 @@ extern "C" int dpd_decoder_bwd_weights(int layer, const float* act, int lda, con
     // of the B operand the GEMM streams anyway (deterministic, no atomics, no extra launch).
     // With db_partials (the 32-row partial column sums dpd_decoder_bwd_data stored for this layer's g: layers 1 and 2) the bias
     // gradient is finished by this GEMM's first-row-block waves: deterministic, no atomics, no extra launch.
-    const int tile_w = g_plan_tile[op];
-    const bool free_db = db && db_partials && (layer == 1 || layer == 2) && dtype == 0 && tile_w >= 30 && tile_w <= 39 && !(Qb % 32);
+    const bool free_db = db && db_partials && (layer == 1 || layer == 2) && dtype == 0 && f32_tile_rs(g_plan_tile[op]) && !(Qb % 32);
     if (db && db_partials && !free_db) return DPD_E_UNSUPPORTED;
     ColsumTwoStep cs{};
     cs.part_in = db_partials ? db_partials + (layer == 1 ? (size_t)((Qb + 31) / 32) * Nout : 0) : nullptr;
     cs.out = db; cs.nparts = (Qb + 31) / 32;
-    // plane compute types: the slab region + arrival words of the base workspace serve the in-launch split-K of gemm_dt
-    const size_t base_b = base_ws_bytes(Kin > Nout ? Kin : Nout, Nout);
-    const size_t gemm_ws = dtype == 0 ? slab_bytes : ((ws && ws_bytes >= base_b) ? base_b : 0);
-    if (int rc = gemm_dt(dtype, op, 1, 0, Kin, Nout, Qb, act, lda, g, Nout, dW, Nout, nullptr, nullptr, 0, ws, gemm_ws, scr, s, nullptr,
-                         apl, gpl, nullptr, free_db ? &cs : nullptr))
-        return rc;
+    GemmDtCall c;
+    c.dtype = dtype; c.op = op; c.transA = 1; c.M = Kin; c.N = Nout; c.K = Qb;
+    c.A = act; c.lda = lda; c.B = g; c.ldb = Nout; c.C = dW; c.ldc = Nout;
+    // fp32: the split-K slabs; plane compute types: the base workspace serves the split-K of gemm_dt
+    c.ws = ws; c.ws_bytes = dtype == 0 ? slab_bytes : base_ws_or_0(ws, ws_bytes, Kin > Nout ? Kin : Nout, Nout);
+    c.scr = scr; c.s = s; c.Apl = apl; c.Bpl = gpl; c.cs2 = free_db ? &cs : nullptr;
+    if (int rc = gemm_dt(c)) return rc;
     if (!db || free_db) return 0;   // bias gradient not wanted / already produced
     float* part = (float*)((char*)ws + slab_bytes);
     DPD_LAUNCH(colsum_stage1<0>, dim3((Nout + 63) / 64, kColChunks), dim3(256), 0, s, g, Nout, (const float*)nullptr,
@@ -1355,52 +1401,41 @@ extern "C" int dpd_decoder_bwd_weights_pair(const float* actA, const float* gA, 
             // traffic and the reduce launch cost more than the shorter K loop saves).
             // Round 4: split-K with the reduction INSIDE the launch (gemm_x3.hip: inlaunch_reduce; g_x3_pair_split > 1 or automatic):
             // 2 x 64 tiles of 128x128 x 3-4 slices = two workgroups per CU instead of one on half of them.
-            const long pe = (long)Kin * Qb, ge = (long)Qb * Nout;
-            int split = g_x3_pair_split, ptile = g_x3_pair_tile;
-            void* cnt = nullptr;
-            const size_t base_b = base_ws_bytes(Kin > Nout ? Kin : Nout, Nout);
-            const bool ws_ok = ws && ws_bytes >= base_b;
-            if (split == 0) {                                     // automatic
-                if (!ptile) ptile = pl->np == 1 ? 2 : 3;
-                split = (ws_ok && ptile <= 5) ? x3_auto_split(pl->np, ptile, 2 * Kin, Nout, Qb) : 1;
-                if (split == 1 && !g_x3_pair_tile) ptile = 3;
-            }
-            size_t slab_b = ws_bytes;
-            if (split > 1 && ws_ok) {                             // ... with no more slices than the slab region holds (tile-padded)
-                const int rows2[2] = {Kin, Kin};
-                split = x3_fit_split(ptile ? ptile : 2, split, rows2, 2, Nout, base_b - kRedCntBytes);
-                if (split == 1 && !g_x3_pair_tile) ptile = 3;
-            }
-            if (split > 1) {                                      // in-launch reduction
-                const int chunk = (((Qb + split - 1) / split) + 63) / 64 * 64;
-                if (!ws_ok || ptile > 5 || chunk * (split - 1) >= Qb) split = 1;
-                else { cnt = (char*)ws + base_b - kRedCntBytes; slab_b = base_b - kRedCntBytes; if (!ptile) ptile = 2; }
-            } else if (split < -1) {                              // slabs + reduce launch (round 2)
-                split = -split;
-                if (Qb % (128 * split) || !ws || (size_t)2 * split * Kin * Nout * sizeof(float) > ws_bytes) split = 1;
-            } else {
-                split = 1;
-            }
-            if (!ptile) ptile = split > 1 ? 2 : 3;
-            if (ptile >= 8 && (pl->np != 1 || Qb % (64 * split))) ptile = split > 1 ? 2 : 3;
-            X3Extra ex;
-            ex.A2 = (const uint16_t*)pl->h2_r8; ex.B2 = (const uint16_t*)pl->g3_r8; ex.C2 = dWB;
-            return gemm_x3(pl->np, 1, 1, Kin, Nout, Qb, (const uint16_t*)pl->h1_r8, Kin, pe, (const uint16_t*)pl->g2_r8, Nout, ge, dWA, Nout,
-                           nullptr, nullptr, 0, ptile, (hipStream_t)stream, nullptr, nullptr, &ex, split, ws, slab_b, nullptr, 0, cnt,
-                           (int)(kRedCntBytes / 8));
+            // Without a tile from dpd_set_gemm_plan: 128x128 (tile 2) when split, the whole-K 64x128 launch (tile 3) when not.
+            int request = g_x3_pair_split;
+            if (request < -1 && Qb % (128 * -request)) request = 1;   // the round-2 form of this launch: even slices of whole 128-deep pieces
+            int tile = g_x3_pair_tile ? g_x3_pair_tile : 2;
+            const int rows2[2] = {Kin, Kin};
+            const X3SplitPlan plan = x3_plan_split(pl->np, tile, request, rows2, 2, Nout, Qb, ws, base_ws_or_0(ws, ws_bytes, Kin > Nout ? Kin : Nout, Nout));
+            if (!g_x3_pair_tile && plan.split == 1) tile = 3;
+            if (tile >= 8 && (pl->np != 1 || Qb % (64 * plan.split))) tile = plan.split > 1 ? 2 : 3;
+            X3Call x;
+            x.np = pl->np; x.a_fmt = 1; x.b_fmt = 1; x.M = Kin; x.N = Nout; x.K = Qb;
+            x.A = (const uint16_t*)pl->h1_r8; x.lda = Kin; x.a_plane = (long)Kin * Qb;
+            x.B = (const uint16_t*)pl->g2_r8; x.ldb = Nout; x.b_plane = (long)Qb * Nout;
+            x.C = dWA; x.ldc = Nout; x.tile = tile; x.s = (hipStream_t)stream;
+            x.ex.A2 = (const uint16_t*)pl->h2_r8; x.ex.B2 = (const uint16_t*)pl->g3_r8; x.ex.C2 = dWB;
+            set_split(x, plan);
+            return gemm_x3(x);
         }
-        if (int rc = gemm_dt(dtype, OP_BWD_DW23, 1, 0, Kin, Nout, Qb, actA, lda, gA, Nout, dWA, Nout, nullptr, nullptr, 0, nullptr, 0,
-                             scr, (hipStream_t)stream, nullptr, have ? pl->h1_r8 : nullptr, have ? pl->g2_r8 : nullptr, nullptr)) return rc;
-        return gemm_dt(dtype, OP_BWD_DW23, 1, 0, Kin, Nout, Qb, actB, lda, gB, Nout, dWB, Nout, nullptr, nullptr, 0, nullptr, 0, scr,
-                       (hipStream_t)stream, nullptr, have ? pl->h2_r8 : nullptr, have ? pl->g3_r8 : nullptr, nullptr);
+        // one GEMM after the other, operands split into the scratch
+        GemmDtCall c;
+        c.dtype = dtype; c.op = OP_BWD_DW23; c.transA = 1; c.M = Kin; c.N = Nout; c.K = Qb;
+        c.A = actA; c.lda = lda; c.B = gA; c.ldb = Nout; c.C = dWA; c.ldc = Nout; c.scr = scr; c.s = (hipStream_t)stream;
+        if (int rc = gemm_dt(c)) return rc;
+        c.A = actB; c.B = gB; c.C = dWB;
+        return gemm_dt(c);
     }
     int tile = g_plan_tile[OP_BWD_DW23];
-    if (!((tile == 8 || tile == 9) || (tile >= 30 && tile <= 33))) tile = 8;
-    if (dbA && !(db_partials && tile >= 30 && tile <= 33)) return DPD_E_UNSUPPORTED;   // layer 2's bias gradient from the stored partials
+    if (!(f32_tile_dma(tile) || f32_tile_rs(tile))) tile = 8;
+    if (dbA && !(db_partials && f32_tile_rs(tile))) return DPD_E_UNSUPPORTED;   // layer 2's bias gradient from the stored partials
     ColsumTwoStep cs{};
     cs.part_in = db_partials; cs.out = dbA; cs.nparts = (Qb + 31) / 32;     // (layer 2 = problem A: the first half of the scratch)
-    return gemm_f32(1, 0, Kin, Nout, Qb, actA, lda, gA, Nout, dWA, Nout, nullptr, nullptr, 0, 1, tile, nullptr, 0,
-                    (hipStream_t)stream, nullptr, actB, gB, dWB, dbA ? &cs : nullptr);
+    GemmF32Call f;
+    f.transA = 1; f.M = Kin; f.N = Nout; f.K = Qb;
+    f.A = actA; f.lda = lda; f.B = gA; f.ldb = Nout; f.C = dWA; f.ldc = Nout;
+    f.tile = tile; f.s = (hipStream_t)stream; f.A2 = actB; f.B2 = gB; f.C2 = dWB; f.cs2 = dbA ? &cs : nullptr;
+    return gemm_f32(f);
 }
 
 // dW1, dW2 and dW3 of a plane compute type in ONE grouped launch (round 4).  Every weight-gradient GEMM of the step contracts over the
@@ -1426,22 +1461,16 @@ extern "C" int dpd_decoder_bwd_weights_trio(int Qb, int KP, int H, int dtype, fl
     // workgroup -- 128x128 makes 288 tiles (32 CUs get two: 58 us), 192x128 makes 112 + 48 + 48 = 208 (36 us), 256x128 144 (44 us).
     // Measured in the bf16 step at B = 64 (profiles/r04_bf16_trio_sweep.txt): the three launches apart 71 us, grouped on 128x128
     // tiles 67 us, on 192x128 tiles 51 us (step 0.3107 -> 0.2909 ms on that box).
-    int tile = g_x3_trio_tile ? g_x3_trio_tile : ((pl->np == 1 && !(Qb % 64)) ? 13 : 2), split = g_x3_trio_split;
-    if (tile > 5 && (pl->np != 1 || split > 1 || (Qb % 64))) tile = 2;       // the BK = 64 tiles: one plane, whole K
-    void* cnt = nullptr;
-    size_t slab_b = 0;
-    if (split > 1) {
-        const size_t base_b = base_ws_bytes(KP > H ? KP : H, H);
-        const int rows3[3] = {KP, H, H};
-        if (ws && ws_bytes >= base_b) split = x3_fit_split(tile, split, rows3, 3, H, base_b - kRedCntBytes);
-        const int chunk = (((Qb + split - 1) / split) + 63) / 64 * 64;
-        if (split <= 1 || !ws || ws_bytes < base_b || chunk * (split - 1) >= Qb) split = 1;
-        else { cnt = (char*)ws + base_b - kRedCntBytes; slab_b = base_b - kRedCntBytes; }
-    }
-    X3Extra ex;
-    ex.A2 = (const uint16_t*)pl->h1_r8; ex.B2 = (const uint16_t*)pl->g2_r8; ex.C2 = dW2; ex.M2 = H;
-    ex.A3 = (const uint16_t*)pl->h2_r8; ex.B3 = (const uint16_t*)pl->g3_r8; ex.C3 = dW3; ex.M3 = H;
-    return gemm_x3(pl->np, 1, 1, KP, H, Qb, (const uint16_t*)pl->X_r8, KP, (long)KP * Qb, (const uint16_t*)pl->g1_r8, H, (long)Qb * H, dW1, H,
-                   nullptr, nullptr, 0, tile, (hipStream_t)stream, nullptr, nullptr, &ex, split, split > 1 ? ws : nullptr, slab_b, nullptr, 0,
-                   cnt, (int)(kRedCntBytes / 8));
+    int tile = g_x3_trio_tile ? g_x3_trio_tile : ((pl->np == 1 && !(Qb % 64)) ? 13 : 2);
+    if (tile > 5 && (pl->np != 1 || g_x3_trio_split > 1 || (Qb % 64))) tile = 2;       // the BK = 64 tiles: one plane, whole K
+    const int rows3[3] = {KP, H, H};
+    X3Call x;
+    x.np = pl->np; x.a_fmt = 1; x.b_fmt = 1; x.M = KP; x.N = H; x.K = Qb;
+    x.A = (const uint16_t*)pl->X_r8; x.lda = KP; x.a_plane = (long)KP * Qb;
+    x.B = (const uint16_t*)pl->g1_r8; x.ldb = H; x.b_plane = (long)Qb * H;
+    x.C = dW1; x.ldc = H; x.tile = tile; x.s = (hipStream_t)stream;
+    x.ex.A2 = (const uint16_t*)pl->h1_r8; x.ex.B2 = (const uint16_t*)pl->g2_r8; x.ex.C2 = dW2; x.ex.M2 = H;
+    x.ex.A3 = (const uint16_t*)pl->h2_r8; x.ex.B3 = (const uint16_t*)pl->g3_r8; x.ex.C3 = dW3; x.ex.M3 = H;
+    set_split(x, x3_plan_split(pl->np, tile, g_x3_trio_split, rows3, 3, H, Qb, ws, base_ws_or_0(ws, ws_bytes, KP > H ? KP : H, H)));
+    return gemm_x3(x);
 }

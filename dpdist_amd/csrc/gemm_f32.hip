@@ -17,7 +17,7 @@
 // Roofline: MFMA-bound.  Algorithmic flops = 2*M*N*K; bytes/flop of a 128x128 tile = 1/32 -> 8 B/clk/CU from L2.
 #include <mutex>
 
-#include "gemm_shared.h"
+#include "gemm_host.h"
 #include "gemm_rs.h"
 
 namespace dpd {
@@ -469,82 +469,68 @@ static int launch_cfg(const GemmArgs& g, hipStream_t s) {
 
 template <bool AK, bool BKC>
 static int launch_tile(int tile, const GemmArgs& g, hipStream_t s) {
-    if (tile >= 30 && tile <= 33) return launch_rs_tile<AK, BKC>(tile, g, s);   // register-streamed kernels (gemm_rs.h)
+    if (f32_tile_rs(tile)) return launch_rs_tile<AK, BKC>(tile, g, s);   // register-streamed kernels (gemm_rs.h)
     switch (tile) {
         // LDS-DMA ring kernels (round 1): tile 8 serves the NT forms g W^T when the caller passes no transposed weight copies, tile 9 is the
         // 128x128 reference of tools/x3_bench.py.  (The other ring / register-staged configurations were A/B references of rounds 1-3; removed
         // in round 6 -- profiles/r03_gemm_bench.txt has their numbers.)
         case 8: return launch_dma<2, 2, 3, AK, BKC>(g, s);   // LDS-DMA ring,  64x64,  256 thr, 48 KiB  (3 blocks/CU)
         case 9: return launch_dma<4, 4, 3, AK, BKC>(g, s);   // LDS-DMA ring, 128x128, 1024 thr, 96 KiB (1 block/CU)
-        case 3: return launch_cfg<64, 64, 32, AK, BKC>(g, s);   // register-staged 64x64: any K % 4 == 0 (the fallback for ragged K)
+        case kF32TileStaged: return launch_cfg<64, 64, 32, AK, BKC>(g, s);   // register-staged 64x64: any K % 4 == 0 (the fallback for ragged K)
         default: return DPD_E_UNSUPPORTED;
     }
 }
 
-int gemm_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-             int ldc, const float* bias, const float* gate, int epilogue, int split_k, int tile, void* ws,
-             size_t ws_bytes, hipStream_t s, float* colsum, const float* A2, const float* B2, float* C2, const ColsumTwoStep* cs2) {
-    if (!A || !B || !C) return DPD_E_NULL;
+int gemm_f32(const GemmF32Call& c) {
+    const int M = c.M, N = c.N, K = c.K;
+    if (!c.A || !c.B || !c.C) return DPD_E_NULL;
     // split_k == 0: "tail split" (gemm_rs.h): whole-K tiles, only the partial last round of tiles is cut along K (needs ws for
     // (pieces - 1) slabs of M*N floats; pieces <= 4).  Silently a plain launch when it does not apply.
-    bool tail_auto = false;
-    if (split_k == 0) {
-        split_k = 1;
-        tail_auto = tile >= 30 && tile <= 33 && ws && ws_bytes >= (size_t)3 * M * N * sizeof(float) && epilogue == EPI_NONE;
-    }
+    const int split_k = c.split_k ? c.split_k : 1;
+    const bool tail_auto = !c.split_k && f32_tile_rs(c.tile) && c.ws && c.ws_bytes >= (size_t)3 * M * N * sizeof(float) && c.epilogue == EPI_NONE;
     if (M <= 0 || N <= 0 || K <= 0 || split_k < 1) return DPD_E_DIM;
-    if ((K & 3) || (N & 3) || (lda & 3) || (ldb & 3) || (ldc & 3)) return DPD_E_UNSUPPORTED;
-    if (transA && (M & 3)) return DPD_E_UNSUPPORTED;
-    if (transA && transB) return DPD_E_UNSUPPORTED;
-    if ((epilogue == EPI_BIAS || epilogue == EPI_BIAS_RELU) && !bias) return DPD_E_NULL;
-    if (epilogue == EPI_GATE && !gate) return DPD_E_NULL;
-    if (epilogue < 0 || epilogue > 3) return DPD_E_UNSUPPORTED;
+    if ((K & 3) || (N & 3) || (c.lda & 3) || (c.ldb & 3) || (c.ldc & 3)) return DPD_E_UNSUPPORTED;
+    if (c.transA && (M & 3)) return DPD_E_UNSUPPORTED;
+    if (c.transA && c.transB) return DPD_E_UNSUPPORTED;
+    if ((c.epilogue == EPI_BIAS || c.epilogue == EPI_BIAS_RELU) && !c.bias) return DPD_E_NULL;
+    if (c.epilogue == EPI_GATE && !c.gate) return DPD_E_NULL;
+    if (c.epilogue < 0 || c.epilogue > 3) return DPD_E_UNSUPPORTED;
 
-    if (tile == 0) tile = 3;     // the register-staged 64x64 kernel: takes every shape
-    const bool whole_tiles = (tile == 8 || tile == 9) || (tile >= 30 && tile <= 33);   // kernels that need whole 32-deep K-tiles
+    int tile = c.tile ? c.tile : kF32TileStaged;
+    const bool whole_tiles = f32_tile_dma(tile) || f32_tile_rs(tile);   // kernels that need whole 32-deep K-tiles
     if (whole_tiles && (K % 32 != 0 || M < 4 || N < 4 || (split_k > 1 && ((K + split_k - 1) / split_k + 31) / 32 * 32 * (split_k - 1) >= K)))
-        tile = 3;   // these kernels need whole K-tiles (and a non-empty last split): fall back to the register-staged kernel
+        tile = kF32TileStaged;   // these kernels need whole K-tiles (and a non-empty last split): fall back to the register-staged kernel
     GemmArgs g{};
-    g.A = A; g.B = B; g.bias = bias; g.gate = gate;
-    g.colsum = (split_k > 1) ? nullptr : colsum;
-    g.A2 = A2; g.B2 = B2; g.C2 = C2;
-    if (tail_auto && !colsum && !A2) { g.tail_split = -1; g.tail_slab = (float*)ws; }
-    if (cs2) {   // deterministic bias gradients in two steps (register-streamed kernels only; rows of a partial block = 32)
-        if (!(tile >= 30 && tile <= 33) || (cs2->part_out && (split_k > 1 || colsum))) return DPD_E_UNSUPPORTED;
-        g.colsum_part = cs2->part_out;
-        g.colsum_part_in = cs2->part_in; g.colsum_part_in2 = cs2->part_in2;
-        g.colsum_b = cs2->out; g.colsum_b2 = cs2->out2; g.colsum_nparts = cs2->nparts;
+    g.A = c.A; g.B = c.B; g.bias = c.bias; g.gate = c.gate;
+    g.colsum = (split_k > 1) ? nullptr : c.colsum;
+    g.A2 = c.A2; g.B2 = c.B2; g.C2 = c.C2;
+    if (tail_auto && !c.colsum && !c.A2) { g.tail_split = -1; g.tail_slab = (float*)c.ws; }
+    if (c.cs2) {   // deterministic bias gradients in two steps (register-streamed kernels only; rows of a partial block = 32)
+        if (!f32_tile_rs(tile) || (c.cs2->part_out && (split_k > 1 || c.colsum))) return DPD_E_UNSUPPORTED;
+        g.colsum_part = c.cs2->part_out;
+        g.colsum_part_in = c.cs2->part_in; g.colsum_part_in2 = c.cs2->part_in2;
+        g.colsum_b = c.cs2->out; g.colsum_b2 = c.cs2->out2; g.colsum_nparts = c.cs2->nparts;
     }
-    if (A2 && (!B2 || !C2 || split_k > 1 || epilogue != EPI_NONE || colsum)) return DPD_E_UNSUPPORTED;
-    if (A2 && !whole_tiles) return DPD_E_UNSUPPORTED;   // grouped launches exist for the DMA / register-streamed kernels only
-    if (colsum && split_k > 1) return DPD_E_UNSUPPORTED;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
+    if (c.A2 && (!c.B2 || !c.C2 || split_k > 1 || c.epilogue != EPI_NONE || c.colsum)) return DPD_E_UNSUPPORTED;
+    if (c.A2 && !whole_tiles) return DPD_E_UNSUPPORTED;   // grouped launches exist for the DMA / register-streamed kernels only
+    if (c.colsum && split_k > 1) return DPD_E_UNSUPPORTED;
+    g.M = M; g.N = N; g.K = K; g.lda = c.lda; g.ldb = c.ldb;
     g.split_k = split_k;
     if (split_k > 1) {
         const int chunk = (((K + split_k - 1) / split_k) + 31) / 32 * 32;
-        if ((size_t)split_k * M * N * sizeof(float) > ws_bytes || !ws) return DPD_E_WORKSPACE;
-        g.k_chunk = chunk; g.C = (float*)ws; g.ldc = N; g.slab_stride = (long)M * N; g.epi = EPI_NONE;
+        if ((size_t)split_k * M * N * sizeof(float) > c.ws_bytes || !c.ws) return DPD_E_WORKSPACE;
+        g.k_chunk = chunk; g.C = (float*)c.ws; g.ldc = N; g.slab_stride = (long)M * N; g.epi = EPI_NONE;
     } else {
-        g.k_chunk = (K + 31) / 32 * 32; g.C = C; g.ldc = ldc; g.slab_stride = 0; g.epi = epilogue;
+        g.k_chunk = (K + 31) / 32 * 32; g.C = c.C; g.ldc = c.ldc; g.slab_stride = 0; g.epi = c.epilogue;
     }
     // profiler bracket: the GEMM kernel AND, with split-K, its reduce kernel (both belong to this GEMM)
-    struct ProfScope {
-        bool on; hipStream_t s; double fl; int form;
-        ~ProfScope() { prof_end(on, s, fl, form); }
-    } prof_scope{prof_begin(s), s, 2.0 * M * N * K, transA ? 1 : 0};
+    ProfScope prof_scope{prof_begin(c.s), c.s, 2.0 * M * N * K, c.transA ? 1 : 0};
     int rc;
-    if (!transA && !transB) rc = launch_tile<true, false>(tile, g, s);       // NN: A[M,K], B[K,N]
-    else if (!transA && transB) rc = launch_tile<true, true>(tile, g, s);    // NT: A[M,K], B[N,K]
-    else rc = launch_tile<false, false>(tile, g, s);                          // TN: A[K,M], B[K,N]
-    if (rc) return rc;
-    if (split_k > 1) {
-        const long total4 = (long)M * N / 4;
-        const int blocks = (int)((total4 + 255) / 256 < 2048 ? (total4 + 255) / 256 : 2048);
-        DPD_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)ws, split_k, (long)M * N, M,
-                           N, C, ldc, bias, gate, epilogue);
-        return (int)hipGetLastError();
-    }
-    return 0;
+    if (!c.transA && !c.transB) rc = launch_tile<true, false>(tile, g, c.s);       // NN: A[M,K], B[K,N]
+    else if (!c.transA && c.transB) rc = launch_tile<true, true>(tile, g, c.s);    // NT: A[M,K], B[N,K]
+    else rc = launch_tile<false, false>(tile, g, c.s);                             // TN: A[K,M], B[K,N]
+    if (rc || split_k == 1) return rc;
+    return splitk_reduce((const float*)c.ws, split_k, (long)M * N, M, N, c.C, c.ldc, c.bias, c.gate, c.epilogue, c.s);
 }
 
 }  // namespace dpd
@@ -565,58 +551,48 @@ extern "C" int dpd_prof_enable(int on) {
     return 0;
 }
 
-// Synchronises with the recorded events; returns the number of GEMM launches seen since dpd_prof_enable(1) and
-// fills total milliseconds / total (padded-shape) flops 2*M*N*K of those launches.
-static int prof_collect_gemm(int form, double* total_ms, double* total_flops) {
+// Synchronises with the recorded events; returns the number of launches with tag `tag` (and, form >= 0, product form `form`) seen since
+// dpd_prof_enable and fills their summed milliseconds and flops / bytes
+static int prof_collect(int tag, int form, double* total_ms, double* total) {
     using dpd::g_prof;
     std::lock_guard<std::mutex> lk(dpd::g_prof_mu);
-    double ms = 0.0, fl = 0.0;
+    double ms = 0.0, sum = 0.0;
     int n = 0;
     for (int i = 0; i < g_prof.n; ++i) {
-        if (g_prof.tag[i] != dpd::DPD_STAGE_GEMM || (form >= 0 && g_prof.form[i] != form)) continue;
+        if (g_prof.tag[i] != tag || (form >= 0 && g_prof.form[i] != form)) continue;
         if (hipEventSynchronize(g_prof.ev[2 * i + 1]) != hipSuccess) return -1;
         float t = 0.f;
         if (hipEventElapsedTime(&t, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]) != hipSuccess) return -1;
         ms += t;
-        fl += g_prof.flops[i];
+        sum += g_prof.flops[i];
         ++n;
     }
     if (total_ms) *total_ms = ms;
-    if (total_flops) *total_flops = fl;
+    if (total) *total = sum;
     return n;
 }
-extern "C" int dpd_prof_collect(double* total_ms, double* total_flops) { return prof_collect_gemm(-1, total_ms, total_flops); }
+// GEMM launches: total milliseconds / total (padded-shape) flops 2*M*N*K
+extern "C" int dpd_prof_collect(double* total_ms, double* total_flops) { return prof_collect(dpd::DPD_STAGE_GEMM, -1, total_ms, total_flops); }
 // the same for the launches of ONE product form: 0 = NN / NT (forward layers and data gradients: one kernel family), 1 = TN (weight gradients)
 extern "C" int dpd_prof_collect_form(int form, double* total_ms, double* total_flops) {
     if (form < 0 || form > 1) return DPD_E_DIM;
-    return prof_collect_gemm(form, total_ms, total_flops);
+    return prof_collect(dpd::DPD_STAGE_GEMM, form, total_ms, total_flops);
 }
 
 // The bandwidth-bound stages recorded since dpd_prof_enable(2): launches of stage `tag` (1 encoder, 2 window gather, 3 fused output
 // layer, 4 optimizer, 5 small-gradient reduction, 6 weight copies), their summed duration [ms] and ALGORITHMIC HBM bytes.
 extern "C" int dpd_prof_collect_stage(int tag, double* total_ms, double* total_bytes) {
-    using dpd::g_prof;
     if (tag <= 0 || tag >= dpd::DPD_STAGE_COUNT) return DPD_E_DIM;
-    std::lock_guard<std::mutex> lk(dpd::g_prof_mu);
-    double ms = 0.0, by = 0.0;
-    int n = 0;
-    for (int i = 0; i < g_prof.n; ++i) {
-        if (g_prof.tag[i] != tag) continue;
-        if (hipEventSynchronize(g_prof.ev[2 * i + 1]) != hipSuccess) return -1;
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]) != hipSuccess) return -1;
-        ms += t;
-        by += g_prof.flops[i];
-        ++n;
-    }
-    if (total_ms) *total_ms = ms;
-    if (total_bytes) *total_bytes = by;
-    return n;
+    return prof_collect(tag, -1, total_ms, total_bytes);
 }
 
 extern "C" int dpd_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,
                             int ldb, float* Cout, int ldc, const float* bias, const float* gate, int epilogue,
                             int split_k, int tile, void* ws, size_t ws_bytes, void* stream) {
-    return dpd::gemm_f32(transA, transB, M, N, K, A, lda, B, ldb, Cout, ldc, bias, gate, epilogue, split_k, tile, ws,
-                         ws_bytes, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, nullptr);
+    dpd::GemmF32Call c;
+    c.transA = transA; c.transB = transB; c.M = M; c.N = N; c.K = K;
+    c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.C = Cout; c.ldc = ldc;
+    c.bias = bias; c.gate = gate; c.epilogue = epilogue; c.split_k = split_k; c.tile = tile;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.s = (hipStream_t)stream;
+    return dpd::gemm_f32(c);
 }

@@ -242,32 +242,6 @@ __device__ __forceinline__ void split_chunk(const float (&v)[8], uint4 (&w)[3]) 
     for (int q = 0; q < 3; ++q) w[q] = make_uint4(u[q][0], u[q][1], u[q][2], u[q][3]);
 }
 
-// optional bf16-plane outputs of a gemm_x3 result (gemm_x3.hip): RC planes [np][M][ld_rc], R8 planes
-// [np][r8_rows/8][N][8] for the rows < r8_rows
-// out[m,n] = epi( sum_z slabs[z][m,n] ), fixed order (gemm_f32.hip); slabs are dense [M,N], N % 4 == 0
-int splitk_reduce(const float* slabs, int split_k, long slab_stride, int M, int N, float* C, int ldc, const float* bias,
-                  const float* gate, int epi, hipStream_t s);
-
-struct X3Out {
-    uint16_t* rc = nullptr;
-    uint16_t* r8 = nullptr;
-    long rc_plane = 0, r8_plane = 0;
-    int ld_rc = 0, r8_rows = 0, np = 0;
-};
-
-// further problems of a grouped plain plane-GEMM launch (gemm_x3.hip): same N, K, B layout and tile; own operands, output and rows.
-// M2 / M3 = 0: the rows of problem 0.  Problems with other rows than problem 0, and a third problem, run on the ring kernels only.
-struct X3Extra {
-    const uint16_t* A2 = nullptr;
-    const uint16_t* B2 = nullptr;
-    float* C2 = nullptr;
-    int M2 = 0;
-    const uint16_t* A3 = nullptr;
-    const uint16_t* B3 = nullptr;
-    float* C3 = nullptr;
-    int M3 = 0;
-};
-
 struct SplitJob {
     const float* src;
     uint16_t* rc;
@@ -279,11 +253,5 @@ struct SplitJobs {
     int n;
     SplitJob j[8];
 };
-
-
-// in-stream GEMM profiler (gemm_f32.hip): event pair around one GEMM (kernel + split-K reduce)
-bool prof_begin(hipStream_t s);
-// form: 0 = the contraction runs along A's rows (NN / NT: the forward and data-gradient products), 1 = TN (weight gradients)
-void prof_end(bool on, hipStream_t s, double flops, int form = 0);
 
 }  // namespace dpd

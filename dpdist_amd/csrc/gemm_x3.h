@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm_shared.h"
+#include "gemm_host.h"
 
 namespace dpd {
 
@@ -42,6 +42,33 @@ struct X3Args {
     unsigned red_gen;              // generation of this launch: a word of another generation (workspace garbage, an aborted launch) counts as 0
     int red_sc1;                   // != 0: slabs published by write-through (sc1) stores and read by sc1 loads, no release / acquire fence
 };
+
+// ---- host-side geometry of a plane GEMM launch: the ONE place that maps a tile code to its workgroup tile ------------------------
+// tile codes of the ring kernel (gemm_x3.hip): 1 = 128x128 (4 waves of 64x64), 2 = 128x128 (8 waves of 64x32), 3 = 64x128, 4 = 128x64,
+// 5 = 64x64, 13 = 192x128 (BK 64, one plane); 21 / 23 / 24 = the phase-staggered kernels of gemm_p8.hip (not listed: bm = 0)
+struct X3Tile {
+    int bm, bn;
+    bool ring;   // BK = 32 ring tile: takes the in-launch split-K reduction (inlaunch_reduce)
+};
+constexpr X3Tile x3_tile(int code) {
+    switch (code) {
+        case 1: case 2: return {128, 128, true};
+        case 3: return {64, 128, true};
+        case 4: return {128, 64, true};
+        case 5: return {64, 64, true};
+        case 13: return {192, 128, false};
+        default: return {0, 0, false};
+    }
+}
+// output tiles of the grouped problems rows[0 .. nprob) x N
+inline size_t x3_tile_count(X3Tile t, const int* rows, int nprob, int N) {
+    size_t tiles = 0;
+    for (int i = 0; i < nprob; ++i) tiles += (size_t)((rows[i] + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
+    return tiles;
+}
+// K range of one split-K slice: whole 64-deep K-tiles.  The split is usable when the last slice is not empty
+constexpr int x3_slice_len(int K, int split) { return ((K + split - 1) / split + 63) / 64 * 64; }
+constexpr bool x3_last_slice_empty(int K, int split) { return x3_slice_len(K, split) * (split - 1) >= K; }
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {

@@ -312,9 +312,10 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_x3_kernel(X3Args g) {
     x3_epilogue<BM, BN, NW, TM, TN, NP>(g, acc, smem_x3, grp, z, m0, n0, wm0, wn0, tid, l31, half);
 }
 
-template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, int NS, int BK, bool TR = false>
+template <int CODE, int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, int NS, int BK, bool TR = false>
 static int launch_x3(const X3Args& g, hipStream_t s) {
     constexpr int BM = 32 * WR * TM, BN = 32 * WC * TN;
+    static_assert(x3_tile(CODE).bm == BM && x3_tile(CODE).bn == BN && x3_tile(CODE).ring == (BK == 32), "tile table (gemm_x3.h)");
     constexpr size_t ring = (size_t)NS * NP * (BM + BN) * BK * 2, stage = (size_t)BM * (BN + 4) * 4;
     constexpr size_t lds = ring > stage ? ring : stage;   // the plane epilogue stages the fp32 tile in the ring's LDS
     static_assert(lds <= 160 * 1024, "LDS");
@@ -327,16 +328,15 @@ static int launch_x3(const X3Args& g, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-// tile codes: 1 = 128x128 (4 waves of 64x64), 2 = 128x128 (8 waves of 64x32), 3 = 64x128, 4 = 128x64, 5 = 64x64, 13 = 192x128 (BK 64, one plane);
-// 21 / 23 / 24 = the phase-staggered kernels of gemm_p8.hip
+// tile codes: gemm_x3.h (x3_tile)
 // TN products with both operands read from their RC planes (RCT images + LDS transpose reads)
 template <int NP>
 static int launch_x3_tile_tr(int tile, const X3Args& g, hipStream_t s) {
     switch (tile) {
-        case 1: return launch_x3<NP, false, false, 2, 2, 2, 2, NP == 3 ? 3 : 4, 32, true>(g, s);
-        case 2: return launch_x3<NP, false, false, 2, 4, 2, 1, NP == 3 ? 3 : 4, 32, true>(g, s);
-        case 3: return launch_x3<NP, false, false, 2, 2, 1, 2, 4, 32, true>(g, s);
-        case 5: return launch_x3<NP, false, false, 2, 2, 1, 1, 4, 32, true>(g, s);
+        case 1: return launch_x3<1, NP, false, false, 2, 2, 2, 2, NP == 3 ? 3 : 4, 32, true>(g, s);
+        case 2: return launch_x3<2, NP, false, false, 2, 4, 2, 1, NP == 3 ? 3 : 4, 32, true>(g, s);
+        case 3: return launch_x3<3, NP, false, false, 2, 2, 1, 2, 4, 32, true>(g, s);
+        case 5: return launch_x3<5, NP, false, false, 2, 2, 1, 1, 4, 32, true>(g, s);
         default: return DPD_E_UNSUPPORTED;
     }
 }
@@ -344,16 +344,16 @@ static int launch_x3_tile_tr(int tile, const X3Args& g, hipStream_t s) {
 template <int NP, bool AK, bool BKC>
 static int launch_x3_tile(int tile, const X3Args& g, hipStream_t s) {
     switch (tile) {
-        case 1: return launch_x3<NP, AK, BKC, 2, 2, 2, 2, NP == 3 ? 3 : 4, 32>(g, s);
-        case 2: return launch_x3<NP, AK, BKC, 2, 4, 2, 1, NP == 3 ? 3 : 4, 32>(g, s);
-        case 3: return launch_x3<NP, AK, BKC, 2, 2, 1, 2, 4, 32>(g, s);
-        case 4: return launch_x3<NP, AK, BKC, 2, 2, 2, 1, 4, 32>(g, s);
-        case 5: return launch_x3<NP, AK, BKC, 2, 2, 1, 1, 4, 32>(g, s);
+        case 1: return launch_x3<1, NP, AK, BKC, 2, 2, 2, 2, NP == 3 ? 3 : 4, 32>(g, s);
+        case 2: return launch_x3<2, NP, AK, BKC, 2, 4, 2, 1, NP == 3 ? 3 : 4, 32>(g, s);
+        case 3: return launch_x3<3, NP, AK, BKC, 2, 2, 1, 2, 4, 32>(g, s);
+        case 4: return launch_x3<4, NP, AK, BKC, 2, 2, 2, 1, 4, 32>(g, s);
+        case 5: return launch_x3<5, NP, AK, BKC, 2, 2, 1, 1, 4, 32>(g, s);
         // 192x128 at BK = 64 (round 4, one plane only: a 3-plane stage would not fit the LDS): the tile with the smallest BM + BN (= LDS fill bytes
         // per flop) that covers dW1 + dW2 + dW3 in at most one workgroup per CU (112 + 48 + 48 = 208 tiles): 8 waves of 96x32, 3 stages x 40 KiB.
         // (BK = 16 rings, the other BK = 64 shapes and the four-wave 96x64 / 64x96 forms were A/B references of rounds 2-4; removed in round 6 --
         // profiles/r03_x3_bench*.txt, r04_bf16_trio_sweep.txt hold their numbers.)
-        case 13: if (NP == 1) return launch_x3<1, AK, BKC, 2, 4, 3, 1, 3, 64>(g, s); return DPD_E_UNSUPPORTED;
+        case 13: if (NP == 1) return launch_x3<13, 1, AK, BKC, 2, 4, 3, 1, 3, 64>(g, s); return DPD_E_UNSUPPORTED;
         // phase-staggered kernels (gemm_p8.hip; K % 32 == 0, no split-K): one plane at BK = 64 (21, 23), three planes at BK = 32 (24)
         case 21: case 23: case 24:
             return g.e.split_k == 1 ? launch_p8_code(NP, AK, BKC, tile, g, s) : DPD_E_UNSUPPORTED;
@@ -361,105 +361,91 @@ static int launch_x3_tile(int tile, const X3Args& g, hipStream_t s) {
     }
 }
 
-// C[M,N] (fp32) = epi( op(A) op(B) ) from bf16 planes.  a_fmt/b_fmt: 0 = RC (k contiguous), 1 = R8 (k = row index),
-// 2 = RC plane of an operand whose k is its ROW index (both operands: A stored [K][M], B stored [K][N]; lda / ldb = row strides).
-int gemm_x3(int np, int a_fmt, int b_fmt, int M, int N, int K, const uint16_t* A, int lda, long a_plane, const uint16_t* B,
-            int ldb, long b_plane, float* C, int ldc, const float* bias, const float* gate, int epilogue, int tile,
-            hipStream_t s, float* colsum, const X3Out* out, const X3Extra* ex, int split_k, void* ws,
-            size_t ws_bytes, const uint16_t* gate16, int gate16_r8, void* red_cnt, int red_cnt_words) {
-    const uint16_t* A2 = ex ? ex->A2 : nullptr;
-    const uint16_t* B2 = ex ? ex->B2 : nullptr;
-    float* C2 = ex ? ex->C2 : nullptr;
-    const int M2 = (ex && ex->M2) ? ex->M2 : M;
-    const bool three = ex && ex->A3;
-    const bool uneven = A2 && (M2 != M || three);      // problems of different rows / a third problem: ring kernels, TN only
-    if (A2 && (!B2 || !C2 || out || colsum || epilogue != EPI_NONE)) return DPD_E_UNSUPPORTED;
-    if (three && (!A2 || !ex->B3 || !ex->C3 || ex->M3 <= 0)) return DPD_E_UNSUPPORTED;
-    if (uneven && (a_fmt != 1 || b_fmt != 1 || tile < 1 || (tile > 5 && tile != 13) || (M2 & 7) || (three && (ex->M3 & 7))))
+// (X3Call: gemm_host.h)
+int gemm_x3(const X3Call& c) {
+    const int M = c.M, N = c.N, K = c.K;
+    const X3Extra& ex = c.ex;
+    const int M2 = ex.M2 ? ex.M2 : M;
+    const bool three = ex.A3 != nullptr;
+    const bool uneven = ex.A2 && (M2 != M || three);      // problems of different rows / a third problem: ring kernels, TN only
+    const bool planes_out = c.out.rc || c.out.r8;
+    int tile = c.tile;
+    if (ex.A2 && (!ex.B2 || !ex.C2 || planes_out || c.colsum || c.epilogue != EPI_NONE)) return DPD_E_UNSUPPORTED;
+    if (three && (!ex.A2 || !ex.B3 || !ex.C3 || ex.M3 <= 0)) return DPD_E_UNSUPPORTED;
+    if (uneven && (c.a_fmt != 1 || c.b_fmt != 1 || tile < 1 || (tile > 5 && tile != 13) || (M2 & 7) || (three && (ex.M3 & 7))))
         return DPD_E_UNSUPPORTED;
-    const int nprob = A2 ? (three ? 3 : 2) : 1;
+    const int nprob = ex.A2 ? (three ? 3 : 2) : 1;
+    const int rows[3] = {M, M2, ex.M3};
     // split-K (deterministic slabs in `ws` + the reduce kernel of gemm_f32.hip): plain products only (the dW shapes: K = query rows
     // is long, M x N gives too few 128x128 tiles for 256 CUs)
-    // red_cnt != NULL: the slices are reduced INSIDE the launch (inlaunch_reduce above; ring kernels, tiles 1-5); `ws` then holds the
+    // red_cnt != NULL: the slices are reduced INSIDE the launch (inlaunch_reduce above; ring tiles); `ws` then holds the
     // raw accumulator slabs of every slice (tile-padded) and red_cnt [>= tiles] arrival words of 8 bytes
-    int chunk = K;
+    const int split_k = c.split_k > 1 ? c.split_k : 1;
     if (split_k > 1) {
-        chunk = (((K + split_k - 1) / split_k) + 63) / 64 * 64;
-        if (out || colsum || epilogue != EPI_NONE || !C || chunk * (split_k - 1) >= K) return DPD_E_UNSUPPORTED;
-        if (!red_cnt && (uneven || !ws || (size_t)split_k * M * N * sizeof(float) * nprob > ws_bytes)) return DPD_E_WORKSPACE;
-    } else {
-        split_k = 1;
+        if (planes_out || c.colsum || c.epilogue != EPI_NONE || !c.C || x3_last_slice_empty(K, split_k)) return DPD_E_UNSUPPORTED;
+        if (!c.red_cnt && (uneven || !c.ws || (size_t)split_k * M * N * sizeof(float) * nprob > c.ws_bytes)) return DPD_E_WORKSPACE;
     }
-    const bool planes_out = out && (out->rc || out->r8);
-    if (!A || !B || (!C && !planes_out)) return DPD_E_NULL;
-    if (planes_out && (out->np != np || (M & 7) || (N & 7) || (out->r8_rows & 7) || (out->rc && (out->ld_rc & 7))))
+    if (!c.A || !c.B || (!c.C && !planes_out)) return DPD_E_NULL;
+    if (planes_out && (c.out.np != c.np || (M & 7) || (N & 7) || (c.out.r8_rows & 7) || (c.out.rc && (c.out.ld_rc & 7))))
         return DPD_E_UNSUPPORTED;
     if (M <= 0 || N <= 0 || K <= 0) return DPD_E_DIM;
-    if (np != 1 && np != 3) return DPD_E_UNSUPPORTED;
-    if ((K % 32) || (N & 3) || (ldc & 3) || (lda & 7) || (ldb & 7)) return DPD_E_UNSUPPORTED;
+    if (c.np != 1 && c.np != 3) return DPD_E_UNSUPPORTED;
+    if ((K % 32) || (N & 3) || (c.ldc & 3) || (c.lda & 7) || (c.ldb & 7)) return DPD_E_UNSUPPORTED;
     if (tile == 13 && (K % 64)) return DPD_E_UNSUPPORTED;   // BK = 64 kernels take whole 64-deep K-tiles
-    if ((epilogue == EPI_BIAS || epilogue == EPI_BIAS_RELU) && !bias) return DPD_E_NULL;
-    if (epilogue == EPI_GATE && !gate && !gate16) return DPD_E_NULL;
-    if (epilogue < 0 || epilogue > 3) return DPD_E_UNSUPPORTED;
-    if (a_fmt && b_fmt == 0) return DPD_E_UNSUPPORTED;   // (R8, RC) never occurs in the decoder
-    if ((a_fmt == 2) != (b_fmt == 2)) return DPD_E_UNSUPPORTED;   // the transpose-read form exists for TN with both operands as RC planes
-    if (a_fmt == 2 && ((M & 7) || (N & 7))) return DPD_E_UNSUPPORTED;
+    if ((c.epilogue == EPI_BIAS || c.epilogue == EPI_BIAS_RELU) && !c.bias) return DPD_E_NULL;
+    if (c.epilogue == EPI_GATE && !c.gate && !c.gate16) return DPD_E_NULL;
+    if (c.epilogue < 0 || c.epilogue > 3) return DPD_E_UNSUPPORTED;
+    if (c.a_fmt && c.b_fmt == 0) return DPD_E_UNSUPPORTED;   // (R8, RC) never occurs in the decoder
+    if ((c.a_fmt == 2) != (c.b_fmt == 2)) return DPD_E_UNSUPPORTED;   // the transpose-read form exists for TN with both operands as RC planes
+    if (c.a_fmt == 2 && ((M & 7) || (N & 7))) return DPD_E_UNSUPPORTED;
     X3Args g{};
-    g.e.C = C; g.e.bias = bias; g.e.gate = gate; g.e.gate16 = gate ? nullptr : gate16; g.e.gate16_r8 = gate16_r8 && !(M & 7); g.e.colsum = colsum;
-    g.e.M = M; g.e.N = N; g.e.K = K; g.e.ldc = ldc; g.e.epi = epilogue;
-    g.e.split_k = 1; g.e.k_chunk = K; g.e.slab_stride = 0;
-    g.A = A; g.B = B; g.a_plane = a_plane; g.b_plane = b_plane; g.lda = lda; g.ldb = ldb;
-    g.A2 = A2; g.B2 = B2; g.C2 = C2;
+    g.e.C = c.C; g.e.bias = c.bias; g.e.gate = c.gate; g.e.gate16 = c.gate ? nullptr : c.gate16; g.e.gate16_r8 = c.gate16_r8 && !(M & 7);
+    g.e.colsum = c.colsum;
+    g.e.M = M; g.e.N = N; g.e.K = K; g.e.ldc = c.ldc; g.e.epi = c.epilogue;
+    g.e.split_k = split_k; g.e.k_chunk = split_k > 1 ? x3_slice_len(K, split_k) : K; g.e.slab_stride = 0;
+    g.A = c.A; g.B = c.B; g.a_plane = c.a_plane; g.b_plane = c.b_plane; g.lda = c.lda; g.ldb = c.ldb;
+    g.A2 = ex.A2; g.B2 = ex.B2; g.C2 = ex.C2;
     if (uneven) {      // TN on R8 planes: the row count of a problem is its A's k-group row length and (with K) its plane stride
         g.M2 = M2; g.lda2 = M2; g.a_plane2 = (long)K * M2;
-        if (three) { g.A3 = ex->A3; g.B3 = ex->B3; g.C3 = ex->C3; g.M3 = ex->M3; g.lda3 = ex->M3; g.a_plane3 = (long)K * ex->M3; }
+        if (three) { g.A3 = ex.A3; g.B3 = ex.B3; g.C3 = ex.C3; g.M3 = ex.M3; g.lda3 = ex.M3; g.a_plane3 = (long)K * ex.M3; }
     }
     if (tile == 0) tile = 1;
-    if (split_k > 1 && red_cnt) {
-        int bm, bn;
-        switch (tile) {
-            case 1: case 2: bm = 128; bn = 128; break;
-            case 3: bm = 64; bn = 128; break;
-            case 4: bm = 128; bn = 64; break;
-            case 5: bm = 64; bn = 64; break;
-            default: return DPD_E_UNSUPPORTED;
-        }
-        const size_t tn = (size_t)((N + bn - 1) / bn);
-        const size_t tiles = ((size_t)((M + bm - 1) / bm) + (A2 ? (M2 + bm - 1) / bm : 0) + (three ? (ex->M3 + bm - 1) / bm : 0)) * tn;
-        if (!ws || tiles * split_k * bm * bn * sizeof(float) > ws_bytes) return DPD_E_WORKSPACE;
-        if (tiles > (size_t)red_cnt_words) return DPD_E_WORKSPACE;
+    if (split_k > 1 && c.red_cnt) {
+        const X3Tile t = x3_tile(tile);
+        if (!t.ring) return DPD_E_UNSUPPORTED;
+        const size_t tiles = x3_tile_count(t, rows, nprob, N);
+        if (!c.ws || tiles * split_k * t.bm * t.bn * sizeof(float) > c.ws_bytes) return DPD_E_WORKSPACE;
+        if (tiles > (size_t)c.red_cnt_words) return DPD_E_WORKSPACE;
         static std::atomic<unsigned> generation{0x5eed0000u};
-        g.e.split_k = split_k; g.e.k_chunk = chunk;          // C / C2 / ldc stay the real output: the reducing slice stores it
-        g.red_slab = (float*)ws; g.red_cnt = (unsigned long long*)red_cnt; g.red_gen = ++generation;
+        // C / C2 / ldc stay the real output: the reducing slice stores it
+        g.red_slab = (float*)c.ws; g.red_cnt = (unsigned long long*)c.red_cnt; g.red_gen = ++generation;
         static const int sc1_mode = [] { const char* e = getenv("DPD_RED_SC1"); return e ? atoi(e) : 1; }();
         g.red_sc1 = sc1_mode;
     } else if (split_k > 1) {
-        g.e.split_k = split_k; g.e.k_chunk = chunk; g.e.slab_stride = (long)M * N; g.e.ldc = N;
-        g.e.C = (float*)ws; g.C2 = (float*)ws + (size_t)split_k * M * N;
+        g.e.slab_stride = (long)M * N; g.e.ldc = N;
+        g.e.C = (float*)c.ws; g.C2 = (float*)c.ws + (size_t)split_k * M * N;
     }
     if (planes_out) {
-        g.out_rc = out->rc; g.out_r8 = out->r8; g.rc_plane = out->rc_plane; g.r8_plane = out->r8_plane;
-        g.ld_rc = out->ld_rc; g.r8_rows = out->r8_rows; g.np_out = out->np;
+        g.out_rc = c.out.rc; g.out_r8 = c.out.r8; g.rc_plane = c.out.rc_plane; g.r8_plane = c.out.r8_plane;
+        g.ld_rc = c.out.ld_rc; g.r8_rows = c.out.r8_rows; g.np_out = c.out.np;
     }
-    struct ProfScope {
-        bool on; hipStream_t s; double fl; int form;
-        ~ProfScope() { prof_end(on, s, fl, form); }
-    } prof_scope{prof_begin(s), s, 2.0 * N * K * ((double)M + (A2 ? M2 : 0) + (three ? ex->M3 : 0)), a_fmt ? 1 : 0};
+    hipStream_t s = c.s;
+    ProfScope prof_scope{prof_begin(s), s, 2.0 * N * K * ((double)M + (ex.A2 ? M2 : 0) + (three ? ex.M3 : 0)), c.a_fmt ? 1 : 0};
     int rc;
-    if (a_fmt == 2) {
-        rc = np == 3 ? launch_x3_tile_tr<3>(tile, g, s) : launch_x3_tile_tr<1>(tile, g, s);
-    } else if (np == 3) {
-        if (!a_fmt && b_fmt) rc = launch_x3_tile<3, true, false>(tile, g, s);       // NN
-        else if (!a_fmt && !b_fmt) rc = launch_x3_tile<3, true, true>(tile, g, s);  // NT
-        else rc = launch_x3_tile<3, false, false>(tile, g, s);                      // TN
+    if (c.a_fmt == 2) {
+        rc = c.np == 3 ? launch_x3_tile_tr<3>(tile, g, s) : launch_x3_tile_tr<1>(tile, g, s);
+    } else if (c.np == 3) {
+        if (!c.a_fmt && c.b_fmt) rc = launch_x3_tile<3, true, false>(tile, g, s);       // NN
+        else if (!c.a_fmt && !c.b_fmt) rc = launch_x3_tile<3, true, true>(tile, g, s);  // NT
+        else rc = launch_x3_tile<3, false, false>(tile, g, s);                          // TN
     } else {
-        if (!a_fmt && b_fmt) rc = launch_x3_tile<1, true, false>(tile, g, s);
-        else if (!a_fmt && !b_fmt) rc = launch_x3_tile<1, true, true>(tile, g, s);
+        if (!c.a_fmt && c.b_fmt) rc = launch_x3_tile<1, true, false>(tile, g, s);
+        else if (!c.a_fmt && !c.b_fmt) rc = launch_x3_tile<1, true, true>(tile, g, s);
         else rc = launch_x3_tile<1, false, false>(tile, g, s);
     }
-    if (rc || split_k == 1 || red_cnt) return rc;
-    if ((rc = splitk_reduce(g.e.C, split_k, (long)M * N, M, N, C, ldc, nullptr, nullptr, EPI_NONE, s))) return rc;
-    if (A2) rc = splitk_reduce(g.C2, split_k, (long)M * N, M, N, C2, ldc, nullptr, nullptr, EPI_NONE, s);
+    if (rc || split_k == 1 || c.red_cnt) return rc;
+    if ((rc = splitk_reduce(g.e.C, split_k, (long)M * N, M, N, c.C, c.ldc, nullptr, nullptr, EPI_NONE, s))) return rc;
+    if (ex.A2) rc = splitk_reduce(g.C2, split_k, (long)M * N, M, N, ex.C2, c.ldc, nullptr, nullptr, EPI_NONE, s);
     return rc;
 }
 
@@ -543,9 +529,12 @@ extern "C" int dpd_split_planes(const float* src, int R, int C, int ld, int np, 
 extern "C" int dpd_gemm_planes(int np, int a_fmt, int b_fmt, int M, int N, int K, const void* A, int lda, long a_plane,
                                const void* B, int ldb, long b_plane, float* C, int ldc, const float* bias, const float* gate,
                                int epilogue, int tile, void* out_rc, void* out_r8, int r8_rows, void* stream) {
-    dpd::X3Out o;
-    o.rc = (uint16_t*)out_rc; o.r8 = (uint16_t*)out_r8; o.np = np; o.ld_rc = N; o.r8_rows = r8_rows;
-    o.rc_plane = (long)M * N; o.r8_plane = (long)r8_rows * N;
-    return dpd::gemm_x3(np, a_fmt, b_fmt, M, N, K, (const uint16_t*)A, lda, a_plane, (const uint16_t*)B, ldb, b_plane, C, ldc,
-                        bias, gate, epilogue, tile, (hipStream_t)stream, nullptr, (out_rc || out_r8) ? &o : nullptr, nullptr, 1, nullptr, 0, nullptr, 0, nullptr, 0);
+    dpd::X3Call c;
+    c.np = np; c.a_fmt = a_fmt; c.b_fmt = b_fmt; c.M = M; c.N = N; c.K = K;
+    c.A = (const uint16_t*)A; c.lda = lda; c.a_plane = a_plane;
+    c.B = (const uint16_t*)B; c.ldb = ldb; c.b_plane = b_plane;
+    c.C = C; c.ldc = ldc; c.bias = bias; c.gate = gate; c.epilogue = epilogue; c.tile = tile; c.s = (hipStream_t)stream;
+    c.out.rc = (uint16_t*)out_rc; c.out.r8 = (uint16_t*)out_r8; c.out.np = np; c.out.ld_rc = N; c.out.r8_rows = r8_rows;
+    c.out.rc_plane = (long)M * N; c.out.r8_plane = (long)r8_rows * N;
+    return dpd::gemm_x3(c);
 }
