@@ -203,6 +203,7 @@ __global__ __launch_bounds__(64) void pose_apply_bwd_kernel(const float* __restr
 
 // ---------------------------------------------------------------------------------------------------------------- pose network, forward
 constexpr int kPP = 64;                 // points per pass of the shared MLP
+constexpr int kTrainMaxN = 2048;        // training evaluation: at most 32 passes (the reference's MAX_NUM_POINT, iterative_PCRNet_ours.py:103-104)
 constexpr int kSlice = 128;             // columns of the last shared layer per workgroup
 // LDS (floats).  Weights arrive by LDS-DMA (global_load_lds_dwordx4: no registers, no wait until they are needed), unpadded, with the
 // 16-byte chunks of row r stored at position chunk ^ (r & 15) (the DMA writes 1 KiB contiguously per wave, so the swizzle is applied to
@@ -294,11 +295,16 @@ __device__ __forceinline__ void store_relu_tile(float* __restrict__ hout, int pt
 // models/ipcr_model.py:198-233: cloud c (< nA: ptsA[c], else ptsB[c - nA]) -> f[(row0 + c), slice*128 .. +128) = max over the points of
 // relu(W5 relu(W4 relu(W3 relu(W2 relu(W1 p + b1) + b2) + b3) + b4) + b5)
 // TRAIN (the training evaluation, dpd_pose_point_fwd_train): the slice-0 workgroup of a cloud also stores the four hidden activations, and every
-// workgroup the TIE MASK of its 128 columns -- bit p of ties[cloud][column] is set iff point p attains the column's maximum and that maximum
-// is positive (relu' = 0 at 0): what the gradient of reduce_max needs (tf.reduce_max / torch.amax share it evenly among ties).  N <= 64.
+// workgroup the TIE MASK of its 128 columns -- W = ceil(N / 64) words per (cloud, column), ties[cloud][w][column]; bit b of word w is set iff
+// point 64 w + b attains the column's maximum and that maximum is positive (relu' = 0 at 0): what the gradient of reduce_max needs
+// (tf.reduce_max / torch.amax share it evenly among ties).  N <= kTrainMaxN.
+// Every 64-point pass stores its word against the PASS maximum (the accumulators of its points are in registers only then); the thread
+// that stores a column's words keeps the column's running maximum and two pass sets: the passes that attain it (`alive`) and the passes
+// whose stored word a later, larger maximum made stale -- it stores zero over those after the last pass (same thread, same address:
+// program order).  The comparisons are on the fp32 values the MFMAs produced, so equality is exact.
 struct PointSave {
     float* h[4];                    // [clouds * N, 64] x 3, [clouds * N, 128]
-    unsigned long long* ties;       // [clouds, OUT]
+    unsigned long long* ties;       // [clouds, ceil(N / 64), OUT]
 };
 // Refinement loops 2..n (dpd_pose_refine): the cloud a workgroup reads is the PREVIOUS loop's source moved by the pose the head made of it --
 // fc4 (pred = W4 h3 + b4), quat_normalize, R, the move and the T composition are a prologue of the next loop's shared MLP instead of a launch
@@ -333,6 +339,9 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
     const float* pts = c < nA ? ptsA + (size_t)c * N * 3 : ptsB + (size_t)(c - nA) * N * 3;
     const float* W5s = net.W[4] + (size_t)slice * kSlice * 128;
     float vmax = 0.f;                                          // column wv * 32 + (l & 31) of the slice, over this lane's rows; relu outputs are >= 0
+    float runmax = 0.f;                                        // TRAIN: the column's maximum over the passes so far (all of its points)
+    unsigned alive = 0, stale = 0;                             // TRAIN: passes whose word stands / has to be zeroed (see PointSave)
+    const int NW = (N + kPP - 1) / kPP;
     dma_weights<64, 64>(net.W[1], lds_base, kW2, wv, l);
     dma_weights<64, 64>(net.W[2], lds_base, kW3, wv, l);
     dma_weights<64, 128>(net.W[3], lds_base, kW4, wv, l);
@@ -449,18 +458,24 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
         if (TRAIN && slice == 0) save_rows<TRAIN>(sv.h[3] + ((size_t)(row0 + c) * N + p0) * 128, lds + kHB, np, 128, kS128, t);
         // layer 5 (slice): waves 0, 1 on the first half of the slice, 2, 3 on the second; max over this lane's valid points
         mfma_layer<128, 2>(lds + kHB, lds + (wv < 2 ? kW5a : kW5b), lds[kBias + 320 + wv * 32 + (l & 31)], 0, (wv & 1) * 32, c0, c1);
+        float pmax = 0.f;                                      // this pass alone
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            if (mfma_row(r, l) < np) vmax = fmaxf(vmax, c0[r]);          // = max(relu(.)): vmax starts at 0
-            if (32 + mfma_row(r, l) < np) vmax = fmaxf(vmax, c1[r]);
+            if (mfma_row(r, l) < np) pmax = fmaxf(pmax, c0[r]);          // = max(relu(.)): starts at 0
+            if (32 + mfma_row(r, l) < np) pmax = fmaxf(pmax, c1[r]);
         }
-        if (TRAIN) {        // (N <= kPP: one pass, the accumulators of every point are still in registers)
+        vmax = fmaxf(vmax, pmax);
+        if (TRAIN) {        // (the accumulators of this pass's points are still in registers)
             __syncthreads();
-            float* red = lds + kHA;
-            red[(l >> 5) * kSlice + wv * 32 + (l & 31)] = vmax;
+            float* red = lds + kHA;                            // (layer 1 of the next pass writes hA after that pass's first two barriers)
+            red[(l >> 5) * kSlice + wv * 32 + (l & 31)] = pmax;
             __syncthreads();
             const int col = wv * 32 + (l & 31);
-            const float m = fmaxf(red[col], red[kSlice + col]);
+            float m = fmaxf(red[col], red[kSlice + col]);      // the pass maximum of the column
+            const int w = p0 / kPP;
+            if (m > runmax) { stale |= alive; alive = 1u << w; runmax = m; }
+            else if (m == runmax && m > 0.f) alive |= 1u << w;
+            else m = 0.f;                                      // a smaller pass maximum (or none positive): an empty word
             unsigned lo = 0, hi = 0;                           // rows 0..31 come from c0, rows 32..63 from c1
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -470,7 +485,14 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
             }
             lo |= (unsigned)__shfl_xor((int)lo, 32, 64);       // the two lane halves hold the other rows of the same column
             hi |= (unsigned)__shfl_xor((int)hi, 32, 64);
-            if ((l >> 5) == 0) sv.ties[(size_t)(row0 + c) * OUT + slice * kSlice + col] = ((unsigned long long)hi << 32) | lo;
+            if ((l >> 5) == 0) sv.ties[((size_t)(row0 + c) * NW + w) * OUT + slice * kSlice + col] = ((unsigned long long)hi << 32) | lo;
+        }
+    }
+    if (TRAIN && (l >> 5) == 0) {
+        while (stale) {
+            const int w = __ffs((int)stale) - 1;
+            stale &= stale - 1;
+            sv.ties[((size_t)(row0 + c) * NW + w) * OUT + slice * kSlice + wv * 32 + (l & 31)] = 0ull;
         }
     }
     __syncthreads();
@@ -661,12 +683,13 @@ extern "C" int dpd_pose_refine(const dpd_pose_net* net, const float* src, const 
 //     (w5)  wave = output column c: dW5[c, :] = sum over clouds of coef * h4[tied point, :], db5[c] = sum of the column's gradient
 //     (dh4) the gradient of layer 4's output, g4 = S W5 with the selection matrix S built from the tie masks, on the fp32
 //                           matrix cores (workgroup = cloud x 32x32 tile, wave = 128 columns): independent of how the maxima spread over points
-//   pose_bwd_cloud_kernel   workgroup = cloud: layers 4..1 on v_mfma_f32_32x32x2_f32 out of LDS; per-cloud partial weight gradients
-//   pose_bwd_reduce_kernel  sums the partials over the clouds in cloud order
+//   pose_bwd_cloud_kernel   workgroup = (cloud, 64-point chunk): layers 4..1 on v_mfma_f32_32x32x2_f32 out of LDS; one partial record of weight
+//                           gradients per chunk
+//   pose_bwd_reduce_kernel  sums the clouds x chunks partials in (cloud, chunk) order
 // fp32 throughout (MFMA fp32 = an fmaf chain per element); every sum has a fixed order (bitwise reproducible).
 namespace dpd {
 
-constexpr int kPart = 128 * 64 + 128 + 64 * 64 + 64 + 64 * 64 + 64 + 64 * 3 + 64;      // dW4 | db4 | dW3 | db3 | dW2 | db2 | dW1 | db1 per cloud
+constexpr int kPart = 128 * 64 + 128 + 64 * 64 + 64 + 64 * 64 + 64 + 64 * 3 + 64;      // dW4 | db4 | dW3 | db3 | dW2 | db2 | dW1 | db1 per (cloud, chunk)
 
 // (wave = output column c; the blocks after the g4 tiles of pose_bwd_w5_dh4_kernel, eight columns each)
 __device__ __forceinline__ void bwd_w5_wave(const float* __restrict__ df, const unsigned long long* __restrict__ ties, const float* __restrict__ h4,
@@ -674,14 +697,21 @@ __device__ __forceinline__ void bwd_w5_wave(const float* __restrict__ df, const 
     const int l = threadIdx.x & 63;
     if (c >= OUT) return;
     float a0 = 0.f, a1 = 0.f, bsum = 0.f;
+    const int NW = (N + 63) / 64;
     for (int cl0 = 0; cl0 < C; cl0 += 64) {
-        // lane = cloud: the column's tie mask and gradient of 64 clouds in ONE load each, so that the row loads below do not wait on them
+        // lane = cloud: the column's tie words and gradient of 64 clouds requested together, so that the row loads below do not wait on them
         const int mine = cl0 + l;
-        const unsigned long long mybits = mine < C ? ties[(size_t)mine * OUT + c] : 0ull;
-        const float myg = (mine < C && mybits) ? df[(size_t)mine * OUT + c] : 0.f;
-        const float mycoef = mybits ? myg / (float)__popcll(mybits) : 0.f;
-        const int myfirst = mybits ? __ffsll((long long)mybits) - 1 : 0;
-        const bool multi = mybits & (mybits - 1);
+        int mycnt = 0, myfirst = 0;                          // tied points over the NW words; the lowest of them
+        if (mine < C) {
+            for (int w = 0; w < NW; ++w) {
+                const unsigned long long b = ties[((size_t)mine * NW + w) * OUT + c];
+                if (b && !mycnt) myfirst = 64 * w + __ffsll((long long)b) - 1;
+                mycnt += __popcll(b);
+            }
+        }
+        const float myg = mycnt ? df[(size_t)mine * OUT + c] : 0.f;
+        const float mycoef = mycnt ? myg / (float)mycnt : 0.f;
+        const bool multi = mycnt > 1;
         const int n = min(64, C - cl0);
         for (int k0 = 0; k0 < n; k0 += 8) {          // eight clouds at a time: their (single) tied rows are requested together
             float2 h[8];
@@ -701,16 +731,18 @@ __device__ __forceinline__ void bwd_w5_wave(const float* __restrict__ df, const 
         while (any) {
             const int k = __ffsll((long long)any) - 1;
             any &= any - 1;
-            unsigned lo = (unsigned)__shfl((int)(unsigned)(mybits & 0xffffffffull), k, 64), hi = (unsigned)__shfl((int)(unsigned)(mybits >> 32), k, 64);
-            unsigned long long bits = ((unsigned long long)hi << 32) | lo;
             const float coef = __shfl(mycoef, k, 64);
-            bits &= bits - 1;                        // the first point was taken above
-            while (bits) {
-                const int p = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                const float2 hh = *reinterpret_cast<const float2*>(h4 + ((size_t)(cl0 + k) * N + p) * 128 + 2 * l);
-                a0 += coef * hh.x;
-                a1 += coef * hh.y;
+            const int first = __shfl(myfirst, k, 64);
+            for (int w = first >> 6; w < NW; ++w) {  // word by word, points ascending (wave-uniform loads)
+                unsigned long long bits = ties[((size_t)(cl0 + k) * NW + w) * OUT + c];
+                if (w == (first >> 6)) bits &= bits - 1;      // the first point was taken above
+                while (bits) {
+                    const int p = 64 * w + __ffsll((long long)bits) - 1;
+                    bits &= bits - 1;
+                    const float2 hh = *reinterpret_cast<const float2*>(h4 + ((size_t)(cl0 + k) * N + p) * 128 + 2 * l);
+                    a0 += coef * hh.x;
+                    a1 += coef * hh.y;
+                }
             }
         }
         // db5[c] = sum of the column's gradient over the clouds in which the maximum is positive: lane sums in a fixed tree
@@ -732,19 +764,33 @@ __device__ __forceinline__ void bwd_w5_wave(const float* __restrict__ df, const 
 // word and the coefficient of its column (LDS broadcasts), the B operand W5[col][n0 + lane % 32] is read straight from global memory (coalesced:
 // v_mfma_f32_32x32x2_f32 wants one k per lane half), all 64 of them requested before the first product.  The eight partial tiles are added in
 // wave order: columns ascending, deterministic; adding an exact zero changes nothing, so this IS the ascending-column sum of the sparse forms.
-// ONE launch for both consumers of d features: blocks [0, 8 clouds) the g4 tiles, the rest dW5 / db5 (eight columns per block) -- two launches of
-// 10.6 + 5.6 us that read the same df / ties and write disjoint outputs.
+// ONE launch for both consumers of d features: blocks [0, clouds x tiles) the g4 tiles, the rest dW5 / db5 (eight columns per block) -- two
+// launches of 10.6 + 5.6 us that read the same df / ties and write disjoint outputs.
+// N > 64: a cloud has 4 ceil(N / 32) tiles; a 32-point tile lies inside ONE tie word (m0 >> 6), but the coefficient divides by the tied points of
+// ALL words -- pose_tie_coef_kernel makes coef [clouds, OUT] once (`coefg`) instead of every tile counting NW words per column.
+__global__ __launch_bounds__(256) void pose_tie_coef_kernel(const float* __restrict__ df, const unsigned long long* __restrict__ ties, int C, int NW,
+                                                             int OUT, float* __restrict__ coef) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= C * OUT) return;
+    const int c = i / OUT, col = i % OUT;
+    int cnt = 0;
+    for (int w = 0; w < NW; ++w) cnt += __popcll(ties[((size_t)c * NW + w) * OUT + col]);
+    coef[i] = cnt ? df[i] / (float)cnt : 0.f;
+}
+
 __global__ __launch_bounds__(512) void pose_bwd_w5_dh4_kernel(const float* __restrict__ df, const unsigned long long* __restrict__ ties,
                                                                const float* __restrict__ W5, const float* __restrict__ h4, int C, int N, int OUT,
-                                                               float* __restrict__ g4g, float* __restrict__ dW5, float* __restrict__ db5) {
+                                                               float* __restrict__ g4g, float* __restrict__ dW5, float* __restrict__ db5,
+                                                               int tiles, const float* __restrict__ coefg) {
     __shared__ unsigned long long sT[1024];
     __shared__ float sC[1024];
     __shared__ float part[8][1024];
-    if ((int)blockIdx.x >= C * 8) {
-        bwd_w5_wave(df, ties, h4, C, N, OUT, dW5, db5, ((int)blockIdx.x - C * 8) * 8 + (int)(threadIdx.x >> 6));
+    if ((int)blockIdx.x >= C * tiles) {
+        bwd_w5_wave(df, ties, h4, C, N, OUT, dW5, db5, ((int)blockIdx.x - C * tiles) * 8 + (int)(threadIdx.x >> 6));
         return;
     }
-    const int c = blockIdx.x >> 3, tile = blockIdx.x & 7, m0 = (tile >> 2) * 32, n0 = (tile & 3) * 32;
+    const int c = (int)blockIdx.x / tiles, tile = (int)blockIdx.x % tiles, m0 = (tile >> 2) * 32, n0 = (tile & 3) * 32;
+    const int NW = (N + 63) / 64;
     const int t = threadIdx.x, wv = t >> 6, l = t & 63, i = l & 31, h = l >> 5;
     const int kb = wv * 128;
     // every global load of the kernel is requested here, together
@@ -757,21 +803,21 @@ __global__ __launch_bounds__(512) void pose_bwd_w5_dh4_kernel(const float* __res
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int col = q * 512 + t;
-        tb[q] = ties[(size_t)c * OUT + col];
-        dv[q] = df[(size_t)c * OUT + col];
+        tb[q] = ties[((size_t)c * NW + (m0 >> 6)) * OUT + col];
+        dv[q] = coefg ? coefg[(size_t)c * OUT + col] : df[(size_t)c * OUT + col];
         const int pr = m0 + (col >> 5);                       // (the epilogue's element: row col / 32 of the tile, input n0 + col % 32)
         hv[q] = pr < N ? h4[((size_t)c * N + pr) * 128 + n0 + (col & 31)] : 0.f;
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         sT[q * 512 + t] = tb[q];
-        sC[q * 512 + t] = tb[q] ? dv[q] / (float)__popcll(tb[q]) : 0.f;
+        sC[q * 512 + t] = coefg ? dv[q] : (tb[q] ? dv[q] / (float)__popcll(tb[q]) : 0.f);      // (coefg == nullptr: one word, NW == 1)
     }
     __syncthreads();
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const int sh = m0 + i;
+    const int sh = (m0 + i) & 63;
 #pragma unroll
     for (int j = 0; j < 64; ++j) {
         const int col = kb + 2 * j + h;
@@ -909,16 +955,19 @@ __global__ __launch_bounds__(kBT) void pose_bwd_cloud_kernel(const float* __rest
     float* GA = lds + kMGA;
     float* GAT = lds + kMGAT;
     float* sp = lds + kMPts;
-    const int c = blockIdx.x, t = threadIdx.x;
-    const int np = N;
-    const float* pts = c < nA ? ptsA + (size_t)c * N * 3 : ptsB + (size_t)(c - nA) * N * 3;
-    float* out = part + (size_t)c * kPart;
+    // workgroup = (cloud, 64-point chunk): chunk-major records, NW per cloud; rows at or beyond np stay zero
+    const int NW = (N + 63) / 64;
+    const int c = (int)blockIdx.x / NW, p0 = ((int)blockIdx.x % NW) * 64, t = threadIdx.x;
+    const int np = min(64, N - p0);
+    const float* pts = (c < nA ? ptsA + (size_t)c * N * 3 : ptsB + (size_t)(c - nA) * N * 3) + (size_t)p0 * 3;
+    const size_t prow = (size_t)c * N + p0;                  // first row of the chunk in g4g / h1..h3
+    float* out = part + (size_t)blockIdx.x * kPart;
     // layer 4 (W4 [128 o][64 i]): g4 -> G [p][o], GT [o][p]; h3 -> HT [i][p]; W4 -> WT [i][o]
-    lds_load_t(g4g + (size_t)c * N * 128, np, 64, 128, GT, kP64, G, kP128, t);
-    lds_load_t(sv.h[2] + (size_t)c * N * 64, np, 64, 64, HT, kP64, nullptr, 0, t);
+    lds_load_t(g4g + prow * 128, np, 64, 128, GT, kP64, G, kP128, t);
+    lds_load_t(sv.h[2] + prow * 64, np, 64, 64, HT, kP64, nullptr, 0, t);
     lds_load_t(net.W[3], 128, 128, 64, WT, kP128, nullptr, 0, t);
     if (t < 192) sp[(t / 3) * 4 + t % 3] = (t / 3) < np ? pts[t] : 0.f;
-    Pre64 ph = pre64_load(sv.h[1] + (size_t)c * N * 64, np, t), pw = pre64_load(net.W[2], 64, t);      // layer 3's operands, in flight
+    Pre64 ph = pre64_load(sv.h[1] + prow * 64, np, t), pw = pre64_load(net.W[2], 64, t);      // layer 3's operands, in flight
     __syncthreads();
     bwd_layer_dw<128>(GT, HT, out, out + 128 * 64, np, t);
     bwd_layer_dx<128>(G, kP128, WT, kP128, HT, GA, kP64, GAT, t);                      // g3 -> GA [p][o3], GAT [o3][p]
@@ -926,7 +975,7 @@ __global__ __launch_bounds__(kBT) void pose_bwd_cloud_kernel(const float* __rest
     // layer 3 (W3 [64][64]): h2 -> HT, W3 -> WT (stride 68)
     pre64_store_t(ph, HT, t);
     pre64_store_t(pw, WT, t);
-    ph = pre64_load(sv.h[0] + (size_t)c * N * 64, np, t);                                              // layer 2's
+    ph = pre64_load(sv.h[0] + prow * 64, np, t);                                              // layer 2's
     pw = pre64_load(net.W[1], 64, t);
     __syncthreads();
     float* o3 = out + 128 * 64 + 128;
@@ -1000,9 +1049,16 @@ int check_point_net(const dpd_pose_net* net) {
 }
 }  // namespace
 
-extern "C" size_t dpd_pose_point_bwd_workspace_bytes(int clouds) {      // per-cloud partial weight gradients + g4 [clouds * 64, 128]
-    return clouds > 0 ? (size_t)clouds * (dpd::kPart + 64 * 128) * sizeof(float) : 0;
+extern "C" int dpd_pose_point_tie_words(int N) { return N > 0 ? (N + dpd::kPP - 1) / dpd::kPP : 0; }
+
+// partial weight gradients per (cloud, 64-point chunk) + g4 [clouds * chunks * 64, 128] (+ coef [clouds, OUT] when a cloud has several chunks)
+extern "C" size_t dpd_pose_point_bwd_workspace_bytes_n(int clouds, int N) {
+    if (clouds <= 0 || N <= 0 || N > dpd::kTrainMaxN) return 0;
+    const size_t W = (size_t)dpd_pose_point_tie_words(N);
+    return ((size_t)clouds * W * (dpd::kPart + 64 * 128) + (W > 1 ? (size_t)clouds * 1024 : 0)) * sizeof(float);
 }
+
+extern "C" size_t dpd_pose_point_bwd_workspace_bytes(int clouds) { return dpd_pose_point_bwd_workspace_bytes_n(clouds, dpd::kPP); }      // N <= 64
 
 extern "C" int dpd_pose_point_fwd_train(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, float* f,
                                         float* h1, float* h2, float* h3, float* h4, unsigned long long* ties, void* stream) {
@@ -1010,7 +1066,7 @@ extern "C" int dpd_pose_point_fwd_train(const dpd_pose_net* net, const float* pt
     if (int rc = check_point_net(net)) return rc;
     if (!ptsA || (nB > 0 && !ptsB) || !f || !h1 || !h2 || !h3 || !h4 || !ties) return DPD_E_NULL;
     if (nA <= 0 || nB < 0 || N <= 0) return DPD_E_DIM;
-    if (N > kPP) return DPD_E_UNSUPPORTED;                 // the tie mask is one 64-bit word per (cloud, column)
+    if (N > kTrainMaxN) return DPD_E_UNSUPPORTED;          // the kernel keeps its pass sets in 32-bit words
     if ((((uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)h3 | (uintptr_t)h4) & 15) != 0) return DPD_E_UNSUPPORTED;
     const int OUT = net->out_features;
     const size_t lds = (size_t)kPointLds * sizeof(float);
@@ -1033,9 +1089,9 @@ extern "C" int dpd_pose_point_bwd(const dpd_pose_net* net, const float* ptsA, co
     for (int i = 0; i < 5; ++i)
         if (!dW[i] || !db[i]) return DPD_E_NULL;
     if (nA <= 0 || nB < 0 || N <= 0) return DPD_E_DIM;
-    if (N > kPP) return DPD_E_UNSUPPORTED;
-    const int C = nA + nB, OUT = net->out_features;
-    if (ws_bytes < dpd_pose_point_bwd_workspace_bytes(C)) return DPD_E_WORKSPACE;
+    if (N > kTrainMaxN) return DPD_E_UNSUPPORTED;
+    const int C = nA + nB, OUT = net->out_features, NW = dpd_pose_point_tie_words(N);
+    if (ws_bytes < dpd_pose_point_bwd_workspace_bytes_n(C, N)) return DPD_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     PointNetW pw{};
     for (int i = 0; i < 5; ++i) { pw.W[i] = net->Wp[i]; pw.b[i] = net->bp[i]; }
@@ -1043,13 +1099,20 @@ extern "C" int dpd_pose_point_bwd(const dpd_pose_net* net, const float* ptsA, co
                  const_cast<unsigned long long*>(ties)};
     const size_t lds = (size_t)kBwdLds * sizeof(float);
     if (int rc = ensure_dyn_lds(g_point_bwd_lds, (const void*)pose_bwd_cloud_kernel, lds)) return rc;
-    float* g4g = (float*)ws + (size_t)C * kPart;                   // [C * N, 128]
-    DPD_LAUNCH(pose_bwd_w5_dh4_kernel, dim3((unsigned)(C * 8 + (OUT + 7) / 8)), dim3(512), 0, s, df, ties, net->Wp[4], h4, C, N, OUT, g4g, dW[4], db[4]);
+    float* g4g = (float*)ws + (size_t)C * NW * kPart;              // [C * N, 128]
+    float* coef = NW > 1 ? g4g + (size_t)C * NW * 64 * 128 : nullptr;      // [C, OUT]
+    const int tiles = NW > 1 ? 4 * ((N + 31) / 32) : 8;            // 32 points x 32 inputs each
+    if (coef) {
+        DPD_LAUNCH(pose_tie_coef_kernel, dim3((unsigned)((C * OUT + 255) / 256)), dim3(256), 0, s, df, ties, C, NW, OUT, coef);
+        DPD_CHECK_LAUNCH();
+    }
+    DPD_LAUNCH(pose_bwd_w5_dh4_kernel, dim3((unsigned)(C * tiles + (OUT + 7) / 8)), dim3(512), 0, s, df, ties, net->Wp[4], h4, C, N, OUT, g4g, dW[4], db[4],
+               tiles, (const float*)coef);
     DPD_CHECK_LAUNCH();
-    DPD_LAUNCH(pose_bwd_cloud_kernel, dim3((unsigned)C), dim3(kBT), lds, s, ptsA, ptsB, nA, N, pw, (const float*)g4g, sv, (float*)ws);
+    DPD_LAUNCH(pose_bwd_cloud_kernel, dim3((unsigned)(C * NW)), dim3(kBT), lds, s, ptsA, ptsB, nA, N, pw, (const float*)g4g, sv, (float*)ws);
     DPD_CHECK_LAUNCH();
-    DPD_LAUNCH(pose_bwd_reduce_kernel, dim3((unsigned)((kPart + 255) / 256)), dim3(256), 0, s, (const float*)ws, C, dW[3], db[3], dW[2], db[2], dW[1], db[1],
-               dW[0], db[0]);
+    DPD_LAUNCH(pose_bwd_reduce_kernel, dim3((unsigned)((kPart + 255) / 256)), dim3(256), 0, s, (const float*)ws, C * NW, dW[3], db[3], dW[2], db[2], dW[1],
+               db[1], dW[0], db[0]);
     DPD_CHECK_LAUNCH();
     return 0;
 }

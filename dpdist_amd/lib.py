@@ -89,6 +89,8 @@ SIGNATURES = {
     "dpd_pose_refine": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     "dpd_pose_point_bwd_workspace_bytes": (c_size_t, [c_int]),
+    "dpd_pose_point_bwd_workspace_bytes_n": (c_size_t, [c_int, c_int]),
+    "dpd_pose_point_tie_words": (c_int, [c_int]),
     "dpd_pose_point_fwd_train": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 7),
     "dpd_pose_point_bwd": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 +
                            [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),

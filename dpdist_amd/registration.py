@@ -42,11 +42,14 @@ def quat_normalize(pred, rot_lim=45.0):
     return torch.cat([torch.tanh(t) * 0.1, torch.cos(ang / 2), axis * torch.sin(ang / 2)], -1)
 
 
+NATIVE_TRAIN_MAX_POINTS = 2048      # dpd_pose_point_fwd_train / _bwd (include/dpdist_capi.h); the reference's MAX_NUM_POINT
+
+
 class _PointFeaturesFn(torch.autograd.Function):
     """Shared MLP + max pool of the pose network (models/ipcr_model.py:198-233) with its weight gradients on the library
-    (include/dpdist_capi.h: dpd_pose_point_fwd_train / dpd_pose_point_bwd; csrc/pose.hip): one launch forward, three backward, instead of
-    ~16 forward and ~45 backward launches of torch / hipBLASLt kernels at batch 16.  The clouds carry no gradient (the refined source of a
-    registration step is a constant of the step, iterative_PCRNet_ours.py:442-470).  Same mathematics as `point(...).amax(1)` -- gradient of
+    (include/dpdist_capi.h: dpd_pose_point_fwd_train / dpd_pose_point_bwd; csrc/pose.hip): one launch forward, three backward (four above
+    64 points), instead of ~16 forward and ~45 backward launches of torch / hipBLASLt kernels at batch 16.  The clouds carry no gradient (the
+    refined source of a registration step is a constant of the step, iterative_PCRNet_ours.py:442-470).  Same mathematics as `point(...).amax(1)` -- gradient of
     the max pool shared evenly among ties like tf.reduce_max -- in another fp32 summation order."""
 
     @staticmethod
@@ -62,9 +65,10 @@ class _PointFeaturesFn(torch.autograd.Function):
         dev = clouds.device
         f = torch.empty(C, w.out_features, device=dev, dtype=torch.float32)
         h = [torch.empty(C * N, k, device=dev, dtype=torch.float32) for k in (64, 64, 64, 128)]
-        ties = torch.empty(C, w.out_features, device=dev, dtype=torch.int64)
-        L.check(L.load().dpd_pose_point_fwd_train(byref(w), L.ptr(clouds), None, C, 0, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
-                                                  ties.data_ptr(), L.cur_stream()), "dpd_pose_point_fwd_train")
+        lib = L.load()
+        ties = torch.empty(C, lib.dpd_pose_point_tie_words(N), w.out_features, device=dev, dtype=torch.int64)
+        L.check(lib.dpd_pose_point_fwd_train(byref(w), L.ptr(clouds), None, C, 0, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
+                                             ties.data_ptr(), L.cur_stream()), "dpd_pose_point_fwd_train")
         ctx.save_for_backward(clouds, ties, *h, *wb)
         return f
 
@@ -85,7 +89,7 @@ class _PointFeaturesFn(torch.autograd.Function):
         dW = (ctypes.c_void_p * 5)(*[grads[2 * i].data_ptr() for i in range(5)])
         db = (ctypes.c_void_p * 5)(*[grads[2 * i + 1].data_ptr() for i in range(5)])
         lib = L.load()
-        nbytes = lib.dpd_pose_point_bwd_workspace_bytes(C)
+        nbytes = lib.dpd_pose_point_bwd_workspace_bytes_n(C, N)
         ws = torch.empty(nbytes // 4, device=clouds.device, dtype=torch.float32)
         L.check(lib.dpd_pose_point_bwd(byref(w), L.ptr(clouds), None, C, 0, N, L.ptr(df), L.ptr(h1), L.ptr(h2), L.ptr(h3), L.ptr(h4), ties.data_ptr(),
                                        dW, db, L.ptr(ws), nbytes, L.cur_stream()), "dpd_pose_point_bwd")
@@ -95,8 +99,8 @@ class _PointFeaturesFn(torch.autograd.Function):
 class _PoseNetRawFn(torch.autograd.Function):
     """The whole pose network of a training evaluation -- shared MLP + max pool (_PointFeaturesFn's kernels) and the head (models/ipcr_model.py:
     273-284) -- as ONE autograd node on the library: five launches forward (dpd_pose_point_fwd_train, dpd_pose_head_fwd_train), eight backward
-    (dpd_pose_head_bwd, dpd_pose_point_bwd), gradients w.r.t. the 18 weight tensors only.  `mask` [B,256]: the dropout mask (0 or 1 / keep)
-    drawn by the caller, or None (evaluation mode).  `sink`: None, or {id(parameter): tensor of its shape} -- the backward then WRITES the
+    (dpd_pose_head_bwd, dpd_pose_point_bwd; nine above 64 points), gradients w.r.t. the 18 weight tensors only.  `mask` [B,256]: the dropout mask
+    (0 or 1 / keep) drawn by the caller, or None (evaluation mode).  `sink`: None, or {id(parameter): tensor of its shape} -- the backward then WRITES the
     gradient of that parameter there (views of the optimizer's flat gradient buffer: no gather copy afterwards) and returns it."""
 
     @staticmethod
@@ -118,7 +122,7 @@ class _PoseNetRawFn(torch.autograd.Function):
         e = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)      # noqa: E731
         f = e(C, w.out_features)
         h = [e(C * N, k) for k in (64, 64, 64, 128)]
-        ties = torch.empty(C, w.out_features, device=dev, dtype=torch.int64)
+        ties = torch.empty(C, lib.dpd_pose_point_tie_words(N), w.out_features, device=dev, dtype=torch.int64)
         L.check(lib.dpd_pose_point_fwd_train(byref(w), L.ptr(source), L.ptr(template), B, B, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]),
                                              L.ptr(h[3]), ties.data_ptr(), st), "dpd_pose_point_fwd_train")
         a1, a2, a3, pred = e(B, 1024), e(B, 512), e(B, 256), e(B, 7)
@@ -158,7 +162,7 @@ class _PoseNetRawFn(torch.autograd.Function):
         ws = torch.empty(nb // 4, device=dev, dtype=torch.float32)
         L.check(lib.dpd_pose_head_bwd(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(dpred), vp(grads[10::2]), vp(grads[11::2]),
                                       L.ptr(df), L.ptr(ws), nb, st), "dpd_pose_head_bwd")
-        nb2 = lib.dpd_pose_point_bwd_workspace_bytes(C)
+        nb2 = lib.dpd_pose_point_bwd_workspace_bytes_n(C, N)
         ws2 = torch.empty(nb2 // 4, device=dev, dtype=torch.float32)
         L.check(lib.dpd_pose_point_bwd(byref(w), L.ptr(source), L.ptr(template), B, B, N, L.ptr(df), L.ptr(h1), L.ptr(h2), L.ptr(h3), L.ptr(h4),
                                        ties.data_ptr(), vp(grads[0:10:2]), vp(grads[1:10:2]), L.ptr(ws2), nb2, st), "dpd_pose_point_bwd")
@@ -207,7 +211,7 @@ class PoseNet(nn.Module):
         """shared MLP + max pool over the points of every cloud: [C, N, 3] -> [C, out_features]"""
         lin = [m for m in self.point if isinstance(m, nn.Linear)]
         if (self.native_train and torch.is_grad_enabled() and clouds.is_cuda and clouds.dtype == torch.float32 and not clouds.requires_grad
-                and clouds.shape[1] <= 64 and [(m.in_features, m.out_features) for m in lin] == [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
+                and clouds.shape[1] <= NATIVE_TRAIN_MAX_POINTS and [(m.in_features, m.out_features) for m in lin] == [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
                 and any(p.requires_grad for m in lin for p in (m.weight, m.bias))):
             return _PointFeaturesFn.apply(clouds.contiguous(), *[t for m in lin for t in (m.weight, m.bias)])
         return self.point(clouds).amax(1)
@@ -222,7 +226,7 @@ class PoseNet(nn.Module):
         lin_p = [m for m in self.point if isinstance(m, nn.Linear)]
         lin_h = [m for m in self.head if isinstance(m, nn.Linear)]
         return (self.native_train and torch.is_grad_enabled() and clouds.is_cuda and clouds.dtype == torch.float32 and not clouds.requires_grad
-                and clouds.shape[1] <= 64 and [(m.in_features, m.out_features) for m in lin_p] == [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
+                and clouds.shape[1] <= NATIVE_TRAIN_MAX_POINTS and [(m.in_features, m.out_features) for m in lin_p] == [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
                 and [(m.in_features, m.out_features) for m in lin_h] == [(2048, 1024), (1024, 512), (512, 256), (256, 7)]
                 and any(p.requires_grad for p in self.parameters()))
 

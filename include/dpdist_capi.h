@@ -367,11 +367,17 @@ int dpd_pose_refine(const dpd_pose_net* net, const float* src, const float* tmpl
  * pcrnet-registration/iterative_PCRNet_ours.py:442-470, which differentiates the network w.r.t. its weights only): forward with what the
  * backward needs, and TF / torch autodiff of the five 1x1 convolutions, their ReLUs and tf.reduce_max.
  *   dpd_pose_point_fwd_train: clouds ptsA [nA,N,3] then ptsB [nB,N,3] (nB may be 0) -> f [nA+nB, out_features]; stored for the backward:
- *     h1, h2, h3 [(nA+nB) N, 64], h4 [(nA+nB) N, 128] (16-byte aligned) and ties [nA+nB, out_features] x 8 bytes: bit p set <=> point p
- *     attains the column's maximum and that maximum is positive (the gradient of reduce_max is shared evenly among ties).  N <= 64.
+ *     h1, h2, h3 [(nA+nB) N, 64], h4 [(nA+nB) N, 128] (16-byte aligned) and the max pool's tie mask, W = dpd_pose_point_tie_words(N) =
+ *     ceil(N / 64) words of 8 bytes per (cloud, column): ties [nA+nB, W, out_features]; bit b of word w set <=> point 64 w + b attains the
+ *     column's maximum and that maximum is positive (the gradient of reduce_max is shared evenly among ties).  For N <= 64 that is one word
+ *     per (cloud, column), [nA+nB, out_features].  N <= 2048 (the reference's MAX_NUM_POINT); beyond: DPD_E_UNSUPPORTED.
  *   dpd_pose_point_bwd: df [nA+nB, out_features] -> dW[i], db[i] (i = 0..4, shapes of net->Wp / bp; overwritten).  ws:
- *     dpd_pose_point_bwd_workspace_bytes(nA + nB) bytes.  Deterministic (every sum in a fixed order).  The head's fields of `net` are not read. */
+ *     dpd_pose_point_bwd_workspace_bytes_n(nA + nB, N) bytes (one partial record per cloud and 64-point chunk; 0 for an N the entries
+ *     refuse); dpd_pose_point_bwd_workspace_bytes(clouds) is that size for N <= 64.  Same N limit.  Deterministic (every sum in a fixed
+ *     order, no atomics).  The head's fields of `net` are not read. */
+int dpd_pose_point_tie_words(int N);
 size_t dpd_pose_point_bwd_workspace_bytes(int clouds);
+size_t dpd_pose_point_bwd_workspace_bytes_n(int clouds, int N);
 int dpd_pose_point_fwd_train(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, float* f, float* h1, float* h2,
                              float* h3, float* h4, unsigned long long* ties, void* stream);
 int dpd_pose_point_bwd(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, const float* df, const float* h1,

@@ -4,7 +4,10 @@ network with DPDist as the loss at the reference's workload (batch 16, 64 points
 / U(-0.01,0.01)^3: pcrnet-registration/run_train_and_eval_PCRNet.bash:16-40), and report the reference's metric
 (results_itrPCRNet_no_stop.py:112-133,465-474: find_errors(gt_pose, find_final_pose_inv(T))) on held-out pairs.
 
-    python tools/registration_demo.py [--dp_steps 6000] [--reg_steps 6000] [--batch 16] [--loss ours|chamfer|both] [--gpus N]
+    python tools/registration_demo.py [--dp_steps 6000] [--reg_steps 6000] [--batch 16] [--loss ours|chamfer|both] [--gpus N] [--num_point 64]
+
+--num_point: points per registration cloud (the reference's --num_point: 256 / 512 / 1024 / 2048, default 512, iterative_PCRNet_ours.py:40;
+this demo's default stays 64).  DPDist itself is trained on 64-point chair clouds either way.
 
 --gpus N (BASELINE config 5, "8 x MI355X DP"): one process per GPU, started like `bench.py --gpus N` starts its ranks (every rank under
 the launch watchdog of dpdist_amd/launch.py).  DPDist is trained identically on every rank (bitwise reproducible fp32 step: 3 s, no
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--loss", default="both", choices=["ours", "chamfer", "both"])
     ap.add_argument("--eval_pairs", type=int, default=128)
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--num_point", type=int, default=64, help="points per registration cloud")
     a = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if a.gpus != world:
@@ -78,7 +82,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     say = print if rank == 0 else (lambda *x, **k: None)
     cu = lambda x: torch.tensor(x, device=dev)   # noqa: E731
-    out = {"n_gpus": world, "workload": {"batch_per_gpu": a.batch, "global_batch": a.batch * world, "num_point": 64, "loops": a.loops, "lim_rot": 45.0, "poses": "U(-45,45)^3 deg, U(-.01,.01)^3",
+    out = {"n_gpus": world, "workload": {"batch_per_gpu": a.batch, "global_batch": a.batch * world, "num_point": a.num_point, "loops": a.loops, "lim_rot": 45.0, "poses": "U(-45,45)^3 deg, U(-.01,.01)^3",
                         "shapes": "synthetic box-union chairs"}}
 
     # 1. DPDist's own trainer (the hot path) on chair distance data: reference recipe = y-rotation + shift augmentation
@@ -111,7 +115,7 @@ def main():
     out["dpdist"] = {"steps": a.dp_steps, "train_l1": run, "heldout_l1": float(ev), "tilt_deg": a.tilt}
 
     # 2. iterative PCRNet, DPDist frozen, as the loss ('ours') and the reference's Chamfer baseline (iterative_PCRNet.py)
-    es_all, et_all, eg_all = synth.registration_pairs(a.eval_pairs, 64, seed=99)
+    es_all, et_all, eg_all = synth.registration_pairs(a.eval_pairs, a.num_point, seed=99)
     per = (a.eval_pairs + world - 1) // world                # held-out pairs are split over the ranks
     sl = slice(rank * per, min(a.eval_pairs, (rank + 1) * per))
     es_np, eg = es_all[sl], eg_all[sl]
@@ -160,7 +164,7 @@ def main():
         gen = 0.0
         for s in range(a.reg_steps):
             tg = time.time()
-            src, tmpl, _ = synth.registration_pairs(a.batch, 64, rng=rng)
+            src, tmpl, _ = synth.registration_pairs(a.batch, a.num_point, rng=rng)
             gen += time.time() - tg
             l, _ = reg.train_step(cu(src), cu(tmpl))
             if (s + 1) % 100 == 0:

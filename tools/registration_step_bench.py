@@ -11,7 +11,11 @@ forward/backward + TF-form Adam, pcrnet-registration/iterative_PCRNet_ours.py:41
 Inputs are resident on the GPU before the clock starts (pair generation is the data loader's business, not this path's).  Also prints
 what one DPDist forward+backward costs on its own (the as-loss engine, same shape), i.e. the share of the step that IS the hot path.
 
-    python tools/registration_step_bench.py [--batch 16] [--steps 300] [--dtype f32|f32x3|bf16] [--loops 8]
+    python tools/registration_step_bench.py [--batch 16] [--steps 300] [--dtype f32|f32x3|bf16] [--loops 8] [--num_point 64]
+
+--num_point other than 64 (the reference registers at 256 .. 2048 points, default 512) adds, per form, what the pose network's training
+evaluation costs on its own (`train_eval_ms`: PoseNet.raw forward + backward, GPU time), whether it ran as the library's node, and the
+kernel launches of one eager training step (`launches_per_step`, counted by torch's profiler).
 """
 import argparse
 import json
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--loops", type=int, default=8)
     ap.add_argument("--dtype", default="f32")
+    ap.add_argument("--num_point", type=int, default=64)
     ap.add_argument("--forms", default="eager_torch,eager_fused,eager_native,graph_fused,graph")
     ap.add_argument("--train-only", action="store_true", help="profiler runs: exactly 8 + 3 * steps training steps per form, nothing else")
     a = ap.parse_args()
@@ -38,8 +43,8 @@ def main():
     from dpdist_amd.registration import IterativeRegistration, PoseNet
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
-    pool = [tuple(torch.tensor(x, device=dev) for x in synth.registration_pairs(a.batch, 64, rng=rng)[:2]) for _ in range(32)]
-    out = {"workload": {"batch": a.batch, "num_point": 64, "loops": a.loops, "dpdist_dtype": a.dtype}}
+    pool = [tuple(torch.tensor(x, device=dev) for x in synth.registration_pairs(a.batch, a.num_point, rng=rng)[:2]) for _ in range(32)]
+    out = {"workload": {"batch": a.batch, "num_point": a.num_point, "loops": a.loops, "dpdist_dtype": a.dtype}}
 
     def harness(graph, fused, native=True):
         torch.manual_seed(0)
@@ -59,6 +64,34 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / n * 1e3
 
+    def train_eval_cost(reg):
+        """The pose network's training evaluation alone (forward + backward of PoseNet.raw on one batch), and the launches of one eager step."""
+        from torch.profiler import ProfilerActivity, profile
+        net, (src, tmpl) = reg.net, pool[0]
+        net.train()
+        params = [p for p in net.parameters()]
+        up = torch.ones(a.batch, 7, device=dev)
+
+        def one():
+            pred = net.raw(src, tmpl)
+            torch.autograd.grad(pred, params, grad_outputs=up)
+            return pred
+        for _ in range(5):
+            pred = one()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(50):
+            one()
+        e1.record()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            reg._train_step_eager(src, tmpl)
+            torch.cuda.synchronize()
+        launches = sum(1 for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA)
+        return {"train_eval_ms": round(e0.elapsed_time(e1) / 50, 4), "train_eval_on_library": type(pred.grad_fn).__name__ == "_PoseNetRawFnBackward",
+                "launches_per_step": launches}
+
     for form in a.forms.split(","):
         graph, fused, native = form.startswith("graph"), form != "eager_torch", form in ("eager_native", "graph")
         model, reg = harness(graph, fused, native)
@@ -77,7 +110,7 @@ def main():
                      "graph_replays": reg.graph_replays, "last_loss": loss.item()}
         if graph:
             # GPU time of one replay alone (events around back-to-back replays of the captured step, no input copies)
-            rec = reg._graphs[("train", (a.batch, 64, 3), 0)]
+            rec = reg._graphs[("train", (a.batch, a.num_point, 3), 0)]
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             e0.record()
@@ -87,6 +120,8 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             out[form]["replay_gpu_ms"] = round(e0.elapsed_time(e1) / 100, 4)
+        if a.num_point != 64:
+            out[form].update(train_eval_cost(reg))
         reg.close()
         print(form, json.dumps(out[form]), flush=True)
 
