@@ -7,7 +7,8 @@ Mirrors `train_multi_gpu_pc_compare_dist.py` for `--train_comp dpdist` (relative
     train_one_epoch_3d / eval_one_epoch_3d     :732-807, :809-873
     epoch loop, eval + checkpoint every 10     :347-357
     learning-rate schedule, Adam               :216,976-990                                 -> DPDistTrainer
-The ModelNet `*_dist_c_scaled.txt` / `*_neg_{l,u}.txt` files are not in the reference tree, so the dataset is a
+With `--data_dir DIR` the datasets are the reference's ModelNet `*_dist_c_scaled.txt` / `*_neg_{l,u}.txt` files, written and
+read by dpdist_amd/dataset.py.  Those files are not in the reference tree, so without `--data_dir` the dataset is a
 synthetic stand-in with the SAME item format as `modelnet_dataset.ModelNetDataset` (`:98-187`): per shape
 3*2N points (surface | near-surface | far) and 2*2N ground-truth distances, on analytic surfaces (spheres / boxes
 of extent <= 0.8 like `dataset_sample_with_gt.py:82`), with the reference's augmentation (random y-rotation +
@@ -46,6 +47,9 @@ def build_parser():
     p.add_argument("--add_noise", type=float, default=0.0)
     p.add_argument("--train_shapes", type=int, default=889, help="synthetic stand-in for the 889 train chairs")
     p.add_argument("--test_shapes", type=int, default=100, help="synthetic stand-in for the 100 test chairs")
+    p.add_argument("--data_dir", default="", help="ModelNet-style tree with distance-label files (python -m dpdist_amd.dataset --root DIR); "
+                                                  "when set, --category picks the shapes and --train_shapes / --test_shapes are ignored")
+    p.add_argument("--num_neg_points", type=int, default=10 ** 4, help="rows per negative set in the label files' names (--data_dir only)")
     p.add_argument("--eval_every", type=int, default=10)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--restore", default="", help="TF V2 checkpoint prefix (model.ckpt) or .npz to start from")
@@ -177,6 +181,9 @@ def train(argv=None):
     from .trainer import DPDistTrainer
 
     F = build_parser().parse_args(argv)
+    if F.data_dir:                                                  # missing label files are an error before any GPU work
+        from .dataset import ModelNetDistanceDataset, require_label_files
+        require_label_files(F.data_dir, [F.category], F.num_neg_points)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -208,8 +215,14 @@ def train(argv=None):
             print(s, flush=True)
 
     log_string(str(F))
-    train_ds = SyntheticDistanceDataset(F.train_shapes, 2 * N, F.batch_size, "train", F.seed)   # npoints=NUM_POINT*2 (:181)
-    test_ds = SyntheticDistanceDataset(F.test_shapes, 2 * N, F.batch_size, "test", F.seed)
+    if F.data_dir:                                                  # :181-186
+        train_ds = ModelNetDistanceDataset(F.data_dir, F.batch_size, npoints=2 * N, split="train", class_choice=[F.category], seed=F.seed,
+                                           num_neg_points=F.num_neg_points)
+        test_ds = ModelNetDistanceDataset(F.data_dir, F.batch_size, npoints=2 * N, split="test", class_choice=[F.category], seed=F.seed,
+                                           num_neg_points=F.num_neg_points)
+    else:
+        train_ds = SyntheticDistanceDataset(F.train_shapes, 2 * N, F.batch_size, "train", F.seed)   # npoints=NUM_POINT*2 (:181)
+        test_ds = SyntheticDistanceDataset(F.test_shapes, 2 * N, F.batch_size, "test", F.seed)
     params = DPDistParams(k=K, mlp=(1024, 1024, 1024), device=dev)
     params.reset_parameters_tf(generator=torch.Generator().manual_seed(F.seed))               # replicated variables
     tr = DPDistTrainer(params, dev_bs, num_point=N, Embedding_Size=F.embedding_size, sigma3dmfv=sigma,

@@ -329,6 +329,22 @@ int dpd_chamfer_bwd(const float* a, const float* b, int B, int N, int M, const i
                     float gscale, float* da, float* db, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest-point distance labels of the training set; replaces scipy's cdist(point_set, candidates).min(0) of the reference's
+ * label generator (dataset_sample_with_gt.py:90-91,121-122).  For each of S shapes
+ *   dist[s][i] = min_j |q_si - p_sj|   (Euclidean, NOT squared),   arg[s][i] = the lowest such j (arg may be NULL).
+ * ref [S,P,3], qry [S,M,3], dist [S,M] fp32, arg [S,M] int32.  One launch covers all shapes.
+ * The squared distance of a pair is (dx*dx + dy*dy) + dz*dz in fp32 with d? = q? - p?, in that order and not fused (the form of
+ * dpd_chamfer_fwd); a minimum does not depend on the visiting order, so dist = sqrtf(min) is defined bit for bit and ties go to the
+ * lowest index.  Inputs are assumed finite (a NaN coordinate never wins the minimum; the result for such a cloud is unspecified).
+ * Any P, M >= 1 up to DPD_NN_MAX_POINTS and S up to DPD_NN_MAX_SHAPES; beyond: DPD_E_UNSUPPORTED.  The workload's shape is
+ * P = 10 000, M = 50 000, S = 1 ... 16.  DPD_NN_CHUNK reference points pass through LDS at a time, DPD_NN_TILE queries per workgroup.  */
+#define DPD_NN_CHUNK 2048
+#define DPD_NN_TILE 256
+#define DPD_NN_MAX_POINTS (1 << 24)
+#define DPD_NN_MAX_SHAPES 65535
+int dpd_nn_dist(const float* ref, const float* qry, int S, int P, int M, float* dist, int32_t* arg, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pose algebra of the iterative registration that consumes DPDist as its loss (row f2; csrc/pose.hip): ONE launch for the chain of
  * ~115 element-wise ops the reference runs per refinement loop.  pred [B,7] = the pose network's raw output (t, angle, axis).
  *   pose   [B,7]   (optional) quat_normalize(pred): (tanh(t) 0.1, cos(a/2), axis sin(a/2)), |a| <= lim_rot_deg
