@@ -1,0 +1,302 @@
+// Earth Mover's distance between two point sets by approximate matching (the published scheme of Fan et al.), the third loss of the
+// registration comparison (pcrnet-registration/run_train_and_eval_PCRNet.bash:64-72; utils/tf_util_loss.py:42-47 earth_mover).
+// The contract is stated in include/dpdist_capi.h (dpd_emd_fwd); it is the definition, there is no reference binary.
+//
+// Ten levels, each three dependent passes over the n x m pair grid.  A pass is either a row pass (a thread owns a point k of xyz1 and
+// sums over every l of xyz2) or a column pass (a thread owns l and sums over every k), and one pass needs the finished vectors of the one
+// before it, so a pass is a launch and the stream is the barrier:
+//     row<ratio>(L7) | col(L7) row<w,ratio>(L7,L6) | col(L6) row<w,ratio>(L6,L5) | ... | col(L-2) row<w>(L-2) | finish
+// Step 3 of a level and step 1 of the next are both row passes over the same pairs, so they share one launch (and one d^2): 21 pass
+// launches and one finish.  A pair's rows are split over ceil(n / 64) workgroups, so a 2048-point batch of 16 fills the device
+// (512 workgroups) where one workgroup per pair would use 16 of the 256 CUs.
+//
+// Fused form: w(k,l) = exp(level d^2) ratioL[k] ratioR[l] is what a level adds to match[l][k], and cost and both gradients are linear in the
+// match, so they are accumulated while w is in registers and match [B,m,n] is written only when the caller asks for it:
+//     row pass (owner k):     cost_k += sum_l w sqrt(d^2),   grad1[k] += sum_l w (x1_k - x2_l) / sqrt(max(d^2, 1e-20))
+//     column pass (owner l):  grad2[l] -= ratioR[l] * sum_k exp(level d^2) ratioL[k] (x1_k - x2_l) / sqrt(max(d^2, 1e-20))
+// (ratioR[l] is a factor of every w of column l, so the column pass that computes it can apply it to a sum it already runs over).
+//
+// Geometry: 256 threads = 4 waves.  Lane i of EVERY wave owns point 64 * blockIdx.y + i; the other cloud sits in LDS as float4
+// {x, y, z, its vector entry} and wave v scans quarter v of it (all lanes read one address: a broadcast ds_read_b128 per pair of points).
+// The four partial sums of a point are combined through LDS as (p0 + p1) + (p2 + p3).  Every sum has one order, there are no atomics, and
+// every output element has one writer per launch: two runs give identical bits.
+// exp goes through v_exp_f32 (base 2) with log2(e) folded into the level on the host; 1 / sqrt through v_rsq_f32.
+#include "common.h"
+
+namespace dpd {
+
+constexpr int kEmdThreads = 256;
+constexpr int kEmdWaves = kEmdThreads / kWave;   // 4
+constexpr int kEmdMax = DPD_EMD_MAX_POINTS;      // 2048: the staged cloud is 32 KiB of LDS
+constexpr int kEmdLevels = 10;
+
+struct EmdWs {            // carved from the caller's workspace, floats
+    float* remainL;       // [B,n]
+    float* ratioL;        // [B,n]
+    float* costk;         // [B,n]  sum_l match[l][k] sqrt(d^2)
+    float* remainR;       // [B,m]
+    float* ratioR;        // [B,m]
+};
+
+__device__ __forceinline__ float emd_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ float emd_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
+
+// stage `cnt` points of cloud p [cnt,3] with their vector entry v (or the constant c when v is NULL) as float4 {x,y,z,v}
+__device__ __forceinline__ void emd_stage(float4* s, const float* __restrict__ p, const float* __restrict__ v, float c, int cnt) {
+    for (int i = threadIdx.x; i < cnt; i += kEmdThreads) s[i] = make_float4(p[i * 3], p[i * 3 + 1], p[i * 3 + 2], v ? v[i] : c);
+}
+
+// Row pass.  W: step 3 of the level whose base-2 exponent scale is lw (match += w, remainL -= sum w, cost and grad1);
+// R: step 1 of the level with scale lr (ratioL).  first: no level has run yet (remainL / remainR are their initial constants, the
+// accumulators are written, not added to); gs is 1 except in the last launch, where grad1 leaves scaled.
+template <bool W, bool R>
+__global__ __launch_bounds__(kEmdThreads) void emd_row_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n, int m,
+                                                              float lw, float lr, int first, EmdWs ws, float* __restrict__ grad1,
+                                                              float* __restrict__ match, float gs) {
+    __shared__ float4 s2[kEmdMax];                       // {x2, y2, z2, remainR[l]}
+    __shared__ float sR[W ? kEmdMax : 1];                // ratioR[l]
+    __shared__ float red[kEmdWaves][6][kWave];
+    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const float* p2 = xyz2 + (size_t)b * m * 3;
+    const float initL = (float)max(n, m) / (float)n, initR = (float)max(n, m) / (float)m;
+    // step 1 of the first level reads the initial remainR; later ones read what the column pass left
+    emd_stage(s2, p2, (first && !W) ? nullptr : ws.remainR + (size_t)b * m, initR, m);
+    if (W)
+        for (int i = threadIdx.x; i < m; i += kEmdThreads) sR[i] = ws.ratioR[(size_t)b * m + i];
+    __syncthreads();
+
+    const int k0 = blockIdx.y * kWave + lane;
+    const int k = min(k0, n - 1);                        // a tail lane recomputes the last point and stores nothing
+    const float* p1 = xyz1 + ((size_t)b * n + k) * 3;
+    const float x = p1[0], y = p1[1], z = p1[2];
+    const float rl = W ? ws.ratioL[(size_t)b * n + k] : 0.f;
+    float* mrow = match ? match + (size_t)b * m * n + k : nullptr;
+
+    const int per = (m + kEmdWaves - 1) / kEmdWaves;
+    const int l0 = wave * per, l1 = min(m, l0 + per);
+    float sw = 0.f, sc = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, sr = 0.f;
+#pragma unroll 4
+    for (int l = l0; l < l1; ++l) {
+        const float4 q = s2[l];
+        const float dx = x - q.x, dy = y - q.y, dz = z - q.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (W) {
+            const float w = emd_exp2(lw * d2) * rl * sR[l];
+            const float inv = emd_rsqrt(fmaxf(d2, 1e-20f));
+            sw += w;
+            sc += w * (d2 * inv);                        // w sqrt(d^2); 0 at d^2 = 0
+            const float t = w * inv;
+            gx += t * dx, gy += t * dy, gz += t * dz;
+            if (mrow && k0 < n) {                        // lanes = consecutive k: coalesced
+                float* e = mrow + (size_t)l * n;
+                *e = first ? w : *e + w;
+            }
+        }
+        if (R) sr += emd_exp2(lr * d2) * q.w;
+    }
+    red[wave][0][lane] = sw, red[wave][1][lane] = sc, red[wave][2][lane] = gx, red[wave][3][lane] = gy, red[wave][4][lane] = gz,
+    red[wave][5][lane] = sr;
+    __syncthreads();
+    if (wave != 0 || k0 >= n) return;
+    float t[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
+    const size_t ik = (size_t)b * n + k;
+    float rem = (first && !W) ? initL : ws.remainL[ik];
+    if (W) {
+        rem = fmaxf(0.f, rem - t[0]);
+        ws.remainL[ik] = rem;
+        ws.costk[ik] = first ? t[1] : ws.costk[ik] + t[1];
+        if (grad1) {
+            float* g = grad1 + ik * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = first ? t[2 + c] : g[c] + t[2 + c];
+                g[c] = v * gs;
+            }
+        }
+    } else {
+        ws.remainL[ik] = rem;
+    }
+    if (R) ws.ratioL[ik] = rem / (1e-9f + t[5]);
+}
+
+// Column pass: step 2 of the level with base-2 exponent scale lv, and grad2's share of that level.
+template <bool G>
+__global__ __launch_bounds__(kEmdThreads) void emd_col_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n, int m,
+                                                              float lv, int first, EmdWs ws, float* __restrict__ grad2, float gs) {
+    __shared__ float4 s1[kEmdMax];                       // {x1, y1, z1, ratioL[k]}
+    __shared__ float red[kEmdWaves][4][kWave];
+    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    emd_stage(s1, xyz1 + (size_t)b * n * 3, ws.ratioL + (size_t)b * n, 0.f, n);
+    __syncthreads();
+
+    const int l0 = blockIdx.y * kWave + lane;
+    const int l = min(l0, m - 1);
+    const float* p2 = xyz2 + ((size_t)b * m + l) * 3;
+    const float x = p2[0], y = p2[1], z = p2[2];
+
+    const int per = (n + kEmdWaves - 1) / kEmdWaves;
+    const int k0 = wave * per, k1 = min(n, k0 + per);
+    float s = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll 4
+    for (int k = k0; k < k1; ++k) {
+        const float4 q = s1[k];
+        const float dx = q.x - x, dy = q.y - y, dz = q.z - z;          // x1 - x2, the sign grad1 uses
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float a = emd_exp2(lv * d2) * q.w;
+        s += a;
+        if (G) {
+            const float t = a * emd_rsqrt(fmaxf(d2, 1e-20f));
+            gx += t * dx, gy += t * dy, gz += t * dz;
+        }
+    }
+    red[wave][0][lane] = s;
+    if (G) red[wave][1][lane] = gx, red[wave][2][lane] = gy, red[wave][3][lane] = gz;
+    __syncthreads();
+    if (wave != 0 || l0 >= m) return;
+    const size_t il = (size_t)b * m + l;
+    const float rem = first ? (float)max(n, m) / (float)m : ws.remainR[il];
+    const float sum = rem * ((red[0][0][lane] + red[1][0][lane]) + (red[2][0][lane] + red[3][0][lane]));
+    const float rr = fminf(rem / (sum + 1e-9f), 1.0f) * rem;
+    ws.ratioR[il] = rr;
+    ws.remainR[il] = fmaxf(0.f, rem - sum);
+    if (G) {
+        float* g = grad2 + il * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = (red[0][1 + c][lane] + red[1][1 + c][lane]) + (red[2][1 + c][lane] + red[3][1 + c][lane]);
+            const float v = first ? -(rr * t) : g[c] - rr * t;
+            g[c] = v * gs;
+        }
+    }
+}
+
+// cost[b] = sum_k costk[b][k] and loss = mean_b cost[b] / n, one workgroup, fixed order
+__global__ __launch_bounds__(256) void emd_finish_kernel(const float* __restrict__ costk, int B, int n, float* __restrict__ cost,
+                                                         float* __restrict__ loss) {
+    __shared__ float red[4];
+    float tot = 0.f;
+    for (int b = 0; b < B; ++b) {
+        float s = 0.f;
+        for (int k = threadIdx.x; k < n; k += 256) s += costk[(size_t)b * n + k];
+        s = block_sum_256(s, red);
+        if (threadIdx.x == 0) cost[b] = s;
+        tot += s / (float)n;
+    }
+    if (threadIdx.x == 0) loss[0] = tot / (float)B;
+}
+
+// cost and gradients of a GIVEN match (the op's match_cost): dir 0 owns k (cost, grad1), dir 1 owns l (grad2)
+__global__ __launch_bounds__(kEmdThreads) void emd_match_cost_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n,
+                                                                     int m, const float* __restrict__ match, int chunks1,
+                                                                     float* __restrict__ costk, float* __restrict__ grad1,
+                                                                     float* __restrict__ grad2, float gs) {
+    __shared__ float4 so[kEmdMax];
+    __shared__ float red[kEmdWaves][4][kWave];
+    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const bool dir = (int)blockIdx.y >= chunks1;
+    const int chunk = dir ? blockIdx.y - chunks1 : blockIdx.y;
+    const int nown = dir ? m : n, noth = dir ? n : m;
+    const float* own = (dir ? xyz2 : xyz1) + (size_t)b * nown * 3;
+    emd_stage(so, (dir ? xyz1 : xyz2) + (size_t)b * noth * 3, nullptr, 0.f, noth);
+    __syncthreads();
+    const int i0 = chunk * kWave + lane, i = min(i0, nown - 1);
+    const float x = own[i * 3], y = own[i * 3 + 1], z = own[i * 3 + 2];
+    const float* mt = match + (size_t)b * m * n;
+    const int per = (noth + kEmdWaves - 1) / kEmdWaves;
+    const int j0 = wave * per, j1 = min(noth, j0 + per);
+    float sc = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    for (int j = j0; j < j1; ++j) {
+        const float4 q = so[j];
+        const float dx = x - q.x, dy = y - q.y, dz = z - q.z;          // own - other: d cost / d own
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float w = dir ? mt[(size_t)i * n + j] : mt[(size_t)j * n + i];
+        const float inv = emd_rsqrt(fmaxf(d2, 1e-20f));
+        sc += w * (d2 * inv);
+        const float t = w * inv;
+        gx += t * dx, gy += t * dy, gz += t * dz;
+    }
+    red[wave][0][lane] = sc, red[wave][1][lane] = gx, red[wave][2][lane] = gy, red[wave][3][lane] = gz;
+    __syncthreads();
+    if (wave != 0 || i0 >= nown) return;
+    float t[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
+    if (!dir) costk[(size_t)b * n + i] = t[0];
+    float* g = dir ? grad2 : grad1;
+    if (g)
+        for (int c = 0; c < 3; ++c) g[((size_t)b * nown + i) * 3 + c] = t[1 + c] * gs;
+}
+
+static int emd_check(const void* xyz1, const void* xyz2, int B, int n, int m, const void* cost, const void* loss, const void* ws,
+                     size_t ws_bytes) {
+    if (!xyz1 || !xyz2 || !cost || !loss || !ws) return DPD_E_NULL;
+    if (B <= 0 || n <= 0 || m <= 0) return DPD_E_DIM;
+    if (n > kEmdMax || m > kEmdMax) return DPD_E_UNSUPPORTED;
+    if (ws_bytes < dpd_emd_workspace_bytes(B, n, m)) return DPD_E_WORKSPACE;
+    return 0;
+}
+
+static EmdWs emd_carve(void* ws, int B, int n, int m) {
+    float* f = (float*)ws;
+    const size_t bn = (size_t)B * n, bm = (size_t)B * m;
+    return EmdWs{f, f + bn, f + 2 * bn, f + 3 * bn, f + 3 * bn + bm};
+}
+
+}  // namespace dpd
+
+extern "C" size_t dpd_emd_workspace_bytes(int B, int n, int m) {
+    if (B <= 0 || n <= 0 || m <= 0 || n > dpd::kEmdMax || m > dpd::kEmdMax) return 0;
+    return ((size_t)B * n * 3 + (size_t)B * m * 2) * sizeof(float);
+}
+
+extern "C" int dpd_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, int m, float gscale, float* cost, float* loss, float* grad1,
+                           float* grad2, float* match, void* ws, size_t ws_bytes, void* stream) {
+    using namespace dpd;
+    if (const int rc = emd_check(xyz1, xyz2, B, n, m, cost, loss, ws, ws_bytes)) return rc;
+    const EmdWs w = emd_carve(ws, B, n, m);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grow(B, (n + kWave - 1) / kWave), gcol(B, (m + kWave - 1) / kWave), blk(kEmdThreads);
+    const float gs = gscale / ((float)B * (float)n);
+    float lv[kEmdLevels];                                 // level * log2(e): exp(level d^2) = exp2(lv d^2)
+    for (int i = 0; i < kEmdLevels; ++i) {
+        const int j = 7 - i;
+        const double level = j == -2 ? 0.0 : -(j >= 0 ? (double)(1 << (2 * j)) : 0.25);
+        lv[i] = (float)(level * 1.4426950408889634074);
+    }
+    DPD_LAUNCH((emd_row_kernel<false, true>), grow, blk, 0, s, xyz1, xyz2, n, m, 0.f, lv[0], 1, w, grad1, match, 1.f);
+    DPD_CHECK_LAUNCH();
+    for (int i = 0; i < kEmdLevels; ++i) {
+        const int first = i == 0;
+        const bool last = i == kEmdLevels - 1;
+        if (grad2)
+            DPD_LAUNCH((emd_col_kernel<true>), gcol, blk, 0, s, xyz1, xyz2, n, m, lv[i], first, w, grad2, last ? gs : 1.f);
+        else
+            DPD_LAUNCH((emd_col_kernel<false>), gcol, blk, 0, s, xyz1, xyz2, n, m, lv[i], first, w, grad2, 1.f);
+        DPD_CHECK_LAUNCH();
+        if (!last)
+            DPD_LAUNCH((emd_row_kernel<true, true>), grow, blk, 0, s, xyz1, xyz2, n, m, lv[i], lv[i + 1], first, w, grad1, match, 1.f);
+        else
+            DPD_LAUNCH((emd_row_kernel<true, false>), grow, blk, 0, s, xyz1, xyz2, n, m, lv[i], 0.f, first, w, grad1, match, gs);
+        DPD_CHECK_LAUNCH();
+    }
+    DPD_LAUNCH(emd_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)w.costk, B, n, cost, loss);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_emd_match_cost(const float* xyz1, const float* xyz2, int B, int n, int m, const float* match, float gscale,
+                                  float* cost, float* loss, float* grad1, float* grad2, void* ws, size_t ws_bytes, void* stream) {
+    using namespace dpd;
+    if (!match) return DPD_E_NULL;
+    if (const int rc = emd_check(xyz1, xyz2, B, n, m, cost, loss, ws, ws_bytes)) return rc;
+    const EmdWs w = emd_carve(ws, B, n, m);
+    const int c1 = (n + kWave - 1) / kWave, c2 = grad2 ? (m + kWave - 1) / kWave : 0;
+    DPD_LAUNCH(emd_match_cost_kernel, dim3(B, c1 + c2), dim3(kEmdThreads), 0, (hipStream_t)stream, xyz1, xyz2, n, m, match, c1, w.costk,
+               grad1, grad2, gscale / ((float)B * (float)n));
+    DPD_CHECK_LAUNCH();
+    DPD_LAUNCH(emd_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)w.costk, B, n, cost, loss);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}

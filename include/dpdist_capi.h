@@ -345,6 +345,34 @@ int dpd_chamfer_bwd(const float* a, const float* b, int B, int N, int M, const i
 int dpd_nn_dist(const float* ref, const float* qry, int S, int P, int M, float* dist, int32_t* arg, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Earth Mover's distance by approximate matching (Fan et al.), the EMD loss of the registration baselines
+ * (utils/tf_util_loss.py:42-47 earth_mover; csrc/emd.hip).  This comment is the definition.
+ * For each pair b, xyz1 [B,n,3] has n points and xyz2 [B,m,3] has m.  All arithmetic is fp32; d2(k,l) = (dx*dx + dy*dy) + dz*dz.
+ * Matching: remainL[k] = max(n,m)/n, remainR[l] = max(n,m)/m, match[l][k] = 0 (shape [m][n]).  For j = 7, 6, ..., -2 take
+ * level = -4^j, except level = 0 at j = -2; each level runs three steps:
+ *   1. for every k: ratioL[k] = remainL[k] / (1e-9 + sum_l exp(level d2(k,l)) remainR[l])
+ *   2. for every l: s = remainR[l] * sum_k exp(level d2(k,l)) ratioL[k];  ratioR[l] = min(remainR[l] / (s + 1e-9), 1) * remainR[l];
+ *      then remainR[l] = max(0, remainR[l] - s)
+ *   3. for every k, with w(k,l) = exp(level d2(k,l)) ratioL[k] ratioR[l]:  match[l][k] += w(k,l) for every l;
+ *      remainL[k] = max(0, remainL[k] - sum_l w(k,l))
+ * Cost and loss: cost[b] = sum_{k,l} match[l][k] sqrt(d2(k,l));  loss[0] = mean_b(cost[b] / n).
+ * Gradient (the match is a constant): d cost / d xyz1[k] = sum_l match[l][k] (xyz1[k] - xyz2[l]) / sqrt(max(d2, 1e-20)), d cost / d xyz2[l]
+ * the negative of the corresponding sum over k; grad1 [B,n,3] and grad2 [B,m,3] receive them times gscale / (B n), i.e.
+ * gscale * d loss / d xyz.  grad1, grad2 and match [B,m,n] are optional (NULL: not computed / not written): cost and gradients are
+ * accumulated level by level from w, so nothing of size [B,m,n] exists unless match is asked for, and they are the same bits with
+ * and without it.  exp is the hardware base-2 exponential of (level log2 e) d2, 1/sqrt the hardware reciprocal square root.
+ * Every sum has a fixed order and there are no atomics: two calls give identical bits.
+ * ws: dpd_emd_workspace_bytes(B, n, m) bytes of device scratch (the four vectors and per-point cost; DPD_E_WORKSPACE if smaller).
+ * 1 <= n, m <= DPD_EMD_MAX_POINTS and B >= 1; beyond: DPD_E_UNSUPPORTED (dpd_emd_workspace_bytes: 0).
+ * dpd_emd_match_cost: cost, loss and the gradients of the same formulas for a GIVEN match [B,m,n] (the op's match_cost).           */
+#define DPD_EMD_MAX_POINTS 2048
+size_t dpd_emd_workspace_bytes(int B, int n, int m);
+int dpd_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, int m, float gscale, float* cost, float* loss, float* grad1,
+                float* grad2, float* match, void* ws, size_t ws_bytes, void* stream);
+int dpd_emd_match_cost(const float* xyz1, const float* xyz2, int B, int n, int m, const float* match, float gscale, float* cost,
+                       float* loss, float* grad1, float* grad2, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pose algebra of the iterative registration that consumes DPDist as its loss (row f2; csrc/pose.hip): ONE launch for the chain of
  * ~115 element-wise ops the reference runs per refinement loop.  pred [B,7] = the pose network's raw output (t, angle, axis).
  *   pose   [B,7]   (optional) quat_normalize(pred): (tanh(t) 0.1, cos(a/2), axis sin(a/2)), |a| <= lim_rot_deg

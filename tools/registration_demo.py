@@ -4,7 +4,7 @@ network with DPDist as the loss at the reference's workload (batch 16, 64 points
 / U(-0.01,0.01)^3: pcrnet-registration/run_train_and_eval_PCRNet.bash:16-40), and report the reference's metric
 (results_itrPCRNet_no_stop.py:112-133,465-474: find_errors(gt_pose, find_final_pose_inv(T))) on held-out pairs.
 
-    python tools/registration_demo.py [--dp_steps 6000] [--reg_steps 6000] [--batch 16] [--loss ours|chamfer|both] [--gpus N] [--num_point 64]
+    python tools/registration_demo.py [--dp_steps 6000] [--reg_steps 6000] [--batch 16] [--loss ours|chamfer|emd|both|all] [--gpus N] [--num_point 64]
 
 --num_point: points per registration cloud (the reference's --num_point: 256 / 512 / 1024 / 2048, default 512, iterative_PCRNet_ours.py:40;
 this demo's default stays 64).  DPDist itself is trained on 64-point chair clouds either way.
@@ -37,7 +37,8 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--loops", type=int, default=8)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--loss", default="both", choices=["ours", "chamfer", "both"])
+    ap.add_argument("--loss", default="both", choices=["ours", "chamfer", "emd", "both", "all"],
+                    help="both = ours + chamfer; all = ours + chamfer + emd (the reference's three runs)")
     ap.add_argument("--eval_pairs", type=int, default=128)
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--num_point", type=int, default=64, help="points per registration cloud")
@@ -64,6 +65,7 @@ def main():
     import torch.distributed as dist
     from dpdist_amd import synth
     from dpdist_amd.aue import chamfer_dist
+    from dpdist_amd.emd import earth_mover
     from dpdist_amd.model import DPDistLoss, DPDistModel
     from dpdist_amd.registration import IterativeRegistration, PoseNet, centroid_residual, find_errors, find_final_pose_inv
     from dpdist_amd.trainer import DPDistTrainer
@@ -114,7 +116,7 @@ def main():
           "(reference's floor for 64 points: ~0.02, train_multi_gpu_pc_compare_dist.py:51-52)" % (a.dp_steps, t2 - t1, t1 - t0, ev))
     out["dpdist"] = {"steps": a.dp_steps, "train_l1": run, "heldout_l1": float(ev), "tilt_deg": a.tilt}
 
-    # 2. iterative PCRNet, DPDist frozen, as the loss ('ours') and the reference's Chamfer baseline (iterative_PCRNet.py)
+    # 2. iterative PCRNet, DPDist frozen, as the loss ('ours') and the reference's Chamfer and EMD baselines (iterative_PCRNet.py --loss_type)
     es_all, et_all, eg_all = synth.registration_pairs(a.eval_pairs, a.num_point, seed=99)
     per = (a.eval_pairs + world - 1) // world                # held-out pairs are split over the ranks
     sl = slice(rank * per, min(a.eval_pairs, (rank + 1) * per))
@@ -149,12 +151,13 @@ def main():
                 "centroid_residual_median": float(np.median(errs[:, 2])), "rot_err_deg": float(errs[:, 1].mean()),
                 "rot_err_median_deg": float(np.median(errs[:, 1])), "rot_success_5deg": float((errs[:, 1] < 5).mean())}
 
-    for name in (["ours", "chamfer"] if a.loss == "both" else [a.loss]):
+    baselines = {"chamfer": lambda moved, tmpl: chamfer_dist(moved, tmpl), "emd": lambda moved, tmpl: earth_mover(moved, tmpl)}
+    for name in {"both": ["ours", "chamfer"], "all": ["ours", "chamfer", "emd"]}.get(a.loss, [a.loss]):
         torch.manual_seed(0)                                  # the same pose network on every rank (replicated variables)
         net = PoseNet().to(dev)
         torch.manual_seed(1000 + rank)                       # ... but its own dropout masks
         rng = np.random.default_rng(1000 * rank)             # ... and its own pairs
-        loss_fn = dp_loss if name == "ours" else (lambda moved, tmpl: chamfer_dist(moved, tmpl))
+        loss_fn = dp_loss if name == "ours" else baselines[name]
         hb.beat("reducer:pose network")
         reg = IterativeRegistration(net, loss_fn, lr=a.lr, max_loops=a.loops, distributed=use_dist)
         hb.beat("eval:before training")
