@@ -9,6 +9,7 @@
 // Ties in the minimum (measure zero for float clouds) go to the lowest index; tf.reduce_min would split the
 // gradient evenly among them.
 #include "common.h"
+#include "chamfer_scan.h"
 
 namespace dpd {
 
@@ -18,27 +19,7 @@ __global__ __launch_bounds__(256) void chamfer_min_kernel(const float* __restric
                                                           float* __restrict__ min_b, int32_t* __restrict__ arg_b, int chunks_a,
                                                           int chunks_b) {
     extern __shared__ float s_y[];   // [ny][3]
-    const int per = chunks_a + chunks_b;
-    const int c = blockIdx.x / per, r = blockIdx.x % per;
-    const bool dir = r >= chunks_a;
-    const int chunk = dir ? r - chunks_a : r;
-    const int nx = dir ? M : N, ny = dir ? N : M;
-    const float* x = (dir ? b : a) + (size_t)c * nx * 3;
-    const float* y = (dir ? a : b) + (size_t)c * ny * 3;
-    for (int e = threadIdx.x; e < ny * 3; e += 256) s_y[e] = y[e];
-    __syncthreads();
-    const int i = chunk * 256 + threadIdx.x;
-    if (i >= nx) return;
-    const float px = x[i * 3], py = x[i * 3 + 1], pz = x[i * 3 + 2];
-    float best = INFINITY;
-    int bj = 0;
-    for (int j = 0; j < ny; ++j) {
-        const float dx = px - s_y[j * 3], dy = py - s_y[j * 3 + 1], dz = pz - s_y[j * 3 + 2];
-        const float d = (dx * dx + dy * dy) + dz * dz;      // reduce_sum over the 3 coordinates, in order (:905)
-        if (d < best) { best = d; bj = j; }
-    }
-    (dir ? min_b : min_a)[(size_t)c * nx + i] = best;
-    (dir ? arg_b : arg_a)[(size_t)c * nx + i] = bj;
+    chamfer_min_scan(a, b, N, M, min_a, arg_a, min_b, arg_b, chunks_a, chunks_b, s_y);
 }
 
 // loss = (mean(min_a) + mean(min_b)) / 2, fixed summation order (one workgroup)

@@ -23,38 +23,9 @@
 //                       (fc4, chain, move, T composition) is the prologue of the NEXT loop's pose_point_kernel (PoseMove), not a launch
 // fp32 throughout (MFMA fp32 / FMA).  The training evaluation of the network and its backward: further down (round 6).
 #include "common.h"
+#include "pose_math.h"
 
 namespace dpd {
-
-struct Pose7 {
-    float t[3];
-    float q[4];
-};
-
-// models/ipcr_model.py:285-294; lim_rad = pi/180 * lim_rot.  lim_rad == 0: the network's output IS the pose (lim_rot falsy).
-__device__ __forceinline__ Pose7 quat_normalize_dev(const float* __restrict__ p, float lim_rad) {
-    Pose7 o;
-    if (lim_rad == 0.f) {
-        o.t[0] = p[0]; o.t[1] = p[1]; o.t[2] = p[2];
-        o.q[0] = p[3]; o.q[1] = p[4]; o.q[2] = p[5]; o.q[3] = p[6];
-        return o;
-    }
-    const float ang = tanhf(p[3]) * lim_rad;
-    const float r = sqrtf(p[4] * p[4] + p[5] * p[5] + p[6] * p[6]) + 1e-6f;
-    const float s = sinf(ang / 2.f);
-    o.t[0] = tanhf(p[0]) * 0.1f; o.t[1] = tanhf(p[1]) * 0.1f; o.t[2] = tanhf(p[2]) * 0.1f;
-    o.q[0] = cosf(ang / 2.f);
-    o.q[1] = p[4] / r * s; o.q[2] = p[5] / r * s; o.q[3] = p[6] / r * s;
-    return o;
-}
-
-// helper.py:552-554 (no normalisation inside)
-__device__ __forceinline__ void quat_to_mat_dev(const float* q, float R[3][3]) {
-    const float q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-    R[0][0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3; R[0][1] = 2.f * (q1 * q2 - q0 * q3); R[0][2] = 2.f * (q1 * q3 + q0 * q2);
-    R[1][0] = 2.f * (q1 * q2 + q0 * q3); R[1][1] = q0 * q0 + q2 * q2 - q1 * q1 - q3 * q3; R[1][2] = 2.f * (q2 * q3 - q0 * q1);
-    R[2][0] = 2.f * (q1 * q3 - q0 * q2); R[2][1] = 2.f * (q2 * q3 + q0 * q1); R[2][2] = q0 * q0 + q3 * q3 - q1 * q1 - q2 * q2;
-}
 
 // one workgroup (one wave) per cloud pair.  mode 0: refinement loop (helper.transformation_quat2mat: quaternion / max(|q|, 1e-12), the
 // moved cloud and T_out use the same normalised pose); mode 1: training evaluation (moved cloud from quaternion / (|q| + 1e-7),
@@ -106,7 +77,7 @@ __global__ __launch_bounds__(64) void pose_apply_fwd_kernel(const float* __restr
         for (int j = 0; j < 7; ++j) pr[j] = pred[(size_t)b * 7 + j];
     }
     const Pose7 P = quat_normalize_dev(pr, lim_rad);
-    const float nrm = sqrtf(P.q[0] * P.q[0] + P.q[1] * P.q[1] + P.q[2] * P.q[2] + P.q[3] * P.q[3]);
+    const float nrm = quat_norm_dev(P.q);
     const float dc = fmaxf(nrm, 1e-12f), dt = nrm + 1e-7f;
     float qc[4], qm[4];
 #pragma unroll
@@ -131,9 +102,7 @@ __global__ __launch_bounds__(64) void pose_apply_fwd_kernel(const float* __restr
         float Rc[3][3];
         quat_to_mat_dev(qc, Rc);
         const int i = threadIdx.x >> 2;
-        float v;
-        if (i < 3) v = ((Rc[i][0] * Tc[0] + Rc[i][1] * Tc[1]) + Rc[i][2] * Tc[2]) + P.t[i] * Tc[3];
-        else v = Tc[3];
+        const float v = pose_compose_entry(Rc, P.t, Tc, i);
         T_out[(size_t)b * 16 + threadIdx.x] = v;
     }
 }
@@ -162,7 +131,7 @@ __global__ __launch_bounds__(64) void pose_apply_bwd_kernel(const float* __restr
     if (threadIdx.x != 0) return;
     const float* p = pred + (size_t)b * 7;
     const Pose7 P = quat_normalize_dev(p, lim_rad);
-    const float nrm = sqrtf(P.q[0] * P.q[0] + P.q[1] * P.q[1] + P.q[2] * P.q[2] + P.q[3] * P.q[3]);
+    const float nrm = quat_norm_dev(P.q);
     const float den = nrm + 1e-7f;
     const float u0 = P.q[0] / den, u1 = P.q[1] / den, u2 = P.q[2] / den, u3 = P.q[3] / den;
     const float (*dR)[3] = reinterpret_cast<const float (*)[3]>(acc);
@@ -377,7 +346,7 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
 #pragma unroll
         for (int j = 0; j < 7; ++j) pr[j] = prs[j];
         const Pose7 P = quat_normalize_dev(pr, mv.lim_rad);
-        const float nrm = sqrtf(P.q[0] * P.q[0] + P.q[1] * P.q[1] + P.q[2] * P.q[2] + P.q[3] * P.q[3]);
+        const float nrm = quat_norm_dev(P.q);
         const float dc = fmaxf(nrm, 1e-12f);
         float qc[4];
 #pragma unroll
@@ -391,9 +360,7 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
                 float Tc[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Tc[r] = mv.T_in ? mv.T_in[(size_t)c * 16 + r * 4 + j] : (r == j ? 1.f : 0.f);
-                float v;
-                if (i < 3) v = ((R[i][0] * Tc[0] + R[i][1] * Tc[1]) + R[i][2] * Tc[2]) + P.t[i] * Tc[3];
-                else v = Tc[3];
+                const float v = pose_compose_entry(R, P.t, Tc, i);
                 mv.T_out[(size_t)c * 16 + t] = v;
             }
         }
@@ -564,7 +531,7 @@ extern "C" int dpd_pose_apply_fwd(const float* pred, const float* src, const flo
     if (!pose && !moved && !T_out) return DPD_E_NULL;
     if (T_out && T_out == T_in) return DPD_E_UNSUPPORTED;
     if (B <= 0 || N <= 0 || mode < 0 || mode > 1) return DPD_E_DIM;
-    const float lim_rad = (float)(3.14159265358979323846 / 180.0 * (double)lim_rot_deg);
+    const float lim_rad = dpd::lim_rad_of(lim_rot_deg);
     DPD_LAUNCH(dpd::pose_apply_fwd_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, pred, src, T_in, N, lim_rad, mode, pose, moved,
                T_out, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr);
     DPD_CHECK_LAUNCH();
@@ -575,7 +542,7 @@ extern "C" int dpd_pose_apply_bwd(const float* pred, const float* src, const flo
                                   void* stream) {
     if (!pred || !src || !dmoved || !dpred) return DPD_E_NULL;
     if (B <= 0 || N <= 0) return DPD_E_DIM;
-    const float lim_rad = (float)(3.14159265358979323846 / 180.0 * (double)lim_rot_deg);
+    const float lim_rad = dpd::lim_rad_of(lim_rot_deg);
     DPD_LAUNCH(dpd::pose_apply_bwd_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, pred, src, dmoved, N, lim_rad, dpred);
     DPD_CHECK_LAUNCH();
     return 0;
@@ -623,7 +590,7 @@ extern "C" int dpd_pose_refine(const dpd_pose_net* net, const float* src, const 
     const RefineWs w = refine_ws((float*)ws, B, N, OUT);
     if (ws_bytes < w.total) return DPD_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const float lim_rad = (float)(3.14159265358979323846 / 180.0 * (double)lim_rot_deg);
+    const float lim_rad = dpd::lim_rad_of(lim_rot_deg);
     const size_t lds = (size_t)kPointLds * sizeof(float);
     if (int rc = ensure_dyn_lds(g_point_lds, (const void*)pose_point_kernel<false>, lds)) return rc;
     PointNetW pw{};

@@ -92,6 +92,10 @@ SIGNATURES = {
     "dpd_pose_refine_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dpd_pose_refine": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "dpd_occlude": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dpd_pose_trace": (c_int, [c_void_p, c_int, c_int, c_float] + [c_void_p] * 7),
+    "dpd_chamfer_sqrt_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
+    "dpd_chamfer_sqrt_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "dpd_pose_point_bwd_workspace_bytes": (c_size_t, [c_int]),
     "dpd_pose_point_bwd_workspace_bytes_n": (c_size_t, [c_int, c_int]),
     "dpd_pose_point_tie_words": (c_int, [c_int]),

@@ -407,6 +407,53 @@ size_t dpd_pose_refine_workspace_bytes(int B, int N, int out_features);
 int dpd_pose_refine(const dpd_pose_net* net, const float* src, const float* tmpl, int B, int N, int loops, float lim_rot_deg,
                     const float* drop_mask, void* ws, size_t ws_bytes, float* moved, float* T_out, float* pred_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The registration experiment's test protocol (pcrnet-registration/results_itrPCRNet_no_stop.py; csrc/regtest.hip): the occlusion of
+ * the source clouds, the per-iteration error tables of the no-stop loop and the square-rooted Chamfer baseline.  None of the four
+ * entries allocates; all are stream-ordered and deterministic (fixed summation orders, no atomics).
+ *
+ * dpd_occlude: helper.add_occlusions (helper.py:963-982) with its host random draws passed in.  src [B,N,3]; per cloud b
+ *   d_i = sqrtf((dx*dx + dy*dy) + dz*dz), d? = src[b,i,?] - src[b,seed_idx[b],?], in fp32, in that order and not fused (the form of
+ *   dpd_nn_dist; equal to np.linalg.norm(s - p, 2, -1) on float32 input bit for bit).  The `drop` points with the smallest (d_i, i),
+ *   compared lexicographically (np.argsort(kind="stable")), are removed.  The S = N - drop survivors are emitted in ascending
+ *   (order_key[b,i], i) order -- order_key [B,N] is the caller's draw (uniform random numbers stand in for the reference's
+ *   np.random.shuffle; it decides which survivors the wrap-around duplicates) -- or, with order_key == NULL, in ascending (d_i, i) order
+ *   (the duplicates then all sit at the rim of the hole).  out [B,N,3]: out[b,j] = survivor[j mod S], the reference's
+ *   concatenate-with-itself-then-truncate; kept [B,N] (optional) receives the source index of every output row.  drop == 0 with a NULL
+ *   key is a copy.  Inputs are assumed finite (no NaN in src or order_key; the result for such a cloud is unspecified, but stays
+ *   inside the arrays).  seed_idx [B] int32 must lie in [0,N): that is the caller's to check (the kernel clamps it so that a bad index
+ *   cannot read outside the cloud).  drop < 0 or drop >= N: DPD_E_DIM (the reference would loop forever on an empty survivor set);
+ *   N > DPD_OCCLUDE_MAX_POINTS (the reference's MAX_NUM_POINT): DPD_E_UNSUPPORTED.
+ *
+ * dpd_pose_trace: pred [L,B,7] = the raw outputs of L refinement loops (dpd_pose_refine's pred_out) -> for every pair
+ *   T_all [L+1,B,4,4] fp32: T_all[0] = I, T_all[l+1] = [R(q / max(|q|, 1e-12)) t; 0 1] @ T_all[l], (t, q) = quat_normalize(pred[l]) --
+ *     the mode-0 arithmetic of dpd_pose_apply_fwd (the same device functions: T_all[L] is dpd_pose_refine's T_out bit for bit);
+ *   te, re, ce [L+1,B] double, from the fp32 T_all[l], all arithmetic in double:
+ *     te = | gt_t - (trans(inv T) + shift) |                                       (get_error + find_errors, :464-474, :112-116)
+ *     re = the angle, in degrees, of R_p R_gt^-1 with R_p = euler2mat(mat2euler(rot(inv T))) as helper.find_final_pose_inv and
+ *          find_errors build it (:118-133) -- the Euler round trip is the identity on a rotation, and maps the not-quite-orthogonal
+ *          fp32 product to one -- taken as atan2(|vee(E - E^T)| / 2, (tr E - 1) / 2) rather than acos, which loses half its digits
+ *          near 0 and 180 degrees;
+ *     ce[0] = 1, ce[l] = | T_all[l] inv(T_all[l-1]) - I |_F^2                                          (check_convergenceT, :155-167).
+ *   gt_pose [B,6] = (t, rx, ry, rz), radians, R_gt = Rx Ry Rz (registration.euler_to_mat); shift [B,3] or NULL = the centroid that was
+ *   subtracted from the source (the T of get_error).  T_all, te, re, ce are each optional (at least one; te and re need gt_pose).
+ *   One thread per pair.  L < 1 or B < 1: DPD_E_DIM.
+ *
+ * dpd_chamfer_sqrt_fwd / _bwd: PCRNet's Chamfer loss (utils/tf_util_loss.py:35-39), argument lists of dpd_chamfer_fwd / _bwd:
+ *   loss[0] = ( mean_bi sqrt(min_j |b_bi - a_bj|^2) + mean_bj sqrt(min_i |a_bj - b_bi|^2) ) / 2.
+ *   min_* receive the SQUARED minima and arg_* the indices: the bits dpd_chamfer_fwd stores (one scan, csrc/chamfer_scan.h).
+ *   Backward: autodiff through the stored argmins; a pair's term is (x - y) / |x - y| times its mean's weight.  DEVIATION: where a
+ *   minimum is 0 (coincident points) the reference's gradient is inf * 0 = NaN; here that pair contributes exactly zero.           */
+#define DPD_OCCLUDE_MAX_POINTS 2048
+int dpd_occlude(const float* src, const int32_t* seed_idx, const float* order_key, int B, int N, int drop, float* out, int32_t* kept,
+                void* stream);
+int dpd_pose_trace(const float* pred, int L, int B, float lim_rot_deg, const float* gt_pose, const float* shift, float* T_all, double* te,
+                   double* re, double* ce, void* stream);
+int dpd_chamfer_sqrt_fwd(const float* a, const float* b, int B, int N, int M, float* min_a, int32_t* arg_a, float* min_b, int32_t* arg_b,
+                         float* loss, void* stream);
+int dpd_chamfer_sqrt_bwd(const float* a, const float* b, int B, int N, int M, const int32_t* arg_a, const int32_t* arg_b, float gscale,
+                         float* da, float* db, void* stream);
+
 /* The TRAINING evaluation of the pose network's shared MLP + max pool (models/ipcr_model.py:198-233 inside the step of
  * pcrnet-registration/iterative_PCRNet_ours.py:442-470, which differentiates the network w.r.t. its weights only): forward with what the
  * backward needs, and TF / torch autodiff of the five 1x1 convolutions, their ReLUs and tf.reduce_max.

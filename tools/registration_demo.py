@@ -5,6 +5,14 @@ network with DPDist as the loss at the reference's workload (batch 16, 64 points
 (results_itrPCRNet_no_stop.py:112-133,465-474: find_errors(gt_pose, find_final_pose_inv(T))) on held-out pairs.
 
     python tools/registration_demo.py [--dp_steps 6000] [--reg_steps 6000] [--batch 16] [--loss ours|chamfer|emd|both|all] [--gpus N] [--num_point 64]
+                                      [--test_iterations N] [--add_occlusions F] [--noise] [--centroid_sub] [--chamfer_form squared|sqrt] [--log_dir DIR]
+
+The held-out pairs go through the reference's test protocol (results_itrPCRNet_no_stop.py; dpdist_amd/regtest.py): the per-iteration
+translation / rotation / convergence tables and the nested success buckets, with the source optionally occluded (--add_occlusions, the
+fraction of points cut out around a random point), perturbed (--noise) or centred (--centroid_sub).  --test_iterations: refinements of
+the test (default --loops, which makes the table's last row the transform `evaluate` reports).  --chamfer_form sqrt: the Chamfer leg
+trains with PCRNet's square-rooted form (utils/tf_util_loss.py:35-39) instead of the AUE task's squared one.  --log_dir: every leg's
+log_data.npz and test.txt (regtest.write_results) under DIR/<leg>.
 
 --num_point: points per registration cloud (the reference's --num_point: 256 / 512 / 1024 / 2048, default 512, iterative_PCRNet_ours.py:40;
 this demo's default stays 64).  DPDist itself is trained on 64-point chair clouds either way.
@@ -42,6 +50,12 @@ def main():
     ap.add_argument("--eval_pairs", type=int, default=128)
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--num_point", type=int, default=64, help="points per registration cloud")
+    ap.add_argument("--test_iterations", type=int, default=0, help="refinements of the no-stop test (default: --loops)")
+    ap.add_argument("--add_occlusions", type=float, default=0.0, help="fraction of every held-out source cut out around a random point")
+    ap.add_argument("--noise", action="store_true", help="perturb the held-out sources (helper.add_noise)")
+    ap.add_argument("--centroid_sub", action="store_true", help="centre the held-out sources before the test")
+    ap.add_argument("--chamfer_form", default="squared", choices=["squared", "sqrt"], help="sqrt = PCRNet's --loss_type chamf")
+    ap.add_argument("--log_dir", default="", help="write every leg's log_data.npz and test.txt under this directory")
     a = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if a.gpus != world:
@@ -63,11 +77,11 @@ def main():
     hb.beat("start:import")
     import torch
     import torch.distributed as dist
-    from dpdist_amd import synth
+    from dpdist_amd import regtest, synth
     from dpdist_amd.aue import chamfer_dist
     from dpdist_amd.emd import earth_mover
     from dpdist_amd.model import DPDistLoss, DPDistModel
-    from dpdist_amd.registration import IterativeRegistration, PoseNet, centroid_residual, find_errors, find_final_pose_inv
+    from dpdist_amd.registration import IterativeRegistration, PoseNet, centroid_residual, find_errors
     from dpdist_amd.trainer import DPDistTrainer
     share_gpu = os.environ.get("DPD_TEST_SHARE_GPU") == "1"      # tests only: every rank on GPU 0 over gloo (bench.py has the same switch)
     if share_gpu:
@@ -86,6 +100,9 @@ def main():
     cu = lambda x: torch.tensor(x, device=dev)   # noqa: E731
     out = {"n_gpus": world, "workload": {"batch_per_gpu": a.batch, "global_batch": a.batch * world, "num_point": a.num_point, "loops": a.loops, "lim_rot": 45.0, "poses": "U(-45,45)^3 deg, U(-.01,.01)^3",
                         "shapes": "synthetic box-union chairs"}}
+    test_iters = a.test_iterations or a.loops
+    out["test"] = {"iterations": test_iters, "add_occlusions": a.add_occlusions, "noise": a.noise, "centroid_sub": a.centroid_sub,
+                   "chamfer_form": a.chamfer_form, "eval_loss_on": "the pairs as they are (no occlusion, no noise)"}
 
     # 1. DPDist's own trainer (the hot path) on chair distance data: reference recipe = y-rotation + shift augmentation
     hb.beat("train:DPDist")
@@ -128,30 +145,42 @@ def main():
     out["identity"] = {"trans_err": float(ident[:, 0].mean()), "rot_err_deg": float(ident[:, 1].mean()), "centroid_residual": float(ident_c.mean())}
     dp_loss = DPDistLoss(model)
 
-    def evaluate(reg):
-        """the reference's metric on this rank's share of the held-out pairs, gathered on every rank"""
-        losses, errs = [], []
+    def evaluate(reg, full=False):
+        """the reference's test protocol on this rank's share of the held-out pairs, gathered on every rank; eval_loss is the loss of
+        the pairs as they are (no occlusion, no noise).  full: also the per-iteration table and the success buckets"""
+        losses = []
         for i in range(0, len(eg), a.batch):
-            l, T = reg.evaluate(es[i:i + a.batch], et[i:i + a.batch])
-            Tn = T.double().cpu().numpy()
-            fp = find_final_pose_inv(Tn)
-            cr = centroid_residual(Tn, eg[i:i + a.batch], es_np[i:i + a.batch])
-            errs += [find_errors(eg[i + j], fp[j]) + (cr[j],) for j in range(fp.shape[0])]
+            l, _ = reg.evaluate(es[i:i + a.batch], et[i:i + a.batch])
             losses.append(l.item())
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(4321 + rank)                          # every evaluation occludes / perturbs the pairs the same way
+        nst = regtest.no_stop_test(reg.net, es, et, eg, iterations=test_iters, batch=a.batch, occlusions=a.add_occlusions, noise=a.noise,
+                                   centroid_sub=a.centroid_sub, generator=gen)
+        Tn = nst["T"].astype(np.float64)
+        Tn[:, :3, 3] -= np.einsum("bij,bj->bi", Tn[:, :3, :3], nst["shift"].astype(np.float64))      # ... as transforms of the uncentred sources
+        tabs = np.stack([nst["TE"], nst["RE"], nst["CE"], np.tile(centroid_residual(Tn, eg, es_np), (test_iters + 1, 1))])
+        secs = nst["seconds"]
         if use_dist:
             parts = [None] * world
-            dist.all_gather_object(parts, (losses, errs))
-            losses, errs = sum((p_[0] for p_ in parts), []), sum((p_[1] for p_ in parts), [])
-        errs = np.array(errs)
+            dist.all_gather_object(parts, (losses, tabs, secs))
+            losses, tabs, secs = sum((p_[0] for p_ in parts), []), np.concatenate([p_[1] for p_ in parts], 2), max(p_[2] for p_ in parts)
+        res = regtest.summarize(tabs[0], tabs[1], tabs[2], secs)
+        errs = np.stack([tabs[0][-1], tabs[1][-1], tabs[3][-1]], 1)      # the table's last row: the final transform's errors
         # median / success rate are the stable figures (the mean is carried by a handful of outliers among the held-out pairs);
         # centroid_residual: where the registered source's centroid ends up -- the pose-space translation error mostly measures
         # rotation error x the centroid's lever arm (registration.centroid_residual)
-        return {"eval_loss": float(np.mean(losses)), "pairs": int(len(errs)), "trans_err": float(errs[:, 0].mean()),
-                "trans_err_median": float(np.median(errs[:, 0])), "centroid_residual": float(errs[:, 2].mean()),
-                "centroid_residual_median": float(np.median(errs[:, 2])), "rot_err_deg": float(errs[:, 1].mean()),
-                "rot_err_median_deg": float(np.median(errs[:, 1])), "rot_success_5deg": float((errs[:, 1] < 5).mean())}
+        ret = {"eval_loss": float(np.mean(losses)), "pairs": int(len(errs)), "trans_err": float(errs[:, 0].mean()),
+               "trans_err_median": float(np.median(errs[:, 0])), "centroid_residual": float(errs[:, 2].mean()),
+               "centroid_residual_median": float(np.median(errs[:, 2])), "rot_err_deg": float(errs[:, 1].mean()),
+               "rot_err_median_deg": float(np.median(errs[:, 1])), "rot_success_5deg": float((errs[:, 1] < 5).mean())}
+        if full:
+            ret["per_iteration"] = {k: res["per_iteration"][k].tolist() for k in ("rot_mean", "rot_std", "trans_mean", "conv_mean")}
+            ret["buckets"] = res["buckets"]
+            ret["test_pairs_per_s"] = res["pairs_per_s"]
+        return ret, res
 
-    baselines = {"chamfer": lambda moved, tmpl: chamfer_dist(moved, tmpl), "emd": lambda moved, tmpl: earth_mover(moved, tmpl)}
+    chamfer = regtest.chamfer_sqrt if a.chamfer_form == "sqrt" else chamfer_dist
+    baselines = {"chamfer": lambda moved, tmpl: chamfer(moved, tmpl), "emd": lambda moved, tmpl: earth_mover(moved, tmpl)}
     for name in {"both": ["ours", "chamfer"], "all": ["ours", "chamfer", "emd"]}.get(a.loss, [a.loss]):
         torch.manual_seed(0)                                  # the same pose network on every rank (replicated variables)
         net = PoseNet().to(dev)
@@ -161,7 +190,7 @@ def main():
         hb.beat("reducer:pose network")
         reg = IterativeRegistration(net, loss_fn, lr=a.lr, max_loops=a.loops, distributed=use_dist)
         hb.beat("eval:before training")
-        say("[%s] before training: %s" % (name, evaluate(reg)), flush=True)
+        say("[%s] before training: %s" % (name, evaluate(reg)[0]), flush=True)
         hb.beat("train:%s" % name)
         t0 = time.time()
         gen = 0.0
@@ -174,10 +203,12 @@ def main():
                 hb.beat("train:%s step %d" % (name, s + 1))
             if (s + 1) % 500 == 0:
                 hb.beat("eval:step %d" % (s + 1))
-                say("[%s] step %d  train loss %.4f  eval %s" % (name, s + 1, l.item(), evaluate(reg)), flush=True)
+                say("[%s] step %d  train loss %.4f  eval %s" % (name, s + 1, l.item(), evaluate(reg)[0]), flush=True)
                 hb.beat("train:%s step %d" % (name, s + 1))
         hb.beat("eval:final")
-        res = evaluate(reg)
+        res, tables = evaluate(reg, full=True)
+        if a.log_dir and rank == 0:
+            regtest.write_results(os.path.join(a.log_dir, name), tables)
         res["train_s"] = time.time() - t0
         res["host_gen_s"] = gen
         res["steps"] = a.reg_steps
