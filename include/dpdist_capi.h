@@ -534,7 +534,22 @@ int dpd_adam_tf_dev(float* p, const float* g, float* m, float* v, size_t n, cons
  *   K, N, lda, ldb, ldc multiples of 4; split_k >= 1 (slabs in ws, reduced by a second kernel,
  *   epilogue applied after the reduction); tile: 0 = auto (= 3); 3 = register-staged 64x64 (any K % 4 == 0); LDS-DMA ring
  *   kernels (K % 32 == 0, else 3 is used) 8 = 64x64/3-stage, 9 = 128x128/3-stage; register-streamed kernels (no LDS, no
- *   barriers; K % 32 == 0; csrc/gemm_rs.h): workgroup of 4 waves, wave tile 30 = 64x64, 31 = 64x32, 32 = 32x64, 33 = 32x32. */
+ *   barriers; K % 32 == 0; csrc/gemm_rs.h): workgroup of 4 waves, wave tile 30 = 64x64, 31 = 64x32, 32 = 32x64, 33 = 32x32.
+ * Pinned by tests/test_gemm_edges_gpu.py (exact against an int64 product, operands and output inside NaN guard bands):
+ *   - strides: lda, ldb, ldc may exceed the logical row; only A / B elements inside [M,K] / [K,N] are read and only C[0:M, 0:N]
+ *     is written.  The gate is read as gate[m * ldc + n]: it has the row stride of C, not N.  bias is [N];
+ *   - fall-back: tiles 8, 9, 30-33 need whole 32-deep K-tiles and M, N >= 4.  With K % 32 != 0, M < 4, N < 4, or a split_k whose
+ *     32-rounded slice length leaves the last slice empty (ceil32(ceil(K / split_k)) * (split_k - 1) >= K), the call runs on tile 3
+ *     instead: same result, any K % 4 == 0;
+ *   - split_k > 1: ws holds split_k slabs of M*N floats (ws_bytes >= split_k * M * N * 4, else DPD_E_WORKSPACE) and need not be
+ *     initialised: every slab is written whole before the reduction reads it, a slab whose K slice is empty as zeros;
+ *   - split_k = 0 = tail split, tiles 30-33 only: taken when ws_bytes >= 3 * M * N * 4, epilogue = 0, the launch has more than 256
+ *     workgroup tiles, its last round of 256 is less than 3/4 full and K gives pieces of at least 256 (csrc/gemm_rs.h); the
+ *     tiles of the last whole tile rows are then cut along K into at most 4 pieces (pieces - 1 slabs in ws, uninitialised is
+ *     fine).  In every other case split_k = 0 is silently split_k = 1 and ws is not touched;
+ *   - refusals, before anything is launched (C and ws untouched): DPD_E_NULL for a NULL A / B / C, epilogue 1 / 2 without bias,
+ *     epilogue 3 without gate; DPD_E_DIM for M, N, K <= 0 or split_k < 0; DPD_E_UNSUPPORTED for K, N, lda, ldb or ldc not a
+ *     multiple of 4, transA with M % 4 != 0, transA && transB, an epilogue outside 0..3, an unknown tile.                       */
 int dpd_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                  float* Cout, int ldc, const float* bias, const float* gate, int epilogue, int split_k, int tile,
                  void* ws, size_t ws_bytes, void* stream);
@@ -549,7 +564,15 @@ int dpd_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, in
  * [N,K]), 1 = R8 (A stored [K,M], B stored [K,N]); lda/ldb = row stride for RC, M resp. N for R8; K % 32 == 0;
  * epilogue/bias/gate as in dpd_gemm_f32; tile 0 = default.  out_rc / out_r8 (may be NULL): the result is ALSO
  * written as np planes, RC [np][M][N] and/or R8 [np][r8_rows/8][N][8] (rows < r8_rows), ready to be an operand of
- * the next GEMM; C may then be NULL.                                                                       */
+ * the next GEMM; C may then be NULL.
+ * Pinned by tests/test_gemm_edges_gpu.py (exact against an int64 product, every buffer inside NaN guard bands):
+ *   - dpd_split_planes: ld % 4 == 0; ld_rc, rc_plane and r8_plane (elements between planes) multiples of 8 (16-byte stores; the caller's
+ *     duty, not checked); ld, ld_rc may exceed C and the plane strides a plane: only src[0:R, 0:C] is read and only the np planes' [R, C] (RC) / [R/8][C][8] (R8) elements written;
+ *   - dpd_gemm_planes: a_fmt / b_fmt (0,1) = NN, (0,0) = NT, (1,1) = TN, (2,2) = TN with both operands as the RC planes of [K,M] / [K,N]
+ *     (tiles 0, 1, 2, 3, 5; M, N multiples of 8); lda / ldb multiples of 8, for an RC operand they may exceed its row and the padding
+ *     columns are never read; ldc % 4 == 0 may exceed N, only C[0:M, 0:N] is written; the gate has the row stride ldc;
+ *   - tiles: 1-5 with one or three planes, 13 one plane and K % 64 == 0, 21 / 23 one plane, 24 three planes; DPD_E_UNSUPPORTED otherwise;
+ *   - out_rc / out_r8 need M, N, r8_rows multiples of 8; out_rc is dense ([np][M][N]); rows >= r8_rows have no R8 output.              */
 int dpd_split_planes(const float* src, int R, int C, int ld, int np, void* rc, int ld_rc, long rc_plane, void* r8,
                      long r8_plane, void* stream);
 int dpd_gemm_planes(int np, int a_fmt, int b_fmt, int M, int N, int K, const void* A, int lda, long a_plane,
