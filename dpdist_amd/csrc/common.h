@@ -26,16 +26,22 @@
     } while (0)
 
 #include <atomic>
+#include <mutex>
 
 namespace dpd {
 
 constexpr int kMfvSlices = DPD_MFV_SLICES;   // workgroups per cloud in the encoder forward = partial norms per cloud
 
-// Opt a kernel into more than 64 KiB of dynamic LDS, once per (kernel, device): `slot` is a per-call-site static array of
-// flags indexed by the CURRENT device, so a process that drives several GPUs configures each of them (the attribute is
-// per device), and concurrent first calls are a benign repeat of an idempotent setting.
+// Opt a kernel into more than 64 KiB of dynamic LDS, per (kernel, device): `slot` belongs to ONE kernel and holds, indexed by the
+// CURRENT device, the number of bytes the attribute was last set to, so a process that drives several GPUs configures each of
+// them (the attribute is per device).  The attribute is raised whenever a request exceeds what was set before: callers size their
+// LDS by run-time shapes (the encoder by N and m, the window gather by m and k), and a flag that only remembered "opted in" let a
+// later, larger launch go out above the attribute.  The size actually requested is recorded, not the 160 KiB cap once, so that the
+// attribute never promises more than some launch of this process has asked for.  Raising it is rare and goes under one lock, so
+// that two racing requests cannot leave a record above the attribute; the common path (already large enough) is one atomic load.
+// Devices 63 and above share the last entry and therefore set the attribute on every call.
 struct LdsOptIn {
-    std::atomic<bool> done[64];
+    std::atomic<size_t> bytes[64];
 };
 inline int ensure_dyn_lds(LdsOptIn& slot, const void* kern, size_t lds) {
     if (lds <= 64 * 1024) return 0;
@@ -43,11 +49,15 @@ inline int ensure_dyn_lds(LdsOptIn& slot, const void* kern, size_t lds) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return (int)e;
-    dev = (dev < 0 || dev >= 64) ? 63 : dev;
-    if (slot.done[dev].load(std::memory_order_acquire)) return 0;
+    const bool shared = dev < 0 || dev >= 63;
+    dev = shared ? 63 : dev;
+    if (!shared && lds <= slot.bytes[dev].load(std::memory_order_acquire)) return 0;
+    static std::mutex raise_lock;
+    std::lock_guard<std::mutex> hold(raise_lock);
+    if (!shared && lds <= slot.bytes[dev].load(std::memory_order_acquire)) return 0;
     e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    slot.done[dev].store(true, std::memory_order_release);
+    slot.bytes[dev].store(lds, std::memory_order_release);
     return 0;
 }
 

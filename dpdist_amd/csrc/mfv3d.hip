@@ -1114,10 +1114,13 @@ static size_t bwd_lds_bytes(int N, int m) {
     return (size_t)(6 * N * m + 3 * N + 16 * 2 * kF + 2 * kF + N + 16 * N * 3 + 4) * sizeof(float);
 }
 
-template <typename K>
-static int set_lds(K kern, size_t lds) {
-    static LdsOptIn lds_opt;   // one per kernel (template on the kernel's type)
-    return ensure_dyn_lds(lds_opt, (const void*)kern, lds);
+// One record per KERNEL: the template parameter is the kernel itself, not its type -- the two forward kernels have the same
+// signature (as have the two instantiations of the apply kernel), and a record keyed on the type let the first of them to pass
+// 64 KiB answer for the other, which then launched without ever having been opted in.
+template <auto Kern>
+static int set_lds(size_t lds) {
+    static LdsOptIn lds_opt;
+    return ensure_dyn_lds(lds_opt, (const void*)Kern, lds);
 }
 
 }  // namespace dpd
@@ -1137,10 +1140,10 @@ extern "C" int dpd_mfv3d_fwd(const float* pts, int C, int N, int m, float sigma,
     const size_t lds = fwd_lds_bytes(N, m, gslice);
     StageProf prof(stream, DPD_STAGE_ENCODER, (double)C * (N * 12.0 + k.G * 80.0));      // points in, [G,20] Fisher vector out
     if (use_fwd2(N)) {
-        if (int rc = set_lds(mfv3d_fwd2_kernel, lds)) return rc;
+        if (int rc = set_lds<mfv3d_fwd2_kernel>(lds)) return rc;
         DPD_LAUNCH(mfv3d_fwd2_kernel, dim3(C * kSlices), dim3(kFwd2Threads), lds, (hipStream_t)stream, pts, fv, k, gslice, MfvFuse{});
     } else {
-        if (int rc = set_lds(mfv3d_fwd_kernel, lds)) return rc;
+        if (int rc = set_lds<mfv3d_fwd_kernel>(lds)) return rc;
         DPD_LAUNCH(mfv3d_fwd_kernel, dim3(C * kSlices), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, fv, k, gslice, MfvFuse{});
     }
     DPD_CHECK_LAUNCH();
@@ -1161,11 +1164,11 @@ extern "C" int dpd_mfv3d_fwd_stacked(const float* pcA, const float* pcB, const f
     // points (+ noise) in; stacked pts / q and the [G,20] Fisher vector (+ per-slice sums of squares) out
     StageProf prof(stream, DPD_STAGE_ENCODER, (double)C * (N * 12.0 * (noise ? 1.5 : 1.0) + N * 24.0 + k.G * 80.0 + (ssq ? kSlices * 80.0 : 0.0)));
     if (use_fwd2(N)) {
-        if (int rc = set_lds(mfv3d_fwd2_kernel, lds)) return rc;
+        if (int rc = set_lds<mfv3d_fwd2_kernel>(lds)) return rc;
         DPD_LAUNCH(mfv3d_fwd2_kernel, dim3(C * kSlices), dim3(kFwd2Threads), lds, (hipStream_t)stream, (const float*)nullptr, fv, k, gslice,
                    MfvFuse{pcA, pcB, noise, pts, q, ssq, B});
     } else {
-        if (int rc = set_lds(mfv3d_fwd_kernel, lds)) return rc;
+        if (int rc = set_lds<mfv3d_fwd_kernel>(lds)) return rc;
         DPD_LAUNCH(mfv3d_fwd_kernel, dim3(C * kSlices), dim3(kFwdThreads), lds, (hipStream_t)stream, (const float*)nullptr, fv, k, gslice,
                    MfvFuse{pcA, pcB, noise, pts, q, ssq, B});
     }
@@ -1193,8 +1196,8 @@ extern "C" int dpd_mfv3d_bwd(const float* pts, const float* dfv, int C, int N, i
         // sliced over the points: kSlices workgroups per cloud, per-Gaussian statistic records exchanged through `ws`
         const int nslice = (N + kSlices - 1) / kSlices;
         const size_t l1 = (size_t)(6 * nslice * m + 3 * nslice + 4) * sizeof(float), l2 = bwd_sliced_lds_bytes(nslice, m);
-        if (int rc = set_lds(mfv3d_bwd_stats_kernel, l1)) return rc;
-        if (int rc = set_lds(mfv3d_bwd_apply_kernel<false>, l2)) return rc;
+        if (int rc = set_lds<mfv3d_bwd_stats_kernel>(l1)) return rc;
+        if (int rc = set_lds<mfv3d_bwd_apply_kernel<false>>(l2)) return rc;
         DPD_LAUNCH(mfv3d_bwd_stats_kernel, dim3(C * kSlices), dim3(kFwdThreads), l1, (hipStream_t)stream, pts, (float*)ws, k, nslice);
         DPD_CHECK_LAUNCH();
         DPD_LAUNCH(mfv3d_bwd_combine_kernel, dim3(C * 4), dim3(512), 0, (hipStream_t)stream, dfv, (float*)ws, k);
@@ -1205,7 +1208,7 @@ extern "C" int dpd_mfv3d_bwd(const float* pts, const float* dfv, int C, int N, i
         return 0;
     }
     const size_t lds = bwd_lds_bytes(N, m);
-    if (int rc = set_lds(mfv3d_bwd_kernel, lds)) return rc;
+    if (int rc = set_lds<mfv3d_bwd_kernel>(lds)) return rc;
     DPD_LAUNCH(mfv3d_bwd_kernel, dim3(C), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, dfv, dpts, k);
     DPD_CHECK_LAUNCH();
     return 0;
@@ -1229,9 +1232,8 @@ extern "C" int dpd_asloss_tail(const float* dX, const int32_t* vox, const float*
     const int nslice = (N + kSlices - 1) / kSlices;
     const int gslices = (kc.G * 5 + kFwdThreads - 1) / kFwdThreads;      // one (voxel, channel group) item per thread
     const size_t l1 = (size_t)(6 * nslice * m + 3 * nslice + 4) * sizeof(float), lg = (size_t)N * sizeof(int), l2 = bwd_sliced_lds_bytes(nslice, m);
-    if (int rc = set_lds(asloss_tail_a_kernel, l1 > lg ? l1 : lg)) return rc;
-    static LdsOptIn opt_final;      // (set_lds keys its flag on the kernel's TYPE, which the two instantiations of the apply kernel share)
-    if (int rc = ensure_dyn_lds(opt_final, (const void*)mfv3d_bwd_apply_kernel<true>, l2)) return rc;
+    if (int rc = set_lds<asloss_tail_a_kernel>(l1 > lg ? l1 : lg)) return rc;
+    if (int rc = set_lds<mfv3d_bwd_apply_kernel<true>>(l2)) return rc;
     hipStream_t s = (hipStream_t)stream;
     DPD_LAUNCH(asloss_tail_a_kernel, dim3(C * gslices + C * kSlices), dim3(kFwdThreads), l1 > lg ? l1 : lg, s, dX, vox, dfv, pts, (float*)mfv_ws, kc,
                nslice, k, KP, gslices, C * gslices);

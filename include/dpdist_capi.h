@@ -61,7 +61,13 @@ int dpd_stack_clouds(const float* pcA, const float* pcB, const float* noise, int
  * 3DmFV encoder.  Replaces utils/dpdist_util.py:22-141 (get_3dmfv_tf, full_fv, normalize=True).
  *   pts [C,N,3] -> fv [C,m^3,20]; Gaussians on the fixed grid of :42-51, uniform weights 1/m^3.
  *   A point further than ~1.7 from every centre underflows every pdf and yields NaN exactly as the
- *   reference does (0/0 at :74).                                                                  */
+ *   reference does (0/0 at :74).
+ *   Sizes: 1 <= m <= 10 and 1 <= N <= 4096, else DPD_E_UNSUPPORTED; sigma > 0 (not NaN) and C >= 1, else DPD_E_DIM.  The
+ *   limit on N that binds is the kernel's dynamic LDS, which must fit 160 KiB:
+ *       4 * (6*N*m + 6*N + 21*ceil(m^3 / 4) + 164) bytes <= 163840
+ *   i.e. N <= 705 for m = 8 (704 for the N % 8 == 0 kernel), N <= 538 for m = 10 (536), N <= 3397 even for m = 1; beyond it
+ *   DPD_E_UNSUPPORTED, before anything is launched and with fv untouched.  N % 8 == 0 (N >= 8) runs the kernel that takes the
+ *   points in pairs, every other N the eight-point-group kernel; both are held to the same bar against the float64 oracle.  */
 int dpd_mfv3d_fwd(const float* pts, int C, int N, int m, float sigma, float* fv, void* stream);
 
 /* Backward of the encoder (TF autodiff of :69-126): dfv [C,m^3,20] -> dpts [C,N,3] (overwritten).
@@ -69,7 +75,14 @@ int dpd_mfv3d_fwd(const float* pts, int C, int N, int m, float sigma, float* fv,
 int dpd_mfv3d_bwd(const float* pts, const float* dfv, int C, int N, int m, float sigma, float* dpts, void* ws,
                   size_t ws_bytes, void* stream);
 /* ws (optional): dpd_mfv3d_bwd_workspace_bytes(C, m) bytes let the backward run as 4 workgroups per cloud (sliced over
- * the points, two launches) instead of one -- 2-3x faster at the as-loss batch sizes; NULL keeps the one-launch form. */
+ * the points, three launches) instead of one -- 2-3x faster at the as-loss batch sizes; NULL keeps the one-launch form.
+ * Sizes: as the forward, and m <= 8 (one Gaussian per lane pair; m = 9, 10: DPD_E_UNSUPPORTED).  Dynamic LDS, 160 KiB at most:
+ *   one launch:  4 * (6*N*m + 52*N + 684) bytes                       (m = 8: N <= 402)
+ *   sliced:      4 * (6*n*m + 52*n + 4) bytes with n = ceil(N / 4)    (m = 8: n <= 409, N <= 1636)
+ * beyond it DPD_E_UNSUPPORTED with dpts and ws untouched.  The sliced form needs N >= 8; for N < 8 the entry runs the one-launch
+ * kernel even when ws is given (ws is then not written).  Slice s holds the points [s*n, min(N, (s+1)*n)): the last slices may
+ * be EMPTY (N = 9: 3, 3, 3, 0 -- its record carries -inf / +inf extrema and zero tie counts, which the merge ignores) or hold ONE
+ * point (N = 10, 13).  The tie count of a max / min is taken over the whole cloud, across the slices.                        */
 size_t dpd_mfv3d_bwd_workspace_bytes(int C, int m);
 
 /* ---------------------------------------------------------------------------------------------
