@@ -34,7 +34,7 @@ __device__ __attribute__((aligned(16))) const unsigned g_zero_chunk[4] = {0u, 0u
 
 // NP planes (1: BK = 64, two k16 steps per phase; 3: BK = 32, one k16 step = six MFMA terms per phase): a K-tile is 48 KiB of LDS for
 // a 256x128 (NP = 1) or 128x128 (NP = 3) tile either way.
-// One output tile of the phase-staggered schedule: prologue, K loop, epilogue (gemm_p8_kernel runs one tile per workgroup).
+// One output tile of the phase-staggered schedule: prologue, K loop, epilogue -- the whole work of a gemm_p8_kernel workgroup.
 // LATE_WAIT: group 0 waits for its DMA pieces after its MFMA cluster instead of before it (tiles 21 and 24: yes, tile 23: no).
 template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, bool LATE_WAIT>
 __device__ __forceinline__ void p8_tile(const X3Args& g, char* smem_x3, int grp, const uint16_t* gA, const uint16_t* gB, int m0, int n0, int tid) {
@@ -234,9 +234,6 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_p8_kernel(X3Args g) {
     p8_tile<NP, AK, BKC, WR, WC, TM, TN, LATE_WAIT>(g, smem_x3, grp, grp ? g.A2 : g.A, grp ? g.B2 : g.B, (t0 / tilesN) * BM, (t0 % tilesN) * BN,
                                                     threadIdx.x);
 }
-
-// (Round 5 built a persistent chained launch on p8_tile -- layers 1 -> 2 -> 3 / g3 -> g2 -> g1 as one launch; bitwise the separate
-// launches, 11 us slower per chain at B = 64 (profiles/r05_chain_bench.txt); removed in round 6, DESIGN.md section 3.6 keeps the finding.)
 
 template <int NP, bool AK, bool BKC, int WR, int WC, int TM, int TN, bool LATE_WAIT>
 static int launch_p8(const X3Args& g, hipStream_t s) {

@@ -12,11 +12,15 @@ Restates (relative to /root/reference/pcrnet-registration):
     iterative_PCRNet_ours.py:410-470   MAX_LOOPS-1 = 7 forward-only pose refinements, then one training step
     results_itrPCRNet_no_stop.py:112-133   find_errors: translation L2 error, rotation angle of R_pred R_gt^-1
 """
+import ctypes
 import math
+from ctypes import byref
 
 import numpy as np
 import torch
 from torch import nn
+
+from . import lib as L      # the ctypes declarations only: the shared library itself is loaded by L.load() at the first call that needs it
 
 
 def quat_to_mat(q):
@@ -43,6 +47,71 @@ def quat_normalize(pred, rot_lim=45.0):
 
 
 NATIVE_TRAIN_MAX_POINTS = 2048      # dpd_pose_point_fwd_train / _bwd (include/dpdist_capi.h); the reference's MAX_NUM_POINT
+# (in, out) of the Linear layers of THE pose network csrc/pose.hip implements (models/ipcr_model.py:198-233,273-284 as PoseNet builds it)
+POINT_WIDTHS = [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
+HEAD_WIDTHS = [(2048, 1024), (1024, 512), (512, 256), (256, 7)]
+
+
+def _linears(seq):
+    return [m for m in seq if isinstance(m, nn.Linear)]
+
+
+def _weights(*seqs):
+    """(weight, bias, weight, bias, ...) of the Linear layers: the order `_pose_net_struct` and the autograd nodes below take them in."""
+    return [t for seq in seqs for m in _linears(seq) for t in (m.weight, m.bias)]
+
+
+def _has_widths(seq, widths):
+    lin = _linears(seq)
+    return [(m.in_features, m.out_features) for m in lin] == widths and all(m.bias is not None for m in lin)
+
+
+def native_point_supported(net):
+    """Whether `net`'s shared MLP is the one csrc/pose.hip implements (3-64-64-64-128-1024, with biases): all `PoseNet._pooled` needs."""
+    return isinstance(net, PoseNet) and _has_widths(net.point, POINT_WIDTHS)
+
+
+def native_refine_supported(net):
+    """Whether `net` is the architecture csrc/pose.hip implements: that shared MLP and the head 2048-1024-512-256-7, all with biases."""
+    return native_point_supported(net) and _has_widths(net.head, HEAD_WIDTHS)
+
+
+def _pose_net_struct(wb):
+    """include/dpdist_capi.h's dpd_pose_net over `_weights(net.point)` (the point entries read no more) or `_weights(net.point, net.head)`."""
+    w = L.PoseNetW()
+    for i, (W, b) in enumerate(zip(wb[0::2], wb[1::2])):
+        W, b = L.req(W, name="weight").data_ptr(), L.req(b, name="bias").data_ptr()
+        if i < 5:
+            w.Wp[i], w.bp[i] = W, b
+        else:
+            w.Wh[i - 5], w.bh[i - 5] = W, b
+    w.out_features = wb[8].shape[0]
+    return w
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _point_forward(w, ptsA, ptsB, nA, nB, N):
+    """dpd_pose_point_fwd_train on the nA clouds of ptsA, then the nB of ptsB (None, 0: one array): (pooled features, hidden activations, tie masks)."""
+    C, dev, lib = nA + nB, ptsA.device, L.load()
+    f = torch.empty(C, w.out_features, device=dev, dtype=torch.float32)
+    h = [torch.empty(C * N, k, device=dev, dtype=torch.float32) for _, k in POINT_WIDTHS[:4]]
+    ties = torch.empty(C, lib.dpd_pose_point_tie_words(N), w.out_features, device=dev, dtype=torch.int64)
+    L.check(lib.dpd_pose_point_fwd_train(byref(w), L.ptr(ptsA), L.ptr(ptsB), nA, nB, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
+                                         ties.data_ptr(), L.cur_stream()), "dpd_pose_point_fwd_train")
+    return f, h, ties
+
+
+def _point_backward(w, ptsA, ptsB, nA, nB, N, df, h, ties, grads):
+    """dpd_pose_point_bwd: from `df` = d loss / d pooled features, the shared MLP's ten weight gradients WRITTEN into `grads` (dW1, db1, .. dW5, db5)."""
+    lib = L.load()
+    nbytes = lib.dpd_pose_point_bwd_workspace_bytes_n(nA + nB, N)
+    ws = torch.empty(nbytes // 4, device=ptsA.device, dtype=torch.float32)
+    L.check(lib.dpd_pose_point_bwd(byref(w), L.ptr(ptsA), L.ptr(ptsB), nA, nB, N, L.ptr(df), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
+                                   ties.data_ptr(), _ptr_array(grads[0::2]), _ptr_array(grads[1::2]), L.ptr(ws), nbytes, L.cur_stream()),
+            "dpd_pose_point_bwd")
 
 
 class _PointFeaturesFn(torch.autograd.Function):
@@ -54,45 +123,19 @@ class _PointFeaturesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, clouds, *wb):
-        from ctypes import byref
-        from . import lib as L
         C, N, _ = clouds.shape
         L.req(clouds, name="clouds", shape=(C, N, 3))
-        w = L.PoseNetW()
-        for i in range(5):
-            w.Wp[i], w.bp[i] = L.req(wb[2 * i], name="weight").data_ptr(), L.req(wb[2 * i + 1], name="bias").data_ptr()
-        w.out_features = wb[8].shape[0]
-        dev = clouds.device
-        f = torch.empty(C, w.out_features, device=dev, dtype=torch.float32)
-        h = [torch.empty(C * N, k, device=dev, dtype=torch.float32) for k in (64, 64, 64, 128)]
-        lib = L.load()
-        ties = torch.empty(C, lib.dpd_pose_point_tie_words(N), w.out_features, device=dev, dtype=torch.int64)
-        L.check(lib.dpd_pose_point_fwd_train(byref(w), L.ptr(clouds), None, C, 0, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
-                                             ties.data_ptr(), L.cur_stream()), "dpd_pose_point_fwd_train")
+        f, h, ties = _point_forward(_pose_net_struct(wb), clouds, None, C, 0, N)
         ctx.save_for_backward(clouds, ties, *h, *wb)
         return f
 
     @staticmethod
     def backward(ctx, df):
-        import ctypes
-        from ctypes import byref
-        from . import lib as L
-        clouds, ties, h1, h2, h3, h4 = ctx.saved_tensors[:6]
-        wb = ctx.saved_tensors[6:]
+        sv = ctx.saved_tensors
+        clouds, ties, h, wb = sv[0], sv[1], sv[2:6], sv[6:]
         C, N, _ = clouds.shape
-        w = L.PoseNetW()
-        for i in range(5):
-            w.Wp[i], w.bp[i] = wb[2 * i].data_ptr(), wb[2 * i + 1].data_ptr()
-        w.out_features = wb[8].shape[0]
-        df = df.contiguous()
         grads = [torch.empty_like(t) for t in wb]
-        dW = (ctypes.c_void_p * 5)(*[grads[2 * i].data_ptr() for i in range(5)])
-        db = (ctypes.c_void_p * 5)(*[grads[2 * i + 1].data_ptr() for i in range(5)])
-        lib = L.load()
-        nbytes = lib.dpd_pose_point_bwd_workspace_bytes_n(C, N)
-        ws = torch.empty(nbytes // 4, device=clouds.device, dtype=torch.float32)
-        L.check(lib.dpd_pose_point_bwd(byref(w), L.ptr(clouds), None, C, 0, N, L.ptr(df), L.ptr(h1), L.ptr(h2), L.ptr(h3), L.ptr(h4), ties.data_ptr(),
-                                       dW, db, L.ptr(ws), nbytes, L.cur_stream()), "dpd_pose_point_bwd")
+        _point_backward(_pose_net_struct(wb), clouds, None, C, 0, N, df.contiguous(), h, ties, grads)
         return (None,) + tuple(grads)
 
 
@@ -105,28 +148,14 @@ class _PoseNetRawFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, source, template, mask, sink, *wb):
-        from ctypes import byref
-        from . import lib as L
         B, N, _ = source.shape
-        C = 2 * B
         L.req(source, name="source", shape=(B, N, 3)), L.req(template, name="template", shape=(B, N, 3))
         if mask is not None:
             L.req(mask, name="mask", shape=(B, 256))
-        w = L.PoseNetW()
-        for i in range(5):
-            w.Wp[i], w.bp[i] = L.req(wb[2 * i], name="weight").data_ptr(), L.req(wb[2 * i + 1], name="bias").data_ptr()
-        for i in range(4):
-            w.Wh[i], w.bh[i] = L.req(wb[10 + 2 * i], name="weight").data_ptr(), L.req(wb[11 + 2 * i], name="bias").data_ptr()
-        w.out_features = wb[8].shape[0]
-        dev, lib, st = source.device, L.load(), L.cur_stream()
-        e = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)      # noqa: E731
-        f = e(C, w.out_features)
-        h = [e(C * N, k) for k in (64, 64, 64, 128)]
-        ties = torch.empty(C, lib.dpd_pose_point_tie_words(N), w.out_features, device=dev, dtype=torch.int64)
-        L.check(lib.dpd_pose_point_fwd_train(byref(w), L.ptr(source), L.ptr(template), B, B, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]),
-                                             L.ptr(h[3]), ties.data_ptr(), st), "dpd_pose_point_fwd_train")
-        a1, a2, a3, pred = e(B, 1024), e(B, 512), e(B, 256), e(B, 7)
-        L.check(lib.dpd_pose_head_fwd_train(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(pred), st),
+        w = _pose_net_struct(wb)
+        f, h, ties = _point_forward(w, source, template, B, B, N)
+        a1, a2, a3, pred = [torch.empty(B, k, device=source.device, dtype=torch.float32) for k in (1024, 512, 256, 7)]
+        L.check(L.load().dpd_pose_head_fwd_train(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(pred), L.cur_stream()),
                 "dpd_pose_head_fwd_train")
         ctx.has_mask = mask is not None
         ctx.sink = sink
@@ -135,45 +164,42 @@ class _PoseNetRawFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpred):
-        import ctypes
-        from ctypes import byref
-        from . import lib as L
         sv = ctx.saved_tensors
-        source, template, ties, f, a1, a2, a3, h1, h2, h3, h4 = sv[:11]
-        wb = sv[11:29]
+        source, template, ties, f, a1, a2, a3 = sv[:7]
+        h, wb = sv[7:11], sv[11:29]
         mask = sv[29] if ctx.has_mask else None
         B, N, _ = source.shape
-        C = 2 * B
-        w = L.PoseNetW()
-        for i in range(5):
-            w.Wp[i], w.bp[i] = wb[2 * i].data_ptr(), wb[2 * i + 1].data_ptr()
-        for i in range(4):
-            w.Wh[i], w.bh[i] = wb[10 + 2 * i].data_ptr(), wb[11 + 2 * i].data_ptr()
-        w.out_features = wb[8].shape[0]
-        dev, lib, st = source.device, L.load(), L.cur_stream()
+        w = _pose_net_struct(wb)
         dpred = dpred.contiguous()
         sink = ctx.sink or {}
         grads = [sink.get(id(t)) for t in wb]
         grads = [g if (g is not None and g.shape == t.shape and g.is_contiguous() and g.data_ptr() % 16 == 0) else torch.empty_like(t)
                  for g, t in zip(grads, wb)]
-        vp = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])      # noqa: E731
         df = torch.empty_like(f)
+        lib = L.load()
         nb = lib.dpd_pose_head_bwd_workspace_bytes(B)
-        ws = torch.empty(nb // 4, device=dev, dtype=torch.float32)
-        L.check(lib.dpd_pose_head_bwd(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(dpred), vp(grads[10::2]), vp(grads[11::2]),
-                                      L.ptr(df), L.ptr(ws), nb, st), "dpd_pose_head_bwd")
-        nb2 = lib.dpd_pose_point_bwd_workspace_bytes_n(C, N)
-        ws2 = torch.empty(nb2 // 4, device=dev, dtype=torch.float32)
-        L.check(lib.dpd_pose_point_bwd(byref(w), L.ptr(source), L.ptr(template), B, B, N, L.ptr(df), L.ptr(h1), L.ptr(h2), L.ptr(h3), L.ptr(h4),
-                                       ties.data_ptr(), vp(grads[0:10:2]), vp(grads[1:10:2]), L.ptr(ws2), nb2, st), "dpd_pose_point_bwd")
+        ws = torch.empty(nb // 4, device=source.device, dtype=torch.float32)
+        L.check(lib.dpd_pose_head_bwd(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(dpred), _ptr_array(grads[10::2]),
+                                      _ptr_array(grads[11::2]), L.ptr(df), L.ptr(ws), nb, L.cur_stream()), "dpd_pose_head_bwd")
+        _point_backward(w, source, template, B, B, N, df, h, ties, grads[:10])
         return (None, None, None, None) + tuple(grads)
+
+
+def _dropout_masks(net, count, B, device):
+    """`count` masks of the head's dropout (keep with probability 1 - p, scale by 1 / (1 - p)) as ONE draw [count, B, 256]; None where it drops nothing."""
+    drop = next((m for m in net.head if isinstance(m, nn.Dropout)), None)
+    if not net.training or drop is None or drop.p <= 0:
+        return None
+    keep = 1.0 - drop.p
+    return torch.empty(count, B, 256, device=device).bernoulli_(keep).div_(keep)
 
 
 class PoseNet(nn.Module):
     """models/ipcr_model.py:198-233 + :273-284 (1xW convs == per-point linear layers)."""
-    next_mask = None         # a dropout mask [B,256] already drawn for the next training evaluation of `raw` (consumed by it)
-    grad_sink = None         # set by IterativeRegistration for the span of one training evaluation (see _PoseNetRawFn)
-    native_train = True      # the training evaluation's shared MLP + max pool on the library (_PointFeaturesFn) when the shape allows it
+    # The hand-off from IterativeRegistration to `raw` for a training evaluation on the library (both None outside one):
+    next_mask = None         # its dropout mask [B,256], drawn by `refine` in one draw with the refinements' masks; the next `raw` consumes it
+    grad_sink = None         # {id(parameter): where _PoseNetRawFn's backward writes that gradient}, for the span of one `_evaluate_grad`
+    native_train = True      # the training evaluation on the library (_PoseNetRawFn / _PointFeaturesFn) when the network and the inputs allow it
 
     def __init__(self, out_features=1024, lim_rot=45.0, keep_prob=0.7):
         super().__init__()
@@ -197,23 +223,28 @@ class PoseNet(nn.Module):
     def load_tf_state_dict(self, sd):
         """TF variables of ipcr_model.pointnet / get_pose: conv{1..5}/{weights [1,kw,cin,cout], biases}, fc{1..4}/{weights
         [in,out], biases} -> the Linear layers (a 1xW VALID conv on [B,N,W,1] / [B,N,1,C] is a per-point linear map)."""
-        lin = [m for m in self.point if isinstance(m, nn.Linear)]
-        for i, l in enumerate(lin, 1):
+        for i, l in enumerate(_linears(self.point), 1):
             w = torch.as_tensor(np.asarray(sd["conv%d/weights" % i]), dtype=torch.float32)
             l.weight.copy_(w.reshape(-1, w.shape[-1]).t())
             l.bias.copy_(torch.as_tensor(np.asarray(sd["conv%d/biases" % i]), dtype=torch.float32))
-        lin = [m for m in self.head if isinstance(m, nn.Linear)]
-        for i, l in enumerate(lin, 1):
+        for i, l in enumerate(_linears(self.head), 1):
             l.weight.copy_(torch.as_tensor(np.asarray(sd["fc%d/weights" % i]), dtype=torch.float32).t())
             l.bias.copy_(torch.as_tensor(np.asarray(sd["fc%d/biases" % i]), dtype=torch.float32))
 
+    def _library_weights(self, clouds, head):
+        """The weights for the library's training node over `clouds` [C,N,3] (the shared MLP's, then the head's when `head`), or None where the
+        evaluation stays in torch: the run-time conditions and the architecture check of `_pooled` and `raw`, stated once."""
+        if not (self.native_train and torch.is_grad_enabled() and clouds.is_cuda and clouds.dtype == torch.float32 and not clouds.requires_grad
+                and clouds.shape[1] <= NATIVE_TRAIN_MAX_POINTS and (native_refine_supported(self) if head else native_point_supported(self))):
+            return None
+        wb = _weights(self.point, self.head) if head else _weights(self.point)
+        return wb if any(t.requires_grad for t in wb) else None
+
     def _pooled(self, clouds):
         """shared MLP + max pool over the points of every cloud: [C, N, 3] -> [C, out_features]"""
-        lin = [m for m in self.point if isinstance(m, nn.Linear)]
-        if (self.native_train and torch.is_grad_enabled() and clouds.is_cuda and clouds.dtype == torch.float32 and not clouds.requires_grad
-                and clouds.shape[1] <= NATIVE_TRAIN_MAX_POINTS and [(m.in_features, m.out_features) for m in lin] == [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
-                and any(p.requires_grad for m in lin for p in (m.weight, m.bias))):
-            return _PointFeaturesFn.apply(clouds.contiguous(), *[t for m in lin for t in (m.weight, m.bias)])
+        wb = self._library_weights(clouds, head=False)
+        if wb is not None:
+            return _PointFeaturesFn.apply(clouds.contiguous(), *wb)
         return self.point(clouds).amax(1)
 
     def features(self, source, template):
@@ -222,34 +253,19 @@ class PoseNet(nn.Module):
         B = source.shape[0]
         return f[:B], f[B:]
 
-    def _native_raw_ok(self, clouds):
-        lin_p = [m for m in self.point if isinstance(m, nn.Linear)]
-        lin_h = [m for m in self.head if isinstance(m, nn.Linear)]
-        return (self.native_train and torch.is_grad_enabled() and clouds.is_cuda and clouds.dtype == torch.float32 and not clouds.requires_grad
-                and clouds.shape[1] <= NATIVE_TRAIN_MAX_POINTS and [(m.in_features, m.out_features) for m in lin_p] == [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
-                and [(m.in_features, m.out_features) for m in lin_h] == [(2048, 1024), (1024, 512), (512, 256), (256, 7)]
-                and any(p.requires_grad for p in self.parameters()))
-
     def raw(self, source, template):
         """get_pose's fc4 output (:273-284) BEFORE quat_normalize: [B,7] = (t, angle, axis)."""
-        if self._native_raw_ok(source) and template.shape == source.shape and template.dtype == source.dtype and not template.requires_grad:
-            # the training evaluation on the library (one autograd node): the dropout mask is drawn here (torch's Philox stream, as the
-            # refinements' masks are), everything else is csrc/pose.hip
-            mask = None
-            drop = next((m for m in self.head if isinstance(m, nn.Dropout)), None)
-            given, self.next_mask = self.next_mask, None
-            if self.training and drop is not None and drop.p > 0:
-                keep = 1.0 - drop.p
-                if given is not None and given.shape == (source.shape[0], 256) and given.device == source.device:
-                    mask = given                                   # drawn with the refinements' masks (IterativeRegistration.refine)
-                else:
-                    mask = torch.empty(source.shape[0], 256, device=source.device).bernoulli_(keep).div_(keep)
-            lin = [m for m in self.point if isinstance(m, nn.Linear)] + [m for m in self.head if isinstance(m, nn.Linear)]
-            return _PoseNetRawFn.apply(source.contiguous(), template.contiguous(), mask, getattr(self, "grad_sink", None),
-                                       *[t for m in lin for t in (m.weight, m.bias)])
-        f = self._pooled(torch.cat([source, template], 0))                  # max pool over the points
         B = source.shape[0]
-        return self.head(torch.cat([f[:B], f[B:]], 1))
+        wb = self._library_weights(source, head=True)
+        if wb is not None and template.shape == source.shape and template.dtype == source.dtype and not template.requires_grad:
+            # the training evaluation on the library (one autograd node): the dropout mask is the one `refine` drew with the refinements'
+            # masks, or drawn here (torch's Philox stream either way); everything else is csrc/pose.hip
+            mask, self.next_mask = self.next_mask, None
+            if mask is None or not self.training or mask.shape != (B, 256) or mask.device != source.device:
+                mask = _dropout_masks(self, 1, B, source.device)
+                mask = None if mask is None else mask[0]
+            return _PoseNetRawFn.apply(source.contiguous(), template.contiguous(), mask, self.grad_sink, *wb)
+        return self.head(torch.cat(self.features(source, template), 1))
 
     def forward(self, source, template):
         pred = self.raw(source, template)
@@ -339,6 +355,11 @@ def pose_errors(T_pred, R_gt, t_gt):
     return (T_pred[:, :3, 3] - t_id).norm(dim=-1), torch.rad2deg(torch.acos(cos))
 
 
+def unit_quat_pose(pose):
+    """(t, q) -> (t, q / |q|): helper.transformation_quat2mat (helper.py:309-329) normalises the quaternion (transforms3d.quat2mat)."""
+    return torch.cat([pose[:, :3], pose[:, 3:7] / pose[:, 3:7].norm(dim=1, keepdim=True).clamp_min(1e-12)], 1)
+
+
 def predicted_pose_applied(source, pose):
     """iterative_PCRNet_ours.py:211-224: split the 7-vector, re-normalise the quaternion (norm + 1e-7) and move the source."""
     quat = pose[:, 3:7]
@@ -372,7 +393,6 @@ class _PoseApplyFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, source, T, lim_rot, mode):
-        from . import lib as L
         B, N, _ = source.shape
         L.req(pred, name="pred", shape=(B, 7)), L.req(source, name="source", shape=(B, N, 3))
         pose, moved = torch.empty_like(pred), torch.empty_like(source)
@@ -393,7 +413,6 @@ class _PoseApplyFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        from . import lib as L
         if ctx.mode != 1:
             raise RuntimeError("pose_apply: only the training evaluation (mode 1) is differentiable; the refinements are forward-only")
         pred, source = ctx.saved_tensors
@@ -413,37 +432,13 @@ def pose_apply(pred, source, T=None, lim_rot=45.0, mode=0):
     return _PoseApplyFn.apply(pred.contiguous(), source.contiguous(), None if T is None else T.contiguous(), lim_rot, mode)
 
 
-def native_refine_supported(net):
-    """Whether `net` is the architecture csrc/pose.hip's forward implements (models/ipcr_model.py:198-233,273-284 as PoseNet builds it)."""
-    if not isinstance(net, PoseNet):
-        return False
-    lin_p = [m for m in net.point if isinstance(m, nn.Linear)]
-    lin_h = [m for m in net.head if isinstance(m, nn.Linear)]
-    if len(lin_p) != 5 or len(lin_h) != 4:
-        return False
-    out = lin_p[4].out_features
-    want_p = [(3, 64), (64, 64), (64, 64), (64, 128), (128, out)]
-    want_h = [(2 * out, 1024), (1024, 512), (512, 256), (256, 7)]
-    return (out == 1024 and [(m.in_features, m.out_features) for m in lin_p] == want_p
-            and [(m.in_features, m.out_features) for m in lin_h] == want_h and all(m.bias is not None for m in lin_p + lin_h))
-
-
 def pose_refine_native(net, source, template, loops, drop_mask=None, want_pred=False):
     """`loops` forward-only refinements (iterative_PCRNet_ours.py:414-441) with the pose network, quat_normalize, the cloud move and the T
     composition all on the library (include/dpdist_capi.h: dpd_pose_refine, four launches per loop + one per call): (moved source, T[, raw outputs
     [loops,B,7]]).  drop_mask [loops,B,256] (0 or 1/keep) or None; the caller draws it (IterativeRegistration.refine does, in train mode)."""
-    from ctypes import byref
-    from . import lib as L
     B, N, _ = source.shape
     L.req(source, name="source", shape=(B, N, 3)), L.req(template, name="template", shape=(B, N, 3))
-    lin_p = [m for m in net.point if isinstance(m, nn.Linear)]
-    lin_h = [m for m in net.head if isinstance(m, nn.Linear)]
-    w = L.PoseNetW()
-    for i, m in enumerate(lin_p):
-        w.Wp[i], w.bp[i] = L.req(m.weight, name="weight").data_ptr(), L.req(m.bias, name="bias").data_ptr()
-    for i, m in enumerate(lin_h):
-        w.Wh[i], w.bh[i] = L.req(m.weight, name="weight").data_ptr(), L.req(m.bias, name="bias").data_ptr()
-    w.out_features = lin_p[4].out_features
+    w = _pose_net_struct(_weights(net.point, net.head))
     lib = L.load()
     nbytes = lib.dpd_pose_refine_workspace_bytes(B, N, w.out_features)
     ws = torch.empty(nbytes // 4, device=source.device, dtype=torch.float32)
@@ -456,16 +451,23 @@ def pose_refine_native(net, source, template, loops, drop_mask=None, want_pred=F
     return (moved, T, pred) if want_pred else (moved, T)
 
 
-def flat_gradient_views(params):
-    """One flat fp32 buffer with every parameter's `.grad` as a view into it (what `optim.TFAdam` does for its own parameters): the
-    data-parallel step all-reduces that ONE buffer instead of a tensor per layer."""
-    params = [p for p in params if p.requires_grad]
-    n = sum(p.numel() for p in params)
-    flat = torch.zeros((n + 3) // 4 * 4, device=params[0].device, dtype=params[0].dtype)
+def _flat_offsets(params):
+    """(parameter, first element of its gradient) in a flat gradient buffer: the parameters back to back in order, as `optim.TFAdam` lays them out."""
     off = 0
     for p in params:
-        p.grad = flat[off:off + p.numel()].view_as(p)
+        yield p, off
         off += p.numel()
+
+
+def flat_gradient_views(params, flat=None):
+    """One flat fp32 buffer (`flat`, or a new one) with every parameter's `.grad` as a view into it (what `optim.TFAdam` does for its own
+    parameters): the data-parallel step all-reduces that ONE buffer instead of a tensor per layer."""
+    params = [p for p in params if p.requires_grad]
+    if flat is None:
+        n = sum(p.numel() for p in params)
+        flat = torch.zeros((n + 3) // 4 * 4, device=params[0].device, dtype=params[0].dtype)
+    for p, off in _flat_offsets(params):
+        p.grad = flat[off:off + p.numel()].view_as(p)
     return flat
 
 
@@ -547,14 +549,9 @@ class IterativeRegistration:
         and of the training evaluation that follows are ONE draw of [loops + 1, B, 256]; the last one waits in `net.next_mask` for `raw`."""
         if self.native_refine and source.is_cuda and loops > 0 and source.dtype == torch.float32:
             with torch.no_grad():
-                mask = None
-                drop = next((m for m in self.net.head if isinstance(m, nn.Dropout)), None)
-                if self.net.training and drop is not None and drop.p > 0:      # torch's dropout: keep with probability 1 - p, scale by 1 / (1 - p)
-                    keep = 1.0 - drop.p
-                    extra = 1 if (train_mask and hasattr(self.net, "next_mask")) else 0
-                    mask = torch.empty(loops + extra, source.shape[0], 256, device=source.device).bernoulli_(keep).div_(keep)
-                    if extra:
-                        self.net.next_mask, mask = mask[loops], mask[:loops]
+                mask = _dropout_masks(self.net, loops + bool(train_mask), source.shape[0], source.device)
+                if mask is not None and train_mask:
+                    self.net.next_mask, mask = mask[loops], mask[:loops]
                 return pose_refine_native(self.net, source.contiguous(), template.contiguous(), loops, mask)
         T = torch.eye(4, device=source.device).repeat(source.shape[0], 1, 1)
         fused = self._fused(source)
@@ -563,9 +560,7 @@ class IterativeRegistration:
                 if fused:                # one launch: quat_normalize, normalisation, R, moved cloud, T <- M T (csrc/pose.hip)
                     _, source, T = pose_apply(self.net.raw(source, template), source, T, self.net.lim_rot, 0)
                     continue
-                pose = self.net(source, template)
-                # helper.transformation_quat2mat (helper.py:309-329) normalises the quaternion (transforms3d.quat2mat)
-                pose = torch.cat([pose[:, :3], pose[:, 3:7] / pose[:, 3:7].norm(dim=1, keepdim=True).clamp_min(1e-12)], 1)
+                pose = unit_quat_pose(self.net(source, template))
                 source = transformation_quat_tensor(source, pose[:, 3:7], pose[:, :3])
                 T = compose(T, pose)
         return source, T
@@ -574,65 +569,51 @@ class IterativeRegistration:
         if self._flat_grad is not None and not hasattr(self.opt, "grad"):
             self._flat_grad.zero_()                          # (a foreign optimizer's zero_grad may have dropped the views: rebind)
             if any(p.grad is None for p in self.net.parameters() if p.requires_grad):
-                off = 0
-                for p in (q for q in self.net.parameters() if q.requires_grad):
-                    p.grad = self._flat_grad[off:off + p.numel()].view_as(p)
-                    off += p.numel()
+                flat_gradient_views(self.net.parameters(), self._flat_grad)
 
     def _evaluate_grad(self, refined_source, template, T=None):
         """forward + backward of the training evaluation (:468 without the collective and the update): (loss, pose, T' or None);
         this rank's gradients are left in the parameters' `.grad`."""
-        Tn = None
         flat, params = getattr(self.opt, "grad", None), getattr(self.opt, "_params", None)
         in_place = (self.concat_grads and isinstance(flat, torch.Tensor) and params is not None
-                    and all(p.grad is not None and p.grad.data_ptr() == flat.data_ptr() + 4 * o for p, o in zip(params, self._offsets(params))))
-        if in_place and hasattr(self.net, "grad_sink"):
+                    and all(p.grad is not None and p.grad.data_ptr() == flat.data_ptr() + 4 * off for p, off in _flat_offsets(params)))
+        sink = in_place and hasattr(self.net, "grad_sink")
+        if sink:
             # for THIS evaluation only (the node keeps the mapping it was built with): its gradients are taken by torch.autograd.grad below,
             # never accumulated into the very views they were written to
             self.net.grad_sink = {id(p): p.grad for p in params}
         try:
-            return self._evaluate_grad_body(refined_source, template, T, flat, params, in_place)
+            Tn = None
+            if self._fused(refined_source):
+                pred = self.net.raw(refined_source, template)
+                out = pose_apply(pred, refined_source, T, self.net.lim_rot, 1)
+                pose, moved = out[0], out[1]
+                Tn = out[2] if T is not None else None
+            else:
+                pose = self.net(refined_source, template)
+                moved = predicted_pose_applied(refined_source, pose)
+                if T is not None:
+                    with torch.no_grad():
+                        Tn = compose(T, unit_quat_pose(pose))
+            loss = self.loss_fn(moved, template)                 # (mean(AB[...,0]) + mean(BA[...,0])) / 2, :248-251
+            if in_place:
+                # TFAdam's flat gradient: the 18 gradients are WRITTEN into it by one concatenation instead of being accumulated into 18 views
+                # of a zeroed buffer (19 in-place adds and a fill per step: 70 us of the captured step at batch 16).  0 + g == g: the same update
+                # The pose network's node writes them straight into the views (grad_sink): no copy at all; the concatenation is the fallback for
+                # whatever did not come back in place (torch pose network, a foreign graph).  The root gradient is a persistent one (no fill).
+                one = self._one if (self._one is not None and self._one.device == loss.device and loss.dim() == 0) else None
+                grads = torch.autograd.grad(loss, params, grad_outputs=one)
+                if not all(g.data_ptr() == p.grad.data_ptr() for g, p in zip(grads, params)):
+                    n = sum(p.numel() for p in params)
+                    torch.cat([g.reshape(-1) for g in grads], out=flat[:n])
+            else:
+                self.opt.zero_grad()
+                self._rebind_flat_gradient()
+                loss.backward()
+            return loss.detach(), pose.detach(), Tn
         finally:
-            if hasattr(self.net, "grad_sink"):
+            if sink:
                 self.net.grad_sink = None
-
-    def _evaluate_grad_body(self, refined_source, template, T, flat, params, in_place):
-        Tn = None
-        if self._fused(refined_source):
-            pred = self.net.raw(refined_source, template)
-            out = pose_apply(pred, refined_source, T, self.net.lim_rot, 1)
-            pose, moved = out[0], out[1]
-            Tn = out[2] if T is not None else None
-        else:
-            pose = self.net(refined_source, template)
-            moved = predicted_pose_applied(refined_source, pose)
-            if T is not None:
-                with torch.no_grad():
-                    pn = torch.cat([pose[:, :3], pose[:, 3:7] / pose[:, 3:7].norm(dim=1, keepdim=True).clamp_min(1e-12)], 1)
-                    Tn = compose(T, pn)
-        loss = self.loss_fn(moved, template)                 # (mean(AB[...,0]) + mean(BA[...,0])) / 2, :248-251
-        if in_place:
-            # TFAdam's flat gradient: the 18 gradients are WRITTEN into it by one concatenation instead of being accumulated into 18 views
-            # of a zeroed buffer (19 in-place adds and a fill per step: 70 us of the captured step at batch 16).  0 + g == g: the same update
-            # The pose network's node writes them straight into the views (grad_sink): no copy at all; the concatenation is the fallback for
-            # whatever did not come back in place (torch pose network, a foreign graph).  The root gradient is a persistent one (no fill).
-            one = self._one if (self._one is not None and self._one.device == loss.device and loss.dim() == 0) else None
-            grads = torch.autograd.grad(loss, params, grad_outputs=one)
-            if not all(g.data_ptr() == p.grad.data_ptr() for g, p in zip(grads, params)):
-                n = sum(p.numel() for p in params)
-                torch.cat([g.reshape(-1) for g in grads], out=flat[:n])
-        else:
-            self.opt.zero_grad()
-            self._rebind_flat_gradient()
-            loss.backward()
-        return loss.detach(), pose.detach(), Tn
-
-    @staticmethod
-    def _offsets(params):
-        off = 0
-        for p in params:
-            yield off
-            off += p.numel()
 
     def _reduce(self):
         if self.reducer is not None and self.reducer.active:
@@ -655,6 +636,9 @@ class IterativeRegistration:
         self._reduce()
         self.opt.step()
         return loss, Tn
+
+    def _eager(self, kind, source, template):
+        return self._train_step_eager(source, template) if kind == "train" else self._evaluate_eager(source, template)
 
     def train_step(self, source, template):
         if self.use_graph and source.is_cuda:
@@ -679,7 +663,7 @@ class IterativeRegistration:
 
     def _graph_step(self, kind, source, template):
         if source.shape != template.shape or source.dtype != torch.float32:
-            return self._train_step_eager(source, template) if kind == "train" else self._evaluate_eager(source, template)
+            return self._eager(kind, source, template)
         key = (kind, tuple(source.shape), source.device.index)
         rec = self._graphs.get(key)
         if rec is not None and rec.loss_key != self._loss_key():     # the frozen loss changed under the graph (new DPDist weights): recapture
@@ -688,7 +672,7 @@ class IterativeRegistration:
         if rec is None:
             seen = self._graph_seen[key] = self._graph_seen.get(key, 0) + 1
             if seen <= self.graph_warmup or len(self._graphs) >= 8:   # real (eager) steps first: library handles, autograd, engine shapes
-                return self._train_step_eager(source, template) if kind == "train" else self._evaluate_eager(source, template)
+                return self._eager(kind, source, template)
             rec = self._graphs[key] = self._capture(kind, source, template)
         rec.src.copy_(source)
         rec.tmpl.copy_(template)

@@ -727,3 +727,55 @@ def test_pose_network_training_evaluation_is_one_node_on_the_library(B, N, with_
     net.native_train = True
     out_n = net.raw(clouds[:B], clouds[B:])
     assert type(out_t.grad_fn).__name__ != "_PoseNetRawFnBackward" and (out_t - out_n).abs().max().item() <= 2e-5 * max(1.0, out_t.abs().max().item())
+
+
+def test_the_library_takes_exactly_the_reference_pose_network():
+    """`native_refine_supported` / `native_point_supported` are the one statement of what csrc/pose.hip implements: the network PoseNet()
+    builds; another feature width, another head layer or another module are the torch path.  The point-only form reads the shared MLP alone."""
+    from dpdist_amd.registration import native_point_supported, native_refine_supported
+    assert native_refine_supported(PoseNet()) and native_point_supported(PoseNet())
+    assert not native_refine_supported(PoseNet(out_features=512)) and not native_point_supported(PoseNet(out_features=512))
+    net = PoseNet()
+    net.head[0] = torch.nn.Linear(2048, 512)
+    assert not native_refine_supported(net) and native_point_supported(net)
+    assert not native_refine_supported(torch.nn.Linear(3, 7)) and not native_point_supported(torch.nn.Linear(3, 7))
+
+
+def _tiny_registration(dev, net):
+    """B = 2, N = 8, eager, a plain mean-square loss (no DPDist engine): the pairs, and the trainer around `net`."""
+    from dpdist_amd.registration import IterativeRegistration
+    src, tmpl, _ = synth.registration_pairs(2, 8, seed=1)
+    reg = IterativeRegistration(net.to(dev), lambda a, b: (a - b).square().mean(), max_loops=3, distributed=False, graph=False)
+    return torch.tensor(src, device=dev), torch.tensor(tmpl, device=dev), reg
+
+
+@pytest.mark.gpu
+def test_reference_pose_network_runs_on_the_library():
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    src, tmpl, reg = _tiny_registration(dev, PoseNet())
+    assert reg.native_refine
+    assert type(reg.net.raw(src, tmpl).grad_fn).__name__ == "_PoseNetRawFnBackward"
+    assert type(reg.net._pooled(torch.cat([src, tmpl], 0)).grad_fn).__name__ == "_PointFeaturesFnBackward"
+    loss, T = reg.train_step(src, tmpl)
+    assert bool(torch.isfinite(loss)) and T.shape == (2, 4, 4)
+    # a source that wants a gradient itself: the library's nodes give weight gradients only, so torch takes it
+    out = reg.net.raw(src.clone().requires_grad_(True), tmpl)
+    assert out.grad_fn is not None and type(out.grad_fn).__name__ != "_PoseNetRawFnBackward"
+    reg.close()
+
+
+@pytest.mark.gpu
+def test_another_pose_network_stays_in_torch_everywhere():
+    """out_features = 512 is not the library's network: `raw`, `_pooled` and the refinements all take torch (the pose algebra stays on
+    csrc/pose.hip), and the step still trains."""
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    src, tmpl, reg = _tiny_registration(dev, PoseNet(out_features=512))
+    assert not reg.native_refine
+    out, f = reg.net.raw(src, tmpl), reg.net._pooled(torch.cat([src, tmpl], 0))
+    assert out.grad_fn is not None and type(out.grad_fn).__name__ != "_PoseNetRawFnBackward"
+    assert f.grad_fn is not None and type(f.grad_fn).__name__ != "_PointFeaturesFnBackward"
+    loss, T = reg.train_step(src, tmpl)
+    assert bool(torch.isfinite(loss)) and T.shape == (2, 4, 4)
+    reg.close()
