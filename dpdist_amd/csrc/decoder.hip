@@ -32,6 +32,7 @@ static int g_x3_tile[OP_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};   // one-plane (bf16)
 static int g_x3_split[OP_COUNT] = {1, 1, 1, 1, 0, 0, 1, 1};
 static int g_x3_pair_tile = 0, g_x3_pair_split = 0;   // plane dW2+dW3 pair: tile (0 = automatic), split-K (as above)
 static int g_x3_trio_tile = 0, g_x3_trio_split = 1;   // plane dW1+dW2+dW3 in one launch (dpd_decoder_bwd_weights_trio): tile, split-K
+static int g_l1u_tile = 33;   // layer 1 over distinct windows (dpd_decoder_fwd_unique): 32 or 33 (dpd_set_gemm_plan op 8)
 constexpr size_t kRedCntBytes = 8192;                 // arrival words of the in-launch reduction: the last 8 KiB of the base workspace
 
 // Compute type of the three wide layers (the `dtype` argument of the decoder entry points):
@@ -966,9 +967,54 @@ __global__ __launch_bounds__(256) void transpose_kernel(TransposeJobs J) {
     }
 }
 
+// Layer 1 over distinct windows, second step (dpd_decoder_fwd_unique): wave = one 32 x 32 tile of h1.  The accumulators of row r are
+// those of its window, Pu[uid[r]] (the chain over the K-tiles before the last), loaded in the MFMA accumulator layout; the chain goes on
+// with the 16 MFMAs of the last K-tile on Xt [Q, 32] and the last 32 rows of W1p -- the same (b, s) order and lane <-> k assignment as
+// gemm_rs_kernel (k = 16 half + 4 b + s) -- then bias, ReLU and put_tile.  An fp32 accumulator that passes through memory keeps its
+// bits, so h1 is bit for bit what gemm_rs_kernel leaves for the whole rows.
+__global__ __launch_bounds__(256) void l1_finish_kernel(const float* __restrict__ Pu, const int32_t* __restrict__ uid,
+                                                        const float* __restrict__ Xt, const float* __restrict__ Wt,
+                                                        const float* __restrict__ bias, float* __restrict__ h1, int Q, int H) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l31 = lane & 31, half = lane >> 5;
+    const int tilesN = H / 32, t = blockIdx.x * 4 + wave;
+    if (t >= (Q / 32) * tilesN) return;
+    const int m0 = (t / tilesN) * 32, col = (t % tilesN) * 32 + l31;
+    int u[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) u[r] = uid[m0 + (r & 3) + 8 * (r >> 2) + 4 * half];
+    float a[4][4], w[4][4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const float4 x = *reinterpret_cast<const float4*>(Xt + (size_t)(m0 + l31) * 32 + 16 * half + 4 * b);
+        a[b][0] = x.x; a[b][1] = x.y; a[b][2] = x.z; a[b][3] = x.w;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) w[b][s] = Wt[(size_t)(16 * half + 4 * b + s) * H + col];
+    }
+    const float bv = bias[col];
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = Pu[(size_t)u[r] * H + col];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[b][s], w[b][s], acc, 0, 0, 0);
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = fmaxf(acc[r] + bv, 0.f);
+    GemmArgs g{};
+    g.C = h1; g.M = Q; g.N = H; g.ldc = H;
+    put_tile(g, v, 0, m0, col, half);
+}
+
 }  // namespace dpd
 
 extern "C" int dpd_set_gemm_plan(int op, int tile, int split_k) {
+    if (op == 8) {      // layer 1 over distinct windows: the two 32-row wave tiles (same bits)
+        if (tile != 32 && tile != 33) return DPD_E_DIM;
+        dpd::g_l1u_tile = tile;
+        return 0;
+    }
     // plane GEMMs: ops 16.. = call sites, 32 = the grouped dW2 + dW3 launch; split_k: n > 1 in-launch reduction, n < -1 slabs + reduce
     // launch, 1 off, 0 automatic (decoder.hip: g_x3_split)
     if (op >= 16 && op < 16 + dpd::OP_COUNT && tile >= 0 && tile <= 26 && split_k >= -8 && split_k <= 8) {
@@ -1126,6 +1172,40 @@ extern "C" int dpd_decoder_fwd(const float* X, const float* mask, int Q, int KP,
         return DPD_E_WORKSPACE;
     }
     for (const GemmDtCall* c : {&l1, &l2, &l3})
+        if (int rc = gemm_dt(*c)) return rc;
+    if (!y) return 0;
+    DPD_LAUNCH(out_fwd_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, h3, p->W4, p->b4, mask, y, pred, Q, H);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_decoder_fwd_unique(const float* Xu /* k-major */, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu, const float* mask,
+                                      int Q, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y,
+                                      float* pred, void* stream) {
+    using namespace dpd;
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !mask || !p || !h1 || !h2 || !h3 || (!y != !pred)) return DPD_E_NULL;
+    if (!p->W1p || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4) return DPD_E_NULL;
+    if (Q <= 0 || KP <= 0 || H <= 0) return DPD_E_DIM;
+    if ((H & 63) || (KP & 31) || KP < 64 || (Q & 31)) return DPD_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    // layer 1, first step: Pu [Q + 32, H] = XuT^T W1p[0 : KP - 32] over the live slots cnt[1] (raw accumulators); XuT is k-major
+    GemmF32Call f;
+    f.transA = 1; f.M = Q + 32; f.N = H; f.K = KP - 32;
+    f.A = Xu; f.lda = Q + 32; f.B = p->W1p; f.ldb = H; f.C = Pu; f.ldc = H;
+    f.epilogue = EPI_NONE; f.split_k = 1; f.tile = g_l1u_tile; f.s = s; f.M_dev = cnt + 1;
+    if (int rc = gemm_f32(f)) return rc;
+    // second step: the last K-tile, bias and ReLU per row
+    DPD_LAUNCH(l1_finish_kernel, dim3(((Q / 32) * (H / 32) + 3) / 4), dim3(256), 0, s, (const float*)Pu, uid, Xt,
+               p->W1p + (size_t)(KP - 32) * H, p->b1, h1, Q, H);
+    DPD_CHECK_LAUNCH();
+    GemmDtCall l2, l3;
+    for (GemmDtCall* c : {&l2, &l3}) {
+        c->dtype = 0; c->op = OP_FWD_L23; c->M = Q; c->N = H; c->K = H; c->lda = H; c->ldb = H; c->ldc = H;
+        c->epilogue = EPI_BIAS_RELU; c->s = s;
+    }
+    l2.A = h1; l2.B = p->W2; l2.bias = p->b2; l2.C = h2;
+    l3.A = h2; l3.B = p->W3; l3.bias = p->b3; l3.C = h3;
+    for (const GemmDtCall* c : {&l2, &l3})
         if (int rc = gemm_dt(*c)) return rc;
     if (!y) return 0;
     DPD_LAUNCH(out_fwd_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, h3, p->W4, p->b4, mask, y, pred, Q, H);

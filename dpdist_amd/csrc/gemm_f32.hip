@@ -514,6 +514,8 @@ int gemm_f32(const GemmF32Call& c) {
     if (c.A2 && (!c.B2 || !c.C2 || split_k > 1 || c.epilogue != EPI_NONE || c.colsum)) return DPD_E_UNSUPPORTED;
     if (c.A2 && !whole_tiles) return DPD_E_UNSUPPORTED;   // grouped launches exist for the DMA / register-streamed kernels only
     if (c.colsum && split_k > 1) return DPD_E_UNSUPPORTED;
+    if (c.M_dev && (!f32_tile_rs(tile) || split_k > 1 || g.tail_split || c.A2 || c.colsum || c.cs2)) return DPD_E_UNSUPPORTED;
+    g.M_dev = c.M_dev;
     g.M = M; g.N = N; g.K = K; g.lda = c.lda; g.ldb = c.ldb;
     g.split_k = split_k;
     if (split_k > 1) {

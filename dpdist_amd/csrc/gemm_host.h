@@ -33,6 +33,7 @@ struct GemmF32Call {
     const float* B2 = nullptr;
     float* C2 = nullptr;
     const ColsumTwoStep* cs2 = nullptr;   // two-step bias gradient (register-streamed kernels)
+    const int* M_dev = nullptr;           // GemmArgs::M_dev (TN, tiles 32 / 33, no split): M is then the capacity
 };
 int gemm_f32(const GemmF32Call& c);
 

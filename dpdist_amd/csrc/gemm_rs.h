@@ -56,9 +56,11 @@ __device__ __forceinline__ void rs_load_step(__amdgpu_buffer_rsrc_t r, unsigned 
 
 // D = pipeline depth in K-tiles (operand register sets): the loads of K-tile t+D-1 are issued, step by step, between the
 // MFMAs of K-tile t, so every operand has D-1 whole tile times ((TM*TN*16) MFMAs x 64 cycles each) to arrive.
-template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D>
+// DM: the live row count comes from the device word g.M_dev (GemmArgs::M_dev); g.M is the capacity the grid was launched for.
+template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D, bool DM = false>
 __global__ __launch_bounds__(64 * WR * WC) void gemm_rs_kernel(GemmArgs g) {
     constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
+    if (DM) g.M = min(g.M, __builtin_amdgcn_readfirstlane(*g.M_dev));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -67,6 +69,8 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_rs_kernel(GemmArgs g) {
     const int tilesM = (g.M + BM - 1) / BM, tilesN = (g.N + BN - 1) / BN;
     const int per_z = tilesM * tilesN;
     const int ngrp = g.A2 ? 2 : 1;
+    // (the XCD map below is taken over the LIVE tile count: over the capacity, the dead tiles would be the high ids and whole XCDs idle)
+    if (DM && (int)blockIdx.x >= per_z * g.split_k * ngrp) return;
     int grp = 0, z, t;
     unsigned kbeg, kend;
     if (g.tail_split > 1) {     // whole-K tiles first, then the K pieces of the last round's tiles
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(float* __restrict__ C,
     }
 }
 
-template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D>
+template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D, bool DM = false>
 static int launch_rs(const GemmArgs& g_in, hipStream_t s) {
     constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
     GemmArgs g = g_in;
@@ -271,7 +275,7 @@ static int launch_rs(const GemmArgs& g_in, hipStream_t s) {
             }
         }
     }
-    DPD_LAUNCH((gemm_rs_kernel<AK, BKC, TM, TN, WR, WC, D>), dim3(nblk), dim3(64 * WR * WC), 0, s, g);
+    DPD_LAUNCH((gemm_rs_kernel<AK, BKC, TM, TN, WR, WC, D, DM>), dim3(nblk), dim3(64 * WR * WC), 0, s, g);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
     if (g.tail_split > 1) {
         const long total4 = (long)(g.M - row0) * g.N / 4;
@@ -286,6 +290,14 @@ static int launch_rs(const GemmArgs& g_in, hipStream_t s) {
 // tile codes 30..33: register-streamed kernels (wave tile, waves per workgroup, pipeline depth)
 template <bool AK, bool BKC>
 static int launch_rs_tile(int tile, const GemmArgs& g, hipStream_t s) {
+    if (g.M_dev) {      // live row count on the device: the TN form of the two 32-row wave tiles (a k-ordered chain per element: same bits)
+        if constexpr (!AK && !BKC) {
+            if (g.split_k != 1 || g.tail_split || g.A2) return DPD_E_UNSUPPORTED;
+            if (tile == 32) return launch_rs<AK, BKC, 1, 2, 2, 2, 2, true>(g, s);
+            if (tile == 33) return launch_rs<AK, BKC, 1, 1, 2, 2, 2, true>(g, s);
+        }
+        return DPD_E_UNSUPPORTED;
+    }
     switch (tile) {
         case 30: return launch_rs<AK, BKC, 2, 2, 2, 2, 2>(g, s);   // 128x128 workgroup, 4 waves of 64x64, 2 operand sets
         case 31: return launch_rs<AK, BKC, 2, 1, 2, 2, 2>(g, s);   // 128x64,  4 waves of 64x32

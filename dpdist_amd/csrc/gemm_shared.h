@@ -47,6 +47,9 @@ struct GemmArgs {
     float* tail_slab;
     int k_chunk;      // K range per split (multiple of BK)
     long slab_stride; // floats between split-K slabs (0 when split_k == 1)
+    // optional (register-streamed TN kernels, A stored [K][M]): the LIVE row count as a device word, <= M.  The grid is launched for M (the capacity);
+    // tiles, the XCD map and every clamp use the live count, workgroups beyond the live tiles leave at once.  NULL: M is the count
+    const int* M_dev;
 };
 
 // host-side bundle of the two-step bias-gradient pointers (see GemmArgs::colsum_part)

@@ -472,6 +472,8 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_lds_kernel(const float* __
     }
 }
 
+#include "patch_rows_unique.h"      // the same gather over distinct windows (window_index_kernel, patch_rows_fwd_unique_kernel)
+
 // Backward as a gather (patch_rows_bwd.h): block (c, slice) owns a slice of the voxels of cloud c
 __global__ __launch_bounds__(256) void patch_rows_bwd_kernel(const float* __restrict__ dX, const int32_t* __restrict__ vox,
                                                               float* __restrict__ dfv, int N, int m, int k, int KP,
@@ -604,6 +606,44 @@ extern "C" int dpd_patch_rows_fwd_scaled(const float* q, const float* fv, const 
     }
     DPD_LAUNCH(patch_rows_fwd_kernel, dim3((C * N + 1) / 2), dim3(256), 0, (hipStream_t)stream, q, fv, X, mask, vox, N, m, k,
                        KP, make_axis(m), C * N, ssq, kMfvSlices);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t dpd_patch_rows_unique_scratch_bytes(int C, int N) {
+    return (C <= 0 || N <= 0) ? 0 : ((size_t)2 * C * N + C) * sizeof(int32_t);
+}
+
+extern "C" int dpd_patch_rows_fwd_unique(const float* q, const float* fv, const float* ssq, int C, int N, int m, int k, int KP, int Qb,
+                                         float* X, int x_rows, float* Xu, float* Xt, float* mask, int32_t* vox, int32_t* uid, int32_t* cnt,
+                                         void* scratch, size_t scratch_bytes, void* stream) {
+    using namespace dpd;
+    if (!q || !fv || !Xu || !Xt || !mask || !vox || !uid || !cnt || !scratch || (x_rows > 0 && !X)) return DPD_E_NULL;
+    if (C <= 0 || N <= 0 || Qb < 0 || x_rows < 0) return DPD_E_DIM;
+    const int Q = C * N;
+    if (Qb > Q || x_rows > Q || Qb % N || x_rows % N) return DPD_E_DIM;       // the two halves, and the rows of X, are whole clouds
+    if (scratch_bytes < dpd_patch_rows_unique_scratch_bytes(C, N)) return DPD_E_WORKSPACE;
+    // the shapes of the LDS form, and a row whose last 32 columns hold everything that differs between two rows of one window
+    if (m < 1 || m > 10 || k < 3 || k > 7 || !(k & 1) || (N & 7) || N > 1024 || KP != dpd_padded_width(k) || k * k * k * kF < KP - 32)
+        return DPD_E_UNSUPPORTED;
+    const size_t lds = (size_t)m * m * m * kF * sizeof(float) + (size_t)(KP / 4) * sizeof(int2) + (size_t)N * (sizeof(float4) + sizeof(UqRow) + sizeof(int));
+    const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
+    for (int x = 0; x < k * k * k; ++x)
+        if ((int)((x * mg_kk) >> 16) != x / (k * k) || (int)(((x % (k * k)) * mg_k) >> 16) != (x % (k * k)) / k) return DPD_E_UNSUPPORTED;
+    if (lds > 128 * 1024) return DPD_E_UNSUPPORTED;
+    int32_t* lu = (int32_t*)scratch;
+    int32_t* first = lu + Q;
+    int32_t* ucount = first + Q;
+    // algorithmic bytes as in dpd_patch_rows_fwd_scaled; the rows out are an upper bound (Xu holds the distinct windows only)
+    StageProf prof(stream, DPD_STAGE_GATHER,
+                   (double)C * m * m * m * kF * 4.0 + Q * 12.0 + Q * 8.0 + Q * 4.0 + (double)Q * 32 * 4.0 + (double)(Q + x_rows) * KP * 4.0);      // Xu [KP - 32, Q + 32]: k-major
+    DPD_LAUNCH(window_index_kernel, dim3(C), dim3(64), (size_t)2 * N * sizeof(int), (hipStream_t)stream, q, N, m, make_axis(m), mask, vox, lu,
+               first, ucount);
+    DPD_CHECK_LAUNCH();
+    static LdsOptIn lu_opt;
+    if (int rc2 = ensure_dyn_lds(lu_opt, (const void*)patch_rows_fwd_unique_kernel, lds)) return rc2;
+    DPD_LAUNCH(patch_rows_fwd_unique_kernel, dim3(x_rows / 8 + C * kUqChunks), dim3(512), lds, (hipStream_t)stream, q, fv, X, x_rows, Xu, Q + 32, Xt, (const int32_t*)lu,
+               (const int32_t*)first, (const int32_t*)ucount, uid, cnt, Q, N, Qb, m, k, KP, make_axis(m), ssq, kMfvSlices, mg_k, mg_kk);
     DPD_CHECK_LAUNCH();
     return 0;
 }

@@ -61,6 +61,10 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "dpd_patch_rows_fwd_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, POINTER(Planes), c_void_p]),
+    "dpd_patch_rows_unique_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "dpd_patch_rows_fwd_unique": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dpd_decoder_fwd_unique": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, POINTER(DecoderParams)] + [c_void_p] * 6),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

@@ -88,6 +88,7 @@ class DPDistTrainer:
         "keep_f32_h": False,   # plane types: also write the fp32 h1 / h2 / g1 / g2 (on: for inspection)
         "dw_trio": None,       # plane types: dW1 + dW2 + dW3 as one grouped launch (None: on for one plane, off for three)
         "dp_buckets": 2,       # data-parallel "early" order: 2 = layers 2-4 as one collective, 3 = one per layer
+        "unique_l1": None,     # exact fp32: layer 1 once per distinct (cloud, voxel) window, same bits (None: on where the shapes allow it)
     }
 
     def __init__(self, params: DPDistParams, batch_size, num_point=64, Embedding_Size=512, sigma3dmfv=0.125, base_lr=1e-4,
@@ -134,11 +135,16 @@ class DPDistTrainer:
         # front end in two launches (dpd_mfv3d_fwd_stacked + dpd_patch_rows_fwd_scaled) instead of four
         self.front2 = bool(opt["front2"])
         self._h3_plane_opt, self._dp_buckets = bool(opt["h3_plane"]), int(opt["dp_buckets"])
+        # `dpd_patch_rows_fwd_unique` + `dpd_decoder_fwd_unique`: exact fp32 and the shapes those two take; any other shape keeps the
+        # plain gather and layer 1 (orthogonal to every other option: the activations have the same bits either way)
+        self.unique_l1 = bool((opt["unique_l1"] is None or opt["unique_l1"]) and self.dt == 0 and N % 8 == 0 and N <= 1024 and Q % 32 == 0
+                              and self.k >= 3 and KP == L.load().dpd_padded_width(self.k) and KP >= 64 and H % 64 == 0 and self.m <= 10)
         # -- allocations: this ORDER decides the addresses (the plane memory follows the workspace) --
         self._alloc_buffers()
         self._alloc_planes(keep_f32_h=opt["keep_f32_h"])
         self._init_data_parallel(group, distributed, adam_on_side)
         self._init_adam_fuse()
+        self._alloc_unique()
         # one plane (bf16): dW1 + dW2 + dW3 as one grouped launch; three planes (f32x3): measured SLOWER grouped (0.557 vs 0.523 ms at B = 32:
         # its dW1 alone runs the phase-staggered 128x128 kernel, the grouped launch needs the ring kernel), so opt-in there (options["dw_trio"])
         self._trio = self._planes is not None and bool(self._planes.np == 1 if opt["dw_trio"] is None else opt["dw_trio"])
@@ -175,6 +181,18 @@ class DPDistTrainer:
         self.m_state = torch.zeros_like(self.grad)
         self.v_state = torch.zeros_like(self.grad)
         self.ws = torch.empty((L.load().dpd_workspace_bytes(Q, P.KP, P.H, self.dt) + 3) // 4, device=dev, dtype=torch.float32)
+
+    def _alloc_unique(self):
+        """Front-end buffers of the distinct-window form (`unique_l1`), allocated last so that every other address stays where it was.
+        They are written by the gather and last read by the decoder forward, X[:BN] by dW1: the prefetch pipeline's gate on X covers them."""
+        self.Xu = self.Xt = self.Pu = self.uid = self.ucnt = self._uscratch = None
+        if not self.unique_l1:
+            return
+        f, dev, Q, P = self._f32, self.P.flat.device, self.Q, self.P
+        self.Xu, self.Xt, self.Pu = f(P.KP - 32, Q + 32), f(Q, 32), f(Q + 32, P.H)     # distinct windows (k-major), last K-tile of every row, raw layer-1 sums
+        self.uid = torch.empty(Q, device=dev, dtype=torch.int32)                  # window slot of every row
+        self.ucnt = torch.zeros(4, device=dev, dtype=torch.int32)                 # {U_AB, M_u, U_ABp, 0}: read by kernels only
+        self._uscratch = torch.empty(L.load().dpd_patch_rows_unique_scratch_bytes(self.C, self.N), device=dev, dtype=torch.uint8)
 
     def _alloc_planes(self, keep_f32_h):
         """The operand planes of the bf16-matrix-core compute types, then the fp32 activations the planes do not stand in for."""
@@ -307,6 +325,12 @@ class DPDistTrainer:
         """norm_from_ssq: fv of the two-launch front end still lacks its L2 norm: the gather applies it from the per-slice sums of
         squares (`_encode` leaves fv normalised)."""
         lib, s, P = L.load(), L.cur_stream(), self.P
+        if self.unique_l1:      # distinct windows for layer 1; whole rows only for the half that carries gradient (dW1 contracts over rows)
+            L.check(lib.dpd_patch_rows_fwd_unique(L.ptr(self.q), L.ptr(self.fv), L.ptr(self._ssq) if norm_from_ssq else None, self.C, self.N,
+                                                  self.m, self.k, P.KP, self.BN, L.ptr(self.X), self.BN, L.ptr(self.Xu), L.ptr(self.Xt),
+                                                  L.ptr(self.mask), L.ptr(self.vox), L.ptr(self.uid), L.ptr(self.ucnt),
+                                                  L.ptr(self._uscratch), self._uscratch.numel(), s), "dpd_patch_rows_fwd_unique")
+            return
         L.check(lib.dpd_patch_rows_fwd_scaled(L.ptr(self.q), L.ptr(self.fv), L.ptr(self._ssq) if norm_from_ssq else None, self.C, self.N,
                                               self.m, self.k, P.KP, None if self._planes is not None else L.ptr(self.X),
                                               L.ptr(self.mask), L.ptr(self.vox), self._planes, s), "dpd_patch_rows_fwd_scaled")
@@ -331,6 +355,12 @@ class DPDistTrainer:
         h3 = None if h3_in_plane else self.h3
         if self._wdirty:
             self.refresh_weight_planes()
+        if self.unique_l1:
+            L.check(lib.dpd_decoder_fwd_unique(L.ptr(self.Xu), L.ptr(self.Xt), L.ptr(self.uid), L.ptr(self.ucnt), L.ptr(self.Pu),
+                                               L.ptr(self.mask), self.Q, P.KP, P.H, self._cparams, L.ptr(self.h1), L.ptr(self.h2), L.ptr(h3),
+                                               None if skip_out else L.ptr(self.y), None if skip_out else L.ptr(self.pred), s),
+                    "dpd_decoder_fwd_unique")
+            return
         L.check(lib.dpd_decoder_fwd(L.ptr(self.X), L.ptr(self.mask), self.Q, P.KP, P.H, self._cparams, self.dt, L.ptr(self.h1),
                                     L.ptr(self.h2), L.ptr(h3), None if skip_out else L.ptr(self.y),
                                     None if skip_out else L.ptr(self.pred), L.ptr(self.ws), self.ws.numel() * 4, self._planes, s),

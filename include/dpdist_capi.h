@@ -108,6 +108,23 @@ int dpd_mfv3d_fwd_stacked(const float* pcA, const float* pcB, const float* noise
 int dpd_patch_rows_fwd_scaled(const float* q, const float* fv, const float* ssq, int C, int N, int m, int k, int KP,
                               float* X, float* mask, int32_t* vox, const struct dpd_planes* pl, void* stream);
 
+/* The same gather over DISTINCT windows (DPD_F32 training step).  The window part of row r = c*N + n depends on (cloud, voxel)
+ * only, so it is written once per distinct pair and layer 1 runs over those rows (dpd_decoder_fwd_unique):
+ *   uid [Q]          slot of the row's window = that of the first row of its cloud with the same voxel; slots are dense and in row
+ *                    order: [0, U_AB) for the rows < Qb, a gap up to U_ABp = roundup(U_AB, 32), then the rows >= Qb up to M_u;
+ *   Xu [KP - 32, Q + 32]  K-MAJOR: column `slot` holds columns [0, KP - 32) of the row that owns the slot; gap columns zero; every
+ *                    other column untouched (layer 1 reads it as a weight gradient reads its activations: 128 contiguous bytes per k);
+ *   Xt [Q, 32]       columns [KP - 32, KP) of every row (the last window values, q - centre, the zero pad);
+ *   cnt [4]          {U_AB, M_u, U_ABp, 0} as device words (the host never needs them);
+ *   X [x_rows, KP]   optional (x_rows = 0: none): the whole rows r < x_rows as dpd_patch_rows_fwd_scaled writes them (what the
+ *                    weight gradient of layer 1 contracts over); mask, vox as there; ssq as there (NULL = fv is normalised).
+ * Qb = the rows of the first half (whole clouds).  scratch: dpd_patch_rows_unique_scratch_bytes(C, N) bytes.  Two launches (index,
+ * gather).  Needs k >= 3, KP == dpd_padded_width(k), N % 8 == 0, N <= 1024, x_rows % N == 0, m <= 10 (else DPD_E_UNSUPPORTED: use the plain gather). */
+size_t dpd_patch_rows_unique_scratch_bytes(int C, int N);
+int dpd_patch_rows_fwd_unique(const float* q, const float* fv, const float* ssq, int C, int N, int m, int k, int KP, int Qb,
+                              float* X, int x_rows, float* Xu, float* Xt, float* mask, int32_t* vox, int32_t* uid, int32_t* cnt,
+                              void* scratch, size_t scratch_bytes, void* stream);
+
 /* Backward of the gather: dX [Q,KP] -> dq [C,N,3] (overwritten; = dX[:,E:E+3]) and
  * dfv [C,m^3,20] (overwritten; scatter-add of the window columns).  Either output may be NULL.  */
 int dpd_patch_rows_bwd(const float* dX, const int32_t* vox, int C, int N, int m, int k, int KP, float* dq,
@@ -158,6 +175,15 @@ int dpd_weights_transpose(const dpd_decoder_params* p, int KP, int H, float* W2T
 int dpd_decoder_fwd(const float* X, const float* mask, int Q, int KP, int H, const dpd_decoder_params* p,
                     int dtype, float* h1, float* h2, float* h3, float* y, float* pred, void* ws, size_t ws_bytes,
                     const dpd_planes* pl, void* stream);
+
+/* dpd_decoder_fwd (DPD_F32) on the outputs of dpd_patch_rows_fwd_unique: layer 1 contracts its first KP - 32 columns once per
+ * distinct window -- Pu [Q + 32, H] = Xu^T W1p[0 : KP - 32] over the cnt[1] live slots, the row count read on the device -- and one more launch
+ * continues each row's accumulators Pu[uid[r]] with the last 32 columns (Xt), adds the bias and applies the ReLU.  The order of
+ * every element's fp32 chain is that of dpd_decoder_fwd's layer 1 on the register-streamed kernels (its default), so h1 -- and
+ * with it h2, h3, y, pred -- has the same BITS.  Pu is scratch.  Needs Q % 32 == 0, KP % 32 == 0, KP >= 64, H % 64 == 0.      */
+int dpd_decoder_fwd_unique(const float* Xu, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu, const float* mask,
+                           int Q, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y,
+                           float* pred, void* stream);
 
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in
@@ -594,7 +620,7 @@ int dpd_gemm_planes(int np, int a_fmt, int b_fmt, int M, int N, int K, const voi
 
 /* Tuning knob (process-wide, never needed for correctness): GEMM tile / split-K per
  * call site.  op: 0 fwd layer 1, 1 fwd layers 2-3, 2 bwd dH, 3 bwd dX, 4 bwd dW1, 5 bwd dW2/3, 6 / 7 bwd dH / dX with a
- * transposed weight copy; 16 + op: one-plane (bf16) tile of gemm_x3.hip for that call site (0 = automatic; 1-5 ring kernels, 13 =
+ * transposed weight copy, 8 layer 1 of dpd_decoder_fwd_unique (tile 32 or 33 only); 16 + op: one-plane (bf16) tile of gemm_x3.hip for that call site (0 = automatic; 1-5 ring kernels, 13 =
  * 192x128 at BK 64, 21 / 23 / 24 phase-staggered), 32: its grouped dW2/dW3 launch, 33: the grouped dW1/dW2/dW3 launch of
  * dpd_decoder_bwd_weights_trio.  tile as in dpd_gemm_f32 (0 = auto); split_k applies to ops 4, 5 and, for the plane weight gradients
  * (ops 20, 21, 32, 33): n > 1 = n K slices per tile reduced inside the launch (last-arriving slice, slice order: deterministic),
