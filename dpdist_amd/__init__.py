@@ -16,4 +16,7 @@ def __getattr__(name):
     if name in ("get_model", "get_loss", "DPDistModel", "DPDistLoss", "placeholder_inputs"):
         from . import model
         return getattr(model, name)
+    if name == "dpdist_matrix":
+        from . import pairwise
+        return pairwise.dpdist_matrix
     raise AttributeError(name)

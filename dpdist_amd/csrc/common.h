@@ -65,7 +65,7 @@ inline int ensure_dyn_lds(LdsOptIn& slot, const void* kern, size_t lds) {
 // event pair and record their ALGORITHMIC HBM bytes (every input read once, every output written once) under a stage tag; bench.py
 // turns that into the `roofline_hbm` object of its JSON line.  Off (one branch, no lock) unless the profiler was enabled with mode 2.
 enum { DPD_STAGE_GEMM = 0, DPD_STAGE_ENCODER = 1, DPD_STAGE_GATHER = 2, DPD_STAGE_OUT_LAYER = 3, DPD_STAGE_OPTIMIZER = 4,
-       DPD_STAGE_SMALL_REDUCE = 5, DPD_STAGE_WEIGHT_COPIES = 6, DPD_STAGE_COUNT = 7 };
+       DPD_STAGE_SMALL_REDUCE = 5, DPD_STAGE_WEIGHT_COPIES = 6, DPD_STAGE_L1_FINISH = 7, DPD_STAGE_COUNT = 8 };
 bool prof_begin_stage(hipStream_t s);
 void prof_end_stage(bool on, hipStream_t s, int tag, double bytes);
 struct StageProf {
@@ -73,11 +73,15 @@ struct StageProf {
     hipStream_t s;
     int tag;
     double bytes;
-    StageProf(void* stream, int tag_, double bytes_) : on(prof_begin_stage((hipStream_t)stream)), s((hipStream_t)stream), tag(tag_), bytes(bytes_) {}
+    StageProf(void* stream, int tag_, double bytes_, bool want = true)
+        : on(want && prof_begin_stage((hipStream_t)stream)), s((hipStream_t)stream), tag(tag_), bytes(bytes_) {}
     ~StageProf() { prof_end_stage(on, s, tag, bytes); }
     StageProf(const StageProf&) = delete;
     StageProf& operator=(const StageProf&) = delete;
 };
+
+// The fp32 GEMM kernels form operand and result addresses as 32-bit BYTE offsets (gemm_rs.h): a [rows, ld] fp32 matrix must stay below 4 GiB
+inline bool fits_gemm_offsets(size_t rows, size_t ld) { return rows * ld * sizeof(float) < (1ull << 32); }
 
 constexpr int kWave = 64;   // CDNA wavefront
 constexpr int kNumXCD = 8;  // MI355X: 8 XCDs, block b runs on XCD b % 8 (speed only, never correctness)

@@ -1007,6 +1007,18 @@ __global__ __launch_bounds__(256) void l1_finish_kernel(const float* __restrict_
     put_tile(g, v, 0, m0, col, half);
 }
 
+// All-pairs distance matrix (dpd_decoder_fwd_cross): Dd[p] = mean over the N rows of pair p of pred[:, 0].  One wave per pair: lane l
+// adds rows l, l + 64, ... in order, then the fixed tree of wave_sum -- the same order for every pair, whatever the launch holds.
+__global__ __launch_bounds__(256) void pair_mean_kernel(const float* __restrict__ pred, int N, int pairs, float* __restrict__ Dd) {
+    const int lane = threadIdx.x & 63, pr = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pr >= pairs) return;
+    const float* src = pred + (size_t)pr * N * 3;
+    float a = 0.f;
+    for (int n = lane; n < N; n += 64) a += src[(size_t)n * 3];
+    a = wave_sum(a);
+    if (lane == 0) Dd[pr] = a / (float)N;
+}
+
 }  // namespace dpd
 
 extern "C" int dpd_set_gemm_plan(int op, int tile, int split_k) {
@@ -1179,25 +1191,26 @@ extern "C" int dpd_decoder_fwd(const float* X, const float* mask, int Q, int KP,
     return 0;
 }
 
-extern "C" int dpd_decoder_fwd_unique(const float* Xu /* k-major */, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu, const float* mask,
-                                      int Q, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y,
-                                      float* pred, void* stream) {
+// Layer 1 over `cap` slots of Xu (k-major, row stride lda; the live count is the device word *m_dev) and its finish launch, layers 2 and 3,
+// the output layer: the launches of dpd_decoder_fwd_unique and dpd_decoder_fwd_cross
+static int fwd_over_slots(const float* Xu, int lda, int cap, const float* Xt, const int32_t* uid, const int32_t* m_dev, float* Pu, const float* mask,
+                          int Q, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y, float* pred,
+                          hipStream_t s, bool prof_stages) {
     using namespace dpd;
-    if (!Xu || !Xt || !uid || !cnt || !Pu || !mask || !p || !h1 || !h2 || !h3 || (!y != !pred)) return DPD_E_NULL;
-    if (!p->W1p || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4) return DPD_E_NULL;
-    if (Q <= 0 || KP <= 0 || H <= 0) return DPD_E_DIM;
-    if ((H & 63) || (KP & 31) || KP < 64 || (Q & 31)) return DPD_E_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    // layer 1, first step: Pu [Q + 32, H] = XuT^T W1p[0 : KP - 32] over the live slots cnt[1] (raw accumulators); XuT is k-major
+    // layer 1, first step: Pu [cap, H] = XuT^T W1p[0 : KP - 32] over the live slots (raw accumulators); XuT is k-major
     GemmF32Call f;
-    f.transA = 1; f.M = Q + 32; f.N = H; f.K = KP - 32;
-    f.A = Xu; f.lda = Q + 32; f.B = p->W1p; f.ldb = H; f.C = Pu; f.ldc = H;
-    f.epilogue = EPI_NONE; f.split_k = 1; f.tile = g_l1u_tile; f.s = s; f.M_dev = cnt + 1;
+    f.transA = 1; f.M = cap; f.N = H; f.K = KP - 32;
+    f.A = Xu; f.lda = lda; f.B = p->W1p; f.ldb = H; f.C = Pu; f.ldc = H;
+    f.epilogue = EPI_NONE; f.split_k = 1; f.tile = g_l1u_tile; f.s = s; f.M_dev = m_dev;
     if (int rc = gemm_f32(f)) return rc;
     // second step: the last K-tile, bias and ReLU per row
-    DPD_LAUNCH(l1_finish_kernel, dim3(((Q / 32) * (H / 32) + 3) / 4), dim3(256), 0, s, (const float*)Pu, uid, Xt,
-               p->W1p + (size_t)(KP - 32) * H, p->b1, h1, Q, H);
-    DPD_CHECK_LAUNCH();
+    {
+        // (prof_stages: the all-pairs engine brackets the two launches that are no GEMM; bytes: Pu rows, Xt, uid in, h1 out)
+        StageProf prof(s, DPD_STAGE_L1_FINISH, (double)Q * (2.0 * H + 33.0) * 4.0, prof_stages);
+        DPD_LAUNCH(l1_finish_kernel, dim3(((Q / 32) * (H / 32) + 3) / 4), dim3(256), 0, s, (const float*)Pu, uid, Xt,
+                   p->W1p + (size_t)(KP - 32) * H, p->b1, h1, Q, H);
+        DPD_CHECK_LAUNCH();
+    }
     GemmDtCall l2, l3;
     for (GemmDtCall* c : {&l2, &l3}) {
         c->dtype = 0; c->op = OP_FWD_L23; c->M = Q; c->N = H; c->K = H; c->lda = H; c->ldb = H; c->ldc = H;
@@ -1208,7 +1221,39 @@ extern "C" int dpd_decoder_fwd_unique(const float* Xu /* k-major */, const float
     for (const GemmDtCall* c : {&l2, &l3})
         if (int rc = gemm_dt(*c)) return rc;
     if (!y) return 0;
+    StageProf prof(s, DPD_STAGE_OUT_LAYER, (double)Q * (H + 7.0) * 4.0, prof_stages);
     DPD_LAUNCH(out_fwd_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, h3, p->W4, p->b4, mask, y, pred, Q, H);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_decoder_fwd_unique(const float* Xu /* k-major */, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu, const float* mask,
+                                      int Q, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y,
+                                      float* pred, void* stream) {
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !mask || !p || !h1 || !h2 || !h3 || (!y != !pred)) return DPD_E_NULL;
+    if (!p->W1p || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4) return DPD_E_NULL;
+    if (Q <= 0 || KP <= 0 || H <= 0) return DPD_E_DIM;
+    if ((H & 63) || (KP & 31) || KP < 64 || (Q & 31)) return DPD_E_UNSUPPORTED;
+    return fwd_over_slots(Xu, Q + 32, Q + 32, Xt, uid, cnt + 1, Pu, mask, Q, KP, H, p, h1, h2, h3, y, pred, (hipStream_t)stream, false);
+}
+
+extern "C" int dpd_decoder_fwd_cross(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt,
+                                     float* Pu, const float* maskr, int pairs, int N, int KP, int H, const dpd_decoder_params* p, float* act0,
+                                     float* act1, float* y, float* pred, float* Dd, void* stream) {
+    using namespace dpd;
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !maskr || !p || !act0 || !act1 || !y || !pred || !Dd) return DPD_E_NULL;
+    if (!p->W1p || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4) return DPD_E_NULL;
+    if (pairs <= 0 || N <= 0 || KP <= 0 || H <= 0 || slot_cap <= 0 || ldu < slot_cap || (long)pairs * N > (1L << 30)) return DPD_E_DIM;
+    if ((H & 63) || (KP & 31) || KP < 64 || (slot_cap & 3) || (ldu & 3)) return DPD_E_UNSUPPORTED;
+    const int Q = (pairs * N + 31) / 32 * 32;       // the rows and their pad rows
+    // (the GEMMs address Xu, Pu and the activations with 32-bit byte offsets)
+    if (!fits_gemm_offsets((size_t)(KP - 32), (size_t)ldu) || !fits_gemm_offsets((size_t)slot_cap, (size_t)H) || !fits_gemm_offsets((size_t)Q, (size_t)H))
+        return DPD_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    // h1 -> act0, h2 -> act1, h3 -> act0: nothing is kept for a backward pass
+    if (int rc = fwd_over_slots(Xu, ldu, slot_cap, Xt, uid, cnt + 1, Pu, maskr, Q, KP, H, p, act0, act1, act0, y, pred, s, true)) return rc;
+    StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)pairs * N * 12.0 + pairs * 4.0);
+    DPD_LAUNCH(pair_mean_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, (const float*)pred, N, pairs, Dd);
     DPD_CHECK_LAUNCH();
     return 0;
 }

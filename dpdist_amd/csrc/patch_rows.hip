@@ -473,6 +473,7 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_lds_kernel(const float* __
 }
 
 #include "patch_rows_unique.h"      // the same gather over distinct windows (window_index_kernel, patch_rows_fwd_unique_kernel)
+#include "patch_rows_cross.h"       // ... for every cloud of one set against every query of another (cross_index_kernel, patch_rows_cross_kernel)
 
 // Backward as a gather (patch_rows_bwd.h): block (c, slice) owns a slice of the voxels of cloud c
 __global__ __launch_bounds__(256) void patch_rows_bwd_kernel(const float* __restrict__ dX, const int32_t* __restrict__ vox,
@@ -644,6 +645,83 @@ extern "C" int dpd_patch_rows_fwd_unique(const float* q, const float* fv, const 
     if (int rc2 = ensure_dyn_lds(lu_opt, (const void*)patch_rows_fwd_unique_kernel, lds)) return rc2;
     DPD_LAUNCH(patch_rows_fwd_unique_kernel, dim3(x_rows / 8 + C * kUqChunks), dim3(512), lds, (hipStream_t)stream, q, fv, X, x_rows, Xu, Q + 32, Xt, (const int32_t*)lu,
                (const int32_t*)first, (const int32_t*)ucount, uid, cnt, Q, N, Qb, m, k, KP, make_axis(m), ssq, kMfvSlices, mg_k, mg_kk);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- all-pairs distance matrix (patch_rows_cross.h) ----
+namespace {
+size_t cross_lds_bytes(int m, int KP) {
+    const size_t G = (size_t)m * m * m;
+    return G * dpd::kF * sizeof(float) + (size_t)(KP / 4) * sizeof(int2) + G * (sizeof(dpd::UqRow) + sizeof(int));
+}
+// THE shape predicate of the all-pairs engine (H <= 0: the decoder's width is not known to the caller): the shapes of the LDS form of
+// the distinct-window gather, and every matrix of a chunk addressable by the GEMM kernels
+bool cross_shape_ok(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
+    if (Ca_chunk <= 0 || Cb <= 0 || N <= 0 || (long)Cb * N > (1L << 24) || (long)Ca_chunk * Cb * N > (1L << 30)) return false;
+    if (m < 1 || m > 10 || k < 3 || k > 7 || !(k & 1) || KP != dpd_padded_width(k) || k * k * k * dpd::kF < KP - 32) return false;
+    const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
+    for (int x = 0; x < k * k * k; ++x)
+        if ((int)((x * mg_kk) >> 16) != x / (k * k) || (int)(((x % (k * k)) * mg_k) >> 16) != (x % (k * k)) / k) return false;
+    const size_t G = (size_t)m * m * m, qn = (size_t)Cb * N;
+    if (cross_lds_bytes(m, KP) > 128 * 1024) return false;
+    const size_t cap = ((size_t)Ca_chunk * (G < qn ? G : qn) + 31) / 32 * 32, rows_p = ((size_t)Ca_chunk * qn + 31) / 32 * 32;
+    if (!dpd::fits_gemm_offsets((size_t)(KP - 32), cap)) return false;
+    if (H > 0 && ((H & 63) || !dpd::fits_gemm_offsets(cap, (size_t)H) || !dpd::fits_gemm_offsets(rows_p, (size_t)H))) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int dpd_cross_slot_capacity(int Ca_chunk, int Cb, int N, int m) {
+    if (Ca_chunk <= 0 || Cb <= 0 || N <= 0 || m < 1 || m > 10) return 0;
+    const long G = (long)m * m * m, qn = (long)Cb * N;
+    const long cap = ((long)Ca_chunk * (G < qn ? G : qn) + 31) / 32 * 32;
+    return cap > 0x7fffffffL ? 0 : (int)cap;
+}
+
+extern "C" size_t dpd_cross_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
+    if (H <= 0 || !cross_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return 0;
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t cap = (size_t)dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
+    const size_t rows_p = ((size_t)Ca_chunk * Cb * N + 31) / 32 * 32;
+    // Xu, Xt, uid, maskr, cnt, Pu, two activation buffers, y, pred, Dd -- in this order, each 256-byte aligned
+    return al((size_t)(KP - 32) * cap * 4) + al(rows_p * 32 * 4) + 2 * al(rows_p * 4) + al(16) + al(cap * H * 4) + 2 * al(rows_p * H * 4) +
+           2 * al(rows_p * 3 * 4) + al((size_t)Ca_chunk * Cb * 4);
+}
+
+extern "C" int dpd_cross_index(const float* q, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox, int32_t* ucount,
+                               void* stream) {
+    using namespace dpd;
+    if (!q || !mask || !vox || !slot_of_vox || !ucount) return DPD_E_NULL;
+    if (Cb <= 0 || N <= 0 || (long)Cb * N > (1L << 24)) return DPD_E_DIM;
+    if (m < 1 || m > 10) return DPD_E_UNSUPPORTED;
+    StageProf prof(stream, DPD_STAGE_GATHER, (double)Cb * N * 20.0 + (double)m * m * m * 4.0);
+    DPD_LAUNCH(cross_index_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, q, Cb * N, m, make_axis(m), mask, vox, slot_of_vox, ucount);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_cross_gather(const float* q, const int32_t* vox, const float* mask, const int32_t* slot_of_vox, const int32_t* ucount,
+                                const float* fv, const float* ssq, int Ca_chunk, int Cb, int N, int m, int k, int KP, float* Xu, int ldu,
+                                float* Xt, int32_t* uid, float* maskr, int32_t* cnt, void* stream) {
+    using namespace dpd;
+    if (!q || !vox || !mask || !slot_of_vox || !ucount || !fv || !Xu || !Xt || !uid || !maskr || !cnt) return DPD_E_NULL;
+    if (Ca_chunk <= 0 || Cb <= 0 || N <= 0) return DPD_E_DIM;
+    if (!cross_shape_ok(Ca_chunk, Cb, N, m, k, KP, 0)) return DPD_E_UNSUPPORTED;
+    const size_t lds = cross_lds_bytes(m, KP);
+    const int QN = Cb * N, G = m * m * m, ucap = G < QN ? G : QN;
+    const int cap = dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
+    if (!cap || ldu < cap) return DPD_E_DIM;
+    if (!fits_gemm_offsets((size_t)(KP - 32), (size_t)ldu)) return DPD_E_UNSUPPORTED;
+    const int rows = Ca_chunk * QN, rows_p = (rows + 31) / 32 * 32;
+    const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
+    // algorithmic bytes: the surface vectors and the queries in; the windows (an upper bound: the slot capacity) and the rows' tails out
+    StageProf prof(stream, DPD_STAGE_GATHER,
+                   (double)Ca_chunk * G * kF * 4.0 + QN * 20.0 + (double)Ca_chunk * ucap * (KP - 32) * 4.0 + (double)rows_p * (32 * 4.0 + 8.0));
+    static LdsOptIn lx_opt;
+    if (int rc2 = ensure_dyn_lds(lx_opt, (const void*)patch_rows_cross_kernel, lds)) return rc2;
+    DPD_LAUNCH(patch_rows_cross_kernel, dim3(Ca_chunk * kCrossChunks), dim3(512), lds, (hipStream_t)stream, q, vox, mask, slot_of_vox, ucount, ucap,
+               fv, Xu, ldu, Xt, uid, maskr, cnt, Ca_chunk, QN, rows_p, m, k, KP, make_axis(m), ssq, kMfvSlices, mg_k, mg_kk);
     DPD_CHECK_LAUNCH();
     return 0;
 }

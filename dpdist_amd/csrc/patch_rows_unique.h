@@ -72,6 +72,69 @@ struct UqRow {
     int own;          // offset of the row's own voxel in the cloud's vector
     unsigned vbits;   // validity bits of the displacements: axis a, d -> bit 8a + d
 };
+// ---- pieces of the LDS form shared by the gathers over distinct windows (this kernel and patch_rows_cross_kernel) ----
+constexpr int kUqPre = 5;                                                     // m = 8: 2560 float4 of a cloud's vector = 5 per thread of 512
+// the first kUqPre float4 per thread of a cloud's Fisher vector, requested before anything else
+__device__ __forceinline__ void uq_prefetch(const float4* __restrict__ fvc, int nv, int tid, float4 (&pre)[kUqPre]) {
+#pragma unroll
+    for (int i = 0; i < kUqPre; ++i) {
+        const int idx = tid + 512 * i;
+        pre[i] = idx < nv ? fvc[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// the cloud's vector into LDS, scaled per channel when scaled (fv * scale: the products of the plain gather)
+__device__ __forceinline__ void uq_stage(float* s_fv, const float* s_sc, bool scaled, const float4* __restrict__ fvc, int nv, int tid,
+                                         const float4 (&pre)[kUqPre]) {
+    auto stage = [&](int idx, float4 x) {
+        if (scaled) {
+            const float4 sc = *reinterpret_cast<const float4*>(&s_sc[(idx % 5) * 4]);
+            x.x *= sc.x; x.y *= sc.y; x.z *= sc.z; x.w *= sc.w;
+        }
+        *reinterpret_cast<float4*>(s_fv + 4 * idx) = x;
+    };
+#pragma unroll
+    for (int i = 0; i < kUqPre; ++i)
+        if (tid + 512 * i < nv) stage(tid + 512 * i, pre[i]);
+    for (int idx = tid + 512 * kUqPre; idx < nv; idx += 512) stage(idx, fvc[idx]);
+}
+// unit table [U]: {offset in floats from the row's own voxel, d0 | d1 << 8 | d2 << 16 | kind << 24}; kind 0 window, 1 q - centre, 2 pad
+__device__ __forceinline__ void uq_build_table(int2* s_tab, int U, int m, int k, unsigned mg_k, unsigned mg_kk, int tid) {
+    const int E4 = k * k * k * (kF / 4), h = (k - 1) / 2;
+    for (int j = tid; j < U; j += 512) {
+        int2 e = make_int2(0, (j == E4 ? 1 : 2) << 24);
+        if (j < E4) {
+            const int nb = j / 5, part = j - 5 * nb;
+            const int d0 = (int)(((unsigned)nb * mg_kk) >> 16), r = nb - d0 * k * k;
+            const int d1 = (int)(((unsigned)r * mg_k) >> 16), d2 = r - d1 * k;
+            e = make_int2((((d0 - h) * m + (d1 - h)) * m + (d2 - h)) * kF + part * 4, d0 | (d1 << 8) | (d2 << 16));
+        }
+        s_tab[j] = e;
+    }
+}
+// window record of voxel (iy, ix, iz)
+__device__ __forceinline__ UqRow uq_record(int iy, int ix, int iz, int m, int k) {
+    const int h = (k - 1) / 2;
+    unsigned vb = 0;
+    for (int d = 0; d < k; ++d) {
+        if ((unsigned)(iy - h + d) < (unsigned)m) vb |= 1u << d;
+        if ((unsigned)(ix - h + d) < (unsigned)m) vb |= 1u << (8 + d);
+        if ((unsigned)(iz - h + d) < (unsigned)m) vb |= 1u << (16 + d);
+    }
+    return UqRow{((iy * m + ix) * m + iz) * kF, vb};
+}
+// float4 unit with table entry e of the row with record (rw, dq)
+__device__ __forceinline__ float4 uq_unit(const float* s_fv, const int2 e, const UqRow rw, const float4 dq) {
+    const int kind = e.y >> 24;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (kind == 0) {
+        if ((rw.vbits >> (e.y & 0xff)) & (rw.vbits >> (8 + ((e.y >> 8) & 0xff))) & (rw.vbits >> (16 + ((e.y >> 16) & 0xff))) & 1u)
+            v = *reinterpret_cast<const float4*>(s_fv + rw.own + e.x);
+    } else if (kind == 1) {
+        v = dq;
+    }
+    return v;
+}
+
 __global__ __launch_bounds__(512) void patch_rows_fwd_unique_kernel(const float* __restrict__ q, const float* __restrict__ fv,
                                                                     float* __restrict__ X, int x_rows, float* __restrict__ XuT, int ldu,
                                                                     float* __restrict__ Xt, const int32_t* __restrict__ lu,
@@ -81,7 +144,7 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_unique_kernel(const float*
                                                                     unsigned mg_k, unsigned mg_kk) {
     extern __shared__ __attribute__((aligned(16))) int2 s_tab4[];             // [KP/4] unit table, the scaled vector [G*kF] fp32, then per row of the cloud
     const int U = KP / 4, UW = U - 8;                                         // float4 units of a row; of its XuT part
-    const int G = m * m * m, h = (k - 1) / 2, GF = G * kF;
+    const int G = m * m * m, GF = G * kF;
     float* s_fv = reinterpret_cast<float*>(s_tab4 + U);
     float4* s_dq = reinterpret_cast<float4*>(s_fv + GF);                      // [N] (q - centre, 0)        (row blocks use 8 entries)
     UqRow* s_row = reinterpret_cast<UqRow*>(s_dq + N);                        // [N]
@@ -104,13 +167,8 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_unique_kernel(const float*
     }
     const float4* fvc = reinterpret_cast<const float4*>(fv + (size_t)cloud * GF);
     const int nv = GF / 4;
-    constexpr int PRE = 5;
-    float4 pre[PRE];
-#pragma unroll
-    for (int i = 0; i < PRE; ++i) {
-        const int idx = tid + 512 * i;
-        pre[i] = idx < nv ? fvc[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    float4 pre[kUqPre];
+    uq_prefetch(fvc, nv, tid, pre);
     if (tid < kF) s_sc[tid] = ssq ? fv_scale(ssq, nsl, cloud, tid) : 1.0f;
     // row records: the 8 rows of a row block, all N rows of a cloud block
     const int r_first = rowblk ? 8 * rg : cloud * N, r_count = rowblk ? 8 : N;
@@ -121,13 +179,7 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_unique_kernel(const float*
         const bool valid = (ix >= 0) && (iy >= 0) && (iz >= 0);
         if (!valid) { ix = 0; iy = 0; iz = 0; }
         s_dq[n] = make_float4(qx - ax.c[ix], qy - ax.c[iy], qz - ax.c[iz], 0.f);       // point_cloud - Centers (:491)
-        unsigned vb = 0;
-        for (int d = 0; d < k; ++d) {
-            if ((unsigned)(iy - h + d) < (unsigned)m) vb |= 1u << d;
-            if ((unsigned)(ix - h + d) < (unsigned)m) vb |= 1u << (8 + d);
-            if ((unsigned)(iz - h + d) < (unsigned)m) vb |= 1u << (16 + d);
-        }
-        s_row[n] = UqRow{((iy * m + ix) * m + iz) * kF, vb};
+        s_row[n] = uq_record(iy, ix, iz, m, k);
         if (!rowblk && first[r]) s_slotrow[lu[r]] = n;
     }
     if (!rowblk && tid < 64) {                    // one wave: slot counts of the clouds (integer sums: any order gives the same words)
@@ -146,43 +198,12 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_unique_kernel(const float*
         }
         if (tid == 0) { s_base[0] = before; s_base[1] = uab; s_base[2] = all; }
     }
-    const int E4 = k * k * k * (kF / 4);
-    for (int j = tid; j < U; j += 512) {
-        int2 e = make_int2(0, (j == E4 ? 1 : 2) << 24);
-        if (j < E4) {
-            const int nb = j / 5, part = j - 5 * nb;
-            const int d0 = (int)(((unsigned)nb * mg_kk) >> 16), r = nb - d0 * k * k;
-            const int d1 = (int)(((unsigned)r * mg_k) >> 16), d2 = r - d1 * k;
-            e = make_int2((((d0 - h) * m + (d1 - h)) * m + (d2 - h)) * kF + part * 4, d0 | (d1 << 8) | (d2 << 16));
-        }
-        s_tab4[j] = e;
-    }
+    uq_build_table(s_tab4, U, m, k, mg_k, mg_kk, tid);
     __syncthreads();
-    auto stage = [&](int idx, float4 x) {
-        if (ssq) {
-            const float4 sc = *reinterpret_cast<const float4*>(&s_sc[(idx % 5) * 4]);
-            x.x *= sc.x; x.y *= sc.y; x.z *= sc.z; x.w *= sc.w;
-        }
-        *reinterpret_cast<float4*>(s_fv + 4 * idx) = x;
-    };
-#pragma unroll
-    for (int i = 0; i < PRE; ++i)
-        if (tid + 512 * i < nv) stage(tid + 512 * i, pre[i]);
-    for (int idx = tid + 512 * PRE; idx < nv; idx += 512) stage(idx, fvc[idx]);
+    uq_stage(s_fv, s_sc, ssq != nullptr, fvc, nv, tid, pre);
     __syncthreads();
     // float4 unit j of the row with record (rw, dq)
-    auto unit = [&](int j, const UqRow rw, const float4 dq) {
-        const int2 e = s_tab4[j];
-        const int kind = e.y >> 24;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (kind == 0) {
-            if ((rw.vbits >> (e.y & 0xff)) & (rw.vbits >> (8 + ((e.y >> 8) & 0xff))) & (rw.vbits >> (16 + ((e.y >> 16) & 0xff))) & 1u)
-                v = *reinterpret_cast<const float4*>(s_fv + rw.own + e.x);
-        } else if (kind == 1) {
-            v = dq;
-        }
-        return v;
-    };
+    auto unit = [&](int j, const UqRow rw, const float4 dq) { return uq_unit(s_fv, s_tab4[j], rw, dq); };
     const int wv = tid >> 6, lane = tid & 63;
     if (rowblk) {                                 // wave = row
         const int row = 8 * rg + wv;

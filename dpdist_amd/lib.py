@@ -65,6 +65,11 @@ SIGNATURES = {
     "dpd_patch_rows_fwd_unique": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dpd_decoder_fwd_unique": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, POINTER(DecoderParams)] + [c_void_p] * 6),
+    "dpd_cross_slot_capacity": (c_int, [c_int] * 4),
+    "dpd_cross_workspace_bytes": (c_size_t, [c_int] * 7),
+    "dpd_cross_index": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
+    "dpd_cross_gather": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 5),
+    "dpd_decoder_fwd_cross": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int] * 4 + [POINTER(DecoderParams)] + [c_void_p] * 6),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

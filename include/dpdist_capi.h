@@ -185,6 +185,49 @@ int dpd_decoder_fwd_unique(const float* Xu, const float* Xt, const int32_t* uid,
                            int Q, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y,
                            float* pred, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * All-pairs distance matrix (DPD_F32, forward only): every cloud of a set A [Ca,N,3] against every cloud of a set B [Cb,N,3],
+ *   D_AB[i,j] = mean_n pred(surface A_i ; query B_j[n])[0]
+ * -- what get_emb_and_concat / get_pc_grid_binary_mask_from_centers (utils/dpdist_util.py:434-511), the decoder (:513-544), relu6/3 and
+ * the mask (:690-698) and the mean of loss_pred (:976-979) give for the pair (A_i, B_j) -- without building the Ca Cb pairs: the
+ * encoder runs once per cloud, and because the voxel of a query does not depend on the surface cloud, layer 1 contracts its first
+ * KP - 32 columns once per (surface cloud, occupied voxel) instead of once per row.  The other direction is the same calls with the
+ * sets swapped.  The caller owns all memory; the host never reads a device word.
+ *
+ * dpd_cross_index: q [Cb,N,3] -> vox [Cb N], mask [Cb N] (the cell rule and the bits of dpd_patch_rows_fwd; a masked query uses
+ *   voxel 0's window), slot_of_vox [m^3] (dense slot of every occupied voxel in ascending voxel id, else -1) and ucount [1] = U, the
+ *   number of occupied voxels (<= min(m^3, Cb N)).  One launch, integer only, deterministic.  m <= 10.
+ * dpd_cross_slot_capacity: the slot capacity of a chunk of Ca_chunk surface clouds, Ca_chunk * min(m^3, Cb N) rounded up to 32
+ *   (0 = refused shape): the columns of Xu and the rows of Pu are sized by it.
+ * dpd_cross_gather: Ca_chunk surface clouds fv [Ca_chunk, m^3, 20] (ssq as in dpd_patch_rows_fwd_scaled, NULL = fv is normalised)
+ *   against those queries; rows are ordered (i, j, n), rows = Ca_chunk Cb N, rows_p = rows rounded up to 32:
+ *     Xu [KP - 32, ldu]  K-MAJOR: column i U + s = columns [0, KP - 32) of the window of surface i around the voxel of slot s, the bits
+ *                        dpd_patch_rows_fwd_scaled writes for such a row; nothing beyond the Ca_chunk U live columns is written;
+ *     Xt [rows_p, 32]    columns [KP - 32, KP) of every row (the window's last values, q - centre, the zero pad);
+ *     uid [rows_p]       i U + slot_of_vox[vox(j, n)];   maskr [rows_p] the mask of the row's query;
+ *     cnt [4]            {U, Ca_chunk U, 0, 0}: cnt[1] is the live slot count the decoder reads on the device;
+ *   pad rows (rows <= r < rows_p) get uid 0, Xt 0, mask 0.  One launch.  Needs k >= 3, KP == dpd_padded_width(k), m <= 10,
+ *   ldu >= dpd_cross_slot_capacity(...) (else DPD_E_UNSUPPORTED / DPD_E_DIM).
+ * dpd_decoder_fwd_cross: the launches of dpd_decoder_fwd_unique on those buffers with an explicit slot capacity (Pu [slot_cap, H],
+ *   ldu = row stride of Xu) -- same bits of y and pred [rows_p, 3] as dpd_decoder_fwd on the plain rows -- with layers 1 to 3
+ *   written into two ping-pong activation buffers act0, act1 [rows_p, H], then Dd [pairs] (pairs = Ca_chunk Cb) = the mean of
+ *   pred[:, 0] over the N rows of each pair, in one fixed summation order that does not depend on the chunk.  Pad rows never enter Dd.
+ *   Needs H % 64 == 0, KP % 32 == 0, slot_cap % 4 == 0, ldu % 4 == 0.
+ * dpd_cross_workspace_bytes: the bytes of one chunk's buffers -- Xu (ldu = the slot capacity), Xt, uid, maskr, cnt, Pu, act0, act1, y,
+ *   pred, Dd, in this order, each rounded up to 256 bytes; 0 for a shape the entries refuse.
+ * Size limit: the GEMMs address their matrices with 32-bit byte offsets, so Xu [KP - 32, ldu], Pu [slot_cap, H] and the activation
+ *   buffers [rows_p, H] must each stay below 4 GiB (DPD_E_UNSUPPORTED from the gather and the decoder, 0 from the workspace report):
+ *   take fewer surface clouds per chunk.                                                                                          */
+int dpd_cross_slot_capacity(int Ca_chunk, int Cb, int N, int m);
+size_t dpd_cross_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H);
+int dpd_cross_index(const float* q, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox, int32_t* ucount, void* stream);
+int dpd_cross_gather(const float* q, const int32_t* vox, const float* mask, const int32_t* slot_of_vox, const int32_t* ucount,
+                     const float* fv, const float* ssq, int Ca_chunk, int Cb, int N, int m, int k, int KP, float* Xu, int ldu, float* Xt,
+                     int32_t* uid, float* maskr, int32_t* cnt, void* stream);
+int dpd_decoder_fwd_cross(const float* Xu, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
+                          const float* maskr, int pairs, int N, int KP, int H, const dpd_decoder_params* p, float* act0, float* act1,
+                          float* y, float* pred, float* Dd, void* stream);
+
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in
  *               dpd_decoder_fwd / dpd_decoder_bwd_data (ws may be NULL);
@@ -646,7 +689,8 @@ int dpd_prof_collect(double* total_ms, double* total_flops);
 int dpd_prof_collect_form(int form, double* total_ms, double* total_flops);
 /* dpd_prof_enable(2) additionally brackets the bandwidth-bound kernels of the step and records their ALGORITHMIC HBM bytes (every
  * input read once, every output written once) by stage: 1 3DmFV encoder, 2 window gather, 3 fused output layer (+ loss + its backward),
- * 4 optimizer, 5 small-gradient reduction, 6 weight copies (transposes / operand planes).  Returns the launches of that stage since
+ * 4 optimizer, 5 small-gradient reduction, 6 weight copies (transposes / operand planes), 7 the finish launch of layer 1 over distinct
+ * windows (dpd_decoder_fwd_cross only, which also records its output layer under 3 and its pair means under 5).  Returns the launches of that stage since
  * dpd_prof_enable(2) and fills their summed duration [ms] and bytes; dpd_prof_collect keeps counting GEMM launches only.          */
 int dpd_prof_collect_stage(int stage, double* total_ms, double* total_bytes);
 

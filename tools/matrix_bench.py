@@ -1,0 +1,123 @@
+"""The all-pairs distance matrix against the same matrix through the pair path, at Ca = Cb = 32 clouds of 64 points, decoder width 1024,
+on synth.s2_modelnet_shaped clouds:
+
+    cross   dpdist_amd.dpdist_matrix (each set encoded once, layer 1 over Ca * U slots, no row matrix)
+    pairs   DPDistModel.forward under no_grad on hand-tiled pairs, 128 pairs (16384 rows per launch) at a time, the mean over the
+            points of pred_listAB / pred_listBA[..., 0]
+
+    python tools/matrix_bench.py            # one JSON line
+
+The two forms alternate, five rounds after a warm-up, each timed with a device event pair; the two matrices must agree within the
+fp32 forward bar of the tests (1e-4 absolute).  The per-kernel split comes from a further pass of each form under the library's in-stream
+stage profiler (event pairs around every launch: dpd_prof_enable(2))."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dpdist_amd import dpdist_matrix, synth  # noqa: E402
+from dpdist_amd import lib as L  # noqa: E402
+from dpdist_amd.model import DPDistModel  # noqa: E402
+
+STAGES = {1: "encoder", 2: "index_and_gather", 3: "output_layer", 5: "pair_mean", 7: "layer1_finish"}
+
+
+def pair_matrix(model, A, B, batch=128):
+    """(D, D_AB, D_BA) through the pair path: pair p = i * Cb + j is (A_i, B_j)"""
+    Ca, Cb, N = A.shape[0], B.shape[0], A.shape[1]
+    a_t = A[:, None].expand(-1, Cb, -1, -1).reshape(Ca * Cb, N, 3)
+    b_t = B[None].expand(Ca, -1, -1, -1).reshape(Ca * Cb, N, 3)
+    ab, ba = [], []
+    with torch.no_grad():
+        for p0 in range(0, Ca * Cb, batch):
+            ps = model(a_t[p0:p0 + batch].contiguous(), b_t[p0:p0 + batch].contiguous())
+            ab.append(ps["pred_listAB"][:, :, 0, 0].mean(1))
+            ba.append(ps["pred_listBA"][:, :, 0, 0].mean(1))
+    d_ab, d_ba = torch.cat(ab).view(Ca, Cb), torch.cat(ba).view(Ca, Cb)
+    return (d_ab + d_ba) / 2, d_ab, d_ba
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def kernel_split(lib, fn):
+    """ms per call of `fn` by kind of launch, from the library's in-stream profiler"""
+    torch.cuda.synchronize()
+    lib.dpd_prof_enable(2)
+    fn()
+    torch.cuda.synchronize()
+    out = {}
+    ms, x = ctypes.c_double(0), ctypes.c_double(0)
+    for form, name in ((0, "gemm_rows"), (1, "gemm_slots")):
+        n = lib.dpd_prof_collect_form(form, ctypes.byref(ms), ctypes.byref(x))
+        if n > 0:
+            out[name] = {"launches": n, "ms": round(ms.value, 4)}
+            if form == 0:       # (the slot product records its flops by the slot CAPACITY, not the live count)
+                out[name]["tflops"] = round(x.value / (ms.value * 1e-3) / 1e12, 1)
+    for tag, name in STAGES.items():
+        n = lib.dpd_prof_collect_stage(tag, ctypes.byref(ms), ctypes.byref(x))
+        if n > 0:
+            out[name] = {"launches": n, "ms": round(ms.value, 4)}
+    lib.dpd_prof_enable(0)
+    out["sum_ms"] = round(sum(v["ms"] for v in out.values()), 4)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clouds", type=int, default=32)
+    ap.add_argument("--points", type=int, default=64)
+    ap.add_argument("--width", type=int, default=1024)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--max-rows", type=int, default=16384)
+    a = ap.parse_args()
+    C, N, H = a.clouds, a.points, a.width
+    dev = torch.device("cuda:0")
+    lib = L.load()
+    A = torch.tensor(synth.s2_modelnet_shaped(C, N, 100)[0], device=dev)
+    B = torch.tensor(synth.s2_modelnet_shaped(C, N, 101)[1], device=dev)
+    model = DPDistModel(Embedding_Size=512, k=5, localSNmlp=(H,) * 3, sigma3dmfv=0.125, device=dev)
+    model.load_tf_state_dict(synth.make_weights("wide", mlp=(H,) * 3))
+    cross = lambda: dpdist_matrix(model, A, B, max_rows=a.max_rows, return_directed=True)   # noqa: E731
+    pairs = lambda: pair_matrix(model, A, B)                                                # noqa: E731
+    got, want = cross(), pairs()
+    torch.cuda.synchronize()
+    err = [float((x.double() - y.double()).abs().max()) for x, y in zip(got, want)]
+    if max(err) > 1e-4:
+        raise SystemExit("the two forms disagree: max |D - D_pairs|, AB, BA = %s" % err)
+    for _ in range(2):
+        cross(), pairs()
+    t = {"cross": [], "pairs": []}
+    for _ in range(a.rounds):
+        t["cross"].append(timed(cross))
+        t["pairs"].append(timed(pairs))
+    slots = {}
+    for name, q in (("AB", B), ("BA", A)):                      # the queries of direction AB are the clouds of B
+        ix = [torch.empty(n, device=dev, dtype=dt) for n, dt in ((C * N, torch.float32), (C * N, torch.int32), (512, torch.int32), (1, torch.int32))]
+        L.check(lib.dpd_cross_index(L.ptr(q), C, N, 8, *[L.ptr(x) for x in ix], L.cur_stream()), "dpd_cross_index")
+        slots[name] = {"U": int(ix[3][0]), "slots": C * int(ix[3][0]), "rows": C * C * N}
+    stat = lambda v: {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}   # noqa: E731
+    res = {"shape": {"Ca": C, "Cb": C, "N": N, "H": H, "m": 8, "k": 5, "max_rows": a.max_rows, "pair_batch": 128},
+           "device": torch.cuda.get_device_name(0), "rounds": a.rounds,
+           "cross": stat(t["cross"]), "pairs": stat(t["pairs"]),
+           "speedup_median": round(float(np.median(t["pairs"]) / np.median(t["cross"])), 3),
+           "max_abs_diff": {"D": err[0], "D_AB": err[1], "D_BA": err[2]}, "live_slots": slots,
+           "kernels": {"cross": kernel_split(lib, cross), "pairs": kernel_split(lib, pairs)},
+           "note": "kernels: one profiled call of each form (event pairs around every launch add ~2 us between launches); the pair path's "
+                   "output layer and its torch glue (tiling, means) are not bracketed"}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
