@@ -16,7 +16,7 @@ def __getattr__(name):
     if name in ("get_model", "get_loss", "DPDistModel", "DPDistLoss", "placeholder_inputs"):
         from . import model
         return getattr(model, name)
-    if name == "dpdist_matrix":
+    if name in ("dpdist_matrix", "DPDistMatrix"):
         from . import pairwise
-        return pairwise.dpdist_matrix
+        return getattr(pairwise, name)
     raise AttributeError(name)

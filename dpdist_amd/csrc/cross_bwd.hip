@@ -1,0 +1,347 @@
+// Backward of the ALL-PAIRS distance matrix (exact fp32, as-loss mode: the decoder is frozen, gradients go to the two cloud sets;
+// include/dpdist_capi.h: dpd_cross_invert, dpd_cross_bwd, dpd_cross_bwd_workspace_bytes).
+//
+// The forward (patch_rows_cross.h) runs layer 1 once per (surface cloud, occupied voxel) slot because the voxel of a query does not
+// depend on the surface cloud.  The layer-1 data gradient is linear, so the same holds backwards: the rows g1 [rows_p, H] of all
+// queries that share a slot are SUMMED first (gs [slot_cap, H]) and multiplied by W1p^T once per slot (dXs [slot_cap, KP]); the window
+// columns of dXs are then scattered to the surface's Fisher vector by a gather over the slots, and only the three q - centre columns
+// are taken per row (dq [rows, 3], a dot product with three rows of W1p).  Rows are ordered (i, j, n) as in the forward.
+// Everything below is deterministic: no atomics on floats, one summation order per output element, whatever the launch holds.
+#include "common.h"
+#include "gemm_host.h"
+
+namespace dpd {
+
+constexpr int kCF = DPD_FV_CHANNELS;
+constexpr int kCrossMaxH = 4096;      // slot_sum_kernel: one wave per 256 columns, at most 16 waves
+
+// One workgroup: the queries sorted by slot (a stable counting sort: ascending query id inside a slot), the start offset of every slot
+// and the voxel of every slot.  Counts by integer LDS atomics (any order gives the same counts), an exclusive prefix over the voxels,
+// then wave 0 places the queries 64 at a time in query order: lanes of one slot take consecutive positions by their rank among the
+// lanes of that slot (a ballot), so the order inside a slot is the query id.  Integer only, one order.
+//   slot_start [m^3 + 1]  start of slot s in qlist for s < U, QN for s >= U (so slot s holds [slot_start[s], slot_start[s + 1]))
+//   qlist [QN]            query ids sorted by (slot, query id)
+//   slot_vox [m^3]        voxel id of slot s for s < U, -1 for s >= U
+__global__ __launch_bounds__(1024) void cross_invert_kernel(const int32_t* __restrict__ vox, const int32_t* __restrict__ slot_of_vox,
+                                                            const int32_t* __restrict__ ucount, int QN, int G,
+                                                            int32_t* __restrict__ slot_start, int32_t* __restrict__ qlist,
+                                                            int32_t* __restrict__ slot_vox) {
+    __shared__ int s_cnt[1024];      // per voxel: the count, then the running position of the voxel's slot
+    __shared__ int s_wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    s_cnt[tid] = 0;
+    __syncthreads();
+    for (int r = tid; r < QN; r += 1024) {
+        int v = vox[r];
+        if ((unsigned)v >= (unsigned)G) v = 0;
+        atomicAdd(&s_cnt[v], 1);
+    }
+    __syncthreads();
+    // exclusive prefix of the counts in voxel order (= slot order: the slots are the occupied voxels in ascending voxel id)
+    const int c = s_cnt[tid];
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < 16; ++w) before += (w < wave) ? s_wsum[w] : 0;
+    const int start = before + incl - c;
+    __syncthreads();
+    s_cnt[tid] = start;
+    const int U = min(max(ucount[0], 0), G);
+    if (tid < G) {
+        const int sl = slot_of_vox[tid];
+        if (sl >= 0 && sl < U) { slot_start[sl] = start; slot_vox[sl] = tid; }
+    }
+    if (tid >= U && tid < G) slot_vox[tid] = -1;
+    if (tid >= U && tid <= G) slot_start[tid] = QN;
+    __syncthreads();
+    if (wave != 0) return;
+    volatile int* pos_of = s_cnt;      // written by one lane, read by others of the same wave in the next round
+    for (int r0 = 0; r0 < QN; r0 += 64) {
+        const int r = r0 + lane;
+        const bool live = r < QN;
+        int v = live ? vox[r] : 0;
+        if ((unsigned)v >= (unsigned)G) v = 0;
+        unsigned long long todo = __ballot(live);
+        int rank = 0, total = 0;
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int v0 = __shfl(v, leader, 64);
+            const unsigned long long same = __ballot(live && v == v0);
+            if (live && v == v0) {
+                rank = __popcll(same & ((1ull << lane) - 1ull));
+                total = __popcll(same);
+            }
+            todo &= ~same;
+        }
+        if (live) {
+            const int pos = pos_of[v] + rank;
+            if ((unsigned)pos < (unsigned)QN) qlist[pos] = r;      // (the counts bound every position)
+        }
+        // one lane per voxel advances its position (LDS is in order inside one wave)
+        if (live && rank == total - 1) pos_of[v] = pos_of[v] + total;
+    }
+}
+
+// Upstream spread, the inverse of pair_mean_kernel: dpred[r] = (Gd[pair of r] / N, 0, 0) for the real rows, 0 for the pad rows
+__global__ __launch_bounds__(256) void cross_spread_kernel(const float* __restrict__ Gd, int N, int rows, int rows_p, float* __restrict__ dpred) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows_p) return;
+    const float v = r < rows ? Gd[r / N] / (float)N : 0.f;
+    dpred[(size_t)r * 3] = v;
+    dpred[(size_t)r * 3 + 1] = 0.f;
+    dpred[(size_t)r * 3 + 2] = 0.f;
+}
+
+// Slot sum + query route: g1 [rows_p, H] is streamed once.  Workgroup t < Ca U owns slot (i, s) = (t / U, t % U): wave w owns the
+// columns [256 w, 256 w + 256), lane l the float4 at 256 w + 4 l.  For every query of the slot's list, in list order:
+//   gs[t, :] += g1[(i, qn), :]                                  (one chain per element, list order)
+//   dq[(i, qn), c] = sum_w wave_sum( g1[(i, qn), cols of w] . W1p[E + c, cols of w] ),  c = 0..2   (fixed tree per wave, waves ascending)
+// Workgroups Ca U <= t < slot_cap write ZERO rows of gs: the slot product runs over the capacity.
+// gs = NULL: the surface set needs no gradient (only dq); dq = NULL: the query set needs none (only gs).
+constexpr int kSlotRows = 32;         // rows between two exchanges of the waves' partial dot products
+__global__ __launch_bounds__(1024) void slot_sum_kernel(const float* __restrict__ g1, const int32_t* __restrict__ cnt,
+                                                        const int32_t* __restrict__ slot_start, const int32_t* __restrict__ qlist,
+                                                        const float* __restrict__ Wq /* W1p + E H: three rows */, int Ca, int QN, int H, int ucap,
+                                                        float* __restrict__ gs, float* __restrict__ dq) {
+    __shared__ float s_part[kSlotRows][16][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int U = min(max(cnt[0], 0), ucap);
+    const int t = blockIdx.x;
+    const int col = 256 * wave + 4 * lane;
+    const bool has = col < H;
+    if (t >= Ca * U) {
+        if (gs && has) *reinterpret_cast<float4*>(gs + (size_t)t * H + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int i = t / U, s = t % U;
+    const int b = min(max(slot_start[s], 0), QN), e = min(max(slot_start[s + 1], b), QN);
+    float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, acc = w0;
+    if (dq && has) {
+        w0 = *reinterpret_cast<const float4*>(Wq + col);
+        w1 = *reinterpret_cast<const float4*>(Wq + (size_t)H + col);
+        w2 = *reinterpret_cast<const float4*>(Wq + 2 * (size_t)H + col);
+    }
+    for (int p0 = b; p0 < e; p0 += kSlotRows) {
+        const int np = min(kSlotRows, e - p0);
+        for (int p = 0; p < np; ++p) {
+            int qn = qlist[p0 + p];
+            qn = min(max(qn, 0), QN - 1);
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (has) x = *reinterpret_cast<const float4*>(g1 + ((size_t)i * QN + qn) * H + col);
+            acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+            if (dq) {
+                const float d0 = wave_sum(((x.x * w0.x + x.y * w0.y) + x.z * w0.z) + x.w * w0.w);
+                const float d1 = wave_sum(((x.x * w1.x + x.y * w1.y) + x.z * w1.z) + x.w * w1.w);
+                const float d2 = wave_sum(((x.x * w2.x + x.y * w2.y) + x.z * w2.z) + x.w * w2.w);
+                if (lane == 0) { s_part[p][wave][0] = d0; s_part[p][wave][1] = d1; s_part[p][wave][2] = d2; }
+            }
+        }
+        if (dq) {
+            __syncthreads();
+            for (int x = threadIdx.x; x < np * 3; x += blockDim.x) {
+                const int p = x / 3, c = x % 3;
+                float d = s_part[p][0][c];
+                for (int w = 1; w < nw; ++w) d += s_part[p][w][c];
+                int qn = qlist[p0 + p];
+                qn = min(max(qn, 0), QN - 1);
+                dq[((size_t)i * QN + qn) * 3 + c] = d;
+            }
+            __syncthreads();
+        }
+    }
+    if (gs && has) *reinterpret_cast<float4*>(gs + (size_t)t * H + col) = acc;
+}
+
+// Window scatter over the slots, as a gather (the form of patch_rows_bwd.h): workgroup (i, slice) owns a slice of the voxels of surface
+// i and, for every (voxel, float4 channel group), sums that window column of every slot of the surface whose window covers the voxel,
+// in ascending slot order.  A voxel outside the grid has no item: zero padding at the border.  U comes from device memory.  Every item
+// is computed by ONE thread from the same loads in the same order whatever the launch shape is.
+__global__ __launch_bounds__(256) void cross_scatter_kernel(const float* __restrict__ dXs, const int32_t* __restrict__ cnt,
+                                                            const int32_t* __restrict__ slot_vox, float* __restrict__ dfv, int m, int k, int KP,
+                                                            int ucap, int slices) {
+    __shared__ int s_vox[1024];       // packed voxel coordinates of the slots (m <= 10: at most 1000)
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x / slices, sl = blockIdx.x % slices;
+    const int G = m * m * m, h = (k - 1) / 2;
+    const int U = min(min(max(cnt[0], 0), ucap), 1024);
+    for (int n = tid; n < U; n += 256) {
+        int v = slot_vox[n];
+        if ((unsigned)v >= (unsigned)G) v = 0;
+        s_vox[n] = (v / (m * m)) | (((v / m) % m) << 8) | ((v % m) << 16);
+    }
+    __syncthreads();
+    const int gper = (G + slices - 1) / slices;
+    const int gbeg = sl * gper, gend = min(G, gbeg + gper);
+    const float* dXc = dXs + (size_t)c * U * KP;
+    for (int item = tid; item < (gend - gbeg) * 5; item += 256) {
+        const int g = gbeg + item / 5, part = item % 5;
+        const int g0 = g / (m * m) + h, g1 = (g / m) % m + h, g2 = g % m + h;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int n0 = 0; n0 < U; n0 += 64) {
+            unsigned long long hm = 0;
+            const int lim = min(64, U - n0);
+            for (int j = 0; j < lim; ++j) {
+                const int pv = s_vox[n0 + j];
+                const int d0 = g0 - (pv & 255), d1 = g1 - ((pv >> 8) & 255), d2 = g2 - (pv >> 16);
+                if ((unsigned)d0 < (unsigned)k && (unsigned)d1 < (unsigned)k && (unsigned)d2 < (unsigned)k) hm |= 1ull << j;
+            }
+            while (__any(hm != 0)) {
+                float4 x[16];
+                bool hit[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    hit[j] = hm != 0;
+                    const int bit = hit[j] ? __ffsll((long long)hm) - 1 : 0;
+                    hm = hit[j] ? (hm & (hm - 1)) : 0;
+                    const int n = n0 + bit;
+                    const int pv = s_vox[n];
+                    const int d0 = g0 - (pv & 255), d1 = g1 - ((pv >> 8) & 255), d2 = g2 - (pv >> 16);
+                    const size_t off = hit[j] ? (size_t)n * KP + ((d0 * k + d1) * k + d2) * kCF + part * 4 : 0;
+                    x[j] = *reinterpret_cast<const float4*>(dXc + off);
+                }
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    acc.x = hit[j] ? acc.x + x[j].x : acc.x; acc.y = hit[j] ? acc.y + x[j].y : acc.y;
+                    acc.z = hit[j] ? acc.z + x[j].z : acc.z; acc.w = hit[j] ? acc.w + x[j].w : acc.w;
+                }
+            }
+        }
+        *reinterpret_cast<float4*>(dfv + ((size_t)c * G + g) * kCF + part * 4) = acc;
+    }
+}
+
+// Query-route reduction: gQ[j, n, c] = gQ[j, n, c] + dq[(0, j, n), c] + dq[(1, j, n), c] + ... in ascending surface: the chain goes on
+// from the accumulated value, so a chunk boundary changes no bit (the caller zeroes gQ before the first chunk).
+__global__ __launch_bounds__(256) void cross_qreduce_kernel(const float* __restrict__ dq, int Ca, int QN3, float* __restrict__ gQ) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= QN3) return;
+    float acc = gQ[e];
+    for (int i = 0; i < Ca; ++i) acc = acc + dq[(size_t)i * QN3 + e];
+    gQ[e] = acc;
+}
+
+}  // namespace dpd
+
+namespace {
+inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+// THE shape predicate of the all-pairs backward: a chunk the forward takes (dpd_cross_workspace_bytes is cross_shape_ok, patch_rows.hip)
+// whose slot product dXs [slot_cap, KP] is addressable by the GEMM kernels, at a width slot_sum_kernel covers
+bool cross_bwd_shape_ok(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
+    if (H <= 0 || H > dpd::kCrossMaxH || (H & 63)) return false;
+    if (!dpd_cross_workspace_bytes(Ca_chunk, Cb, N, m, k, KP, H)) return false;
+    const size_t cap = (size_t)dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
+    return cap && dpd::fits_gemm_offsets(cap, (size_t)KP);
+}
+}  // namespace
+
+extern "C" size_t dpd_cross_bwd_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
+    if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return 0;
+    const size_t cap = (size_t)dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
+    const size_t rows_p = ((size_t)Ca_chunk * Cb * N + 31) / 32 * 32;
+    const size_t G = (size_t)m * m * m;
+    // Xu, Xt, uid, maskr, cnt, Pu, h1, h2, h3, y, pred | dpred, dy, ga, gb, dq, gs, dXs, dfv -- in this order, each 256-byte aligned
+    return al256((size_t)(KP - 32) * cap * 4) + al256(rows_p * 32 * 4) + 2 * al256(rows_p * 4) + al256(16) + al256(cap * H * 4) +
+           3 * al256(rows_p * H * 4) + 2 * al256(rows_p * 12) +
+           2 * al256(rows_p * 12) + 2 * al256(rows_p * H * 4) + al256(rows_p * 12) + al256(cap * H * 4) + al256(cap * (size_t)KP * 4) +
+           al256((size_t)Ca_chunk * G * dpd::kCF * 4);
+}
+
+extern "C" int dpd_cross_invert(const int32_t* vox, const int32_t* slot_of_vox, const int32_t* ucount, int Cb, int N, int m,
+                                int32_t* slot_start, int32_t* qlist, int32_t* slot_vox, void* stream) {
+    using namespace dpd;
+    if (!vox || !slot_of_vox || !ucount || !slot_start || !qlist || !slot_vox) return DPD_E_NULL;
+    if (Cb <= 0 || N <= 0 || (long)Cb * N > (1L << 24)) return DPD_E_DIM;
+    if (m < 1 || m > 10) return DPD_E_UNSUPPORTED;
+    StageProf prof(stream, DPD_STAGE_GATHER, (double)Cb * N * 8.0 + (double)m * m * m * 12.0);
+    DPD_LAUNCH(cross_invert_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, vox, slot_of_vox, ucount, Cb * N, m * m * m, slot_start, qlist,
+               slot_vox);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_cross_slot_sum(const float* g1, const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const float* W1p,
+                                  int Ca_chunk, int Cb, int N, int m, int k, int KP, int H, int slot_cap, float* gs, float* dq, void* stream) {
+    using namespace dpd;
+    if (!g1 || !cnt || !slot_start || !qlist || (!gs && !dq) || (dq && !W1p)) return DPD_E_NULL;
+    if (Ca_chunk <= 0 || Cb <= 0 || N <= 0 || slot_cap <= 0) return DPD_E_DIM;
+    if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return DPD_E_UNSUPPORTED;
+    if (slot_cap != dpd_cross_slot_capacity(Ca_chunk, Cb, N, m)) return DPD_E_DIM;
+    const int QN = Cb * N, G = m * m * m, ucap = G < QN ? G : QN;
+    const int rows = Ca_chunk * QN;
+    StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)rows * H * 4.0 + (gs ? (double)slot_cap * H * 4.0 : 0.0) + (dq ? rows * 12.0 : 0.0) + QN * 4.0);
+    // with gs = NULL only the live slots matter, but the live count is a device word: the dead workgroups return at once
+    DPD_LAUNCH(slot_sum_kernel, dim3(slot_cap), dim3(64 * ((H + 255) / 256)), 0, (hipStream_t)stream, g1, cnt, slot_start, qlist,
+               W1p ? W1p + (size_t)(k * k * k * kCF) * H : nullptr, Ca_chunk, QN, H, ucap, gs, dq);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_cross_scatter(const float* dXs, const int32_t* cnt, const int32_t* slot_vox, int Ca_chunk, int Cb, int N, int m, int k,
+                                 int KP, float* dfv, void* stream) {
+    using namespace dpd;
+    if (!dXs || !cnt || !slot_vox || !dfv) return DPD_E_NULL;
+    if (Ca_chunk <= 0 || Cb <= 0 || N <= 0) return DPD_E_DIM;
+    if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, 64)) return DPD_E_UNSUPPORTED;
+    const int QN = Cb * N, G = m * m * m, ucap = G < QN ? G : QN;
+    const int slices = (G * 5 + 255) / 256;      // one (voxel, channel group) item per thread
+    StageProf prof(stream, DPD_STAGE_GATHER, (double)Ca_chunk * ucap * (k * k * k * kCF) * 4.0 + (double)Ca_chunk * G * kCF * 4.0);
+    DPD_LAUNCH(cross_scatter_kernel, dim3(Ca_chunk * slices), dim3(256), 0, (hipStream_t)stream, dXs, cnt, slot_vox, dfv, m, k, KP, ucap, slices);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y, const float* h1, const float* h2, const float* h3,
+                             const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox, int Ca_chunk, int Cb,
+                             int N, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dpred, float* dy, float* ga,
+                             float* gb, float* dq, float* gs, float* dXs, float* dfv, float* gQ, void* stream) {
+    using namespace dpd;
+    const bool surface = dfv != nullptr, query = gQ != nullptr;
+    if (!Gd || !maskr || !y || !h1 || !h2 || !h3 || !cnt || !slot_start || !qlist || !p || !dpred || !dy || !ga || !gb) return DPD_E_NULL;
+    if (!surface && !query) return DPD_E_NULL;
+    if (surface && (!slot_vox || !gs || !dXs || !p->W1pT)) return DPD_E_NULL;
+    if (query && (!dq || !p->W1p)) return DPD_E_NULL;
+    if (!p->W2 || !p->W3 || !p->W4 || !p->W1p) return DPD_E_NULL;
+    if (Ca_chunk <= 0 || Cb <= 0 || N <= 0 || slot_cap <= 0) return DPD_E_DIM;
+    if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return DPD_E_UNSUPPORTED;
+    if (slot_cap != dpd_cross_slot_capacity(Ca_chunk, Cb, N, m)) return DPD_E_DIM;
+    hipStream_t s = (hipStream_t)stream;
+    const int QN = Cb * N, rows = Ca_chunk * QN, rows_p = (rows + 31) / 32 * 32;
+    // 2. upstream spread
+    {
+        StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)Ca_chunk * Cb * 4.0 + rows_p * 12.0);
+        DPD_LAUNCH(cross_spread_kernel, dim3((rows_p + 255) / 256), dim3(256), 0, s, Gd, N, rows, rows_p, dpred);
+        DPD_CHECK_LAUNCH();
+    }
+    // 3. layers 4..2: g3 -> ga, g2 -> gb, g1 -> ga (masked queries and pad rows: exact zeros through the mask)
+    if (int rc = dpd_decoder_bwd_data(dpred, maskr, y, h1, h2, h3, rows_p, KP, H, p, DPD_F32, dy, ga, gb, ga, nullptr, nullptr, nullptr, 0, nullptr, 7,
+                                      stream))
+        return rc;
+    // 5. slot sum + query route
+    if (int rc = dpd_cross_slot_sum(ga, cnt, slot_start, qlist, p->W1p, Ca_chunk, Cb, N, m, k, KP, H, slot_cap, surface ? gs : nullptr,
+                                    query ? dq : nullptr, stream))
+        return rc;
+    if (surface) {
+        // 6. slot product over the capacity (the dead rows of gs are zero): dXs [slot_cap, KP] = gs W1p^T, NN on the transposed copy
+        GemmF32Call f;
+        f.M = slot_cap; f.N = KP; f.K = H;
+        f.A = gs; f.lda = H; f.B = p->W1pT; f.ldb = KP; f.C = dXs; f.ldc = KP;
+        f.epilogue = EPI_NONE; f.split_k = 1; f.s = s;
+        f.tile = ((long)((slot_cap + 127) / 128) * ((KP + 127) / 128) >= 512) ? 30 : 32;      // the choice of the pair path's dX product
+        if (int rc = gemm_f32(f)) return rc;
+        // 7. window scatter over the slots
+        if (int rc = dpd_cross_scatter(dXs, cnt, slot_vox, Ca_chunk, Cb, N, m, k, KP, dfv, stream)) return rc;
+    }
+    if (query) {
+        // 9. query-route reduction, continued from what earlier chunks left in gQ
+        StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)rows * 12.0 + QN * 24.0);
+        DPD_LAUNCH(cross_qreduce_kernel, dim3((QN * 3 + 255) / 256), dim3(256), 0, s, (const float*)dq, Ca_chunk, QN * 3, gQ);
+        DPD_CHECK_LAUNCH();
+    }
+    return 0;
+}

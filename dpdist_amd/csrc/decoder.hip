@@ -1258,6 +1258,29 @@ extern "C" int dpd_decoder_fwd_cross(const float* Xu /* k-major */, int ldu, int
     return 0;
 }
 
+// dpd_decoder_fwd_cross with the three activations kept for dpd_cross_bwd: the same launches on the same operands, so the same bits
+extern "C" int dpd_decoder_fwd_cross_keep(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid,
+                                          const int32_t* cnt, float* Pu, const float* maskr, int pairs, int N, int KP, int H,
+                                          const dpd_decoder_params* p, float* h1, float* h2, float* h3, float* y, float* pred, float* Dd,
+                                          void* stream) {
+    using namespace dpd;
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !maskr || !p || !h1 || !h2 || !h3 || !y || !pred) return DPD_E_NULL;      // (Dd = NULL: no pair means)
+    if (h1 == h2 || h2 == h3 || h1 == h3) return DPD_E_DIM;
+    if (!p->W1p || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4) return DPD_E_NULL;
+    if (pairs <= 0 || N <= 0 || KP <= 0 || H <= 0 || slot_cap <= 0 || ldu < slot_cap || (long)pairs * N > (1L << 30)) return DPD_E_DIM;
+    if ((H & 63) || (KP & 31) || KP < 64 || (slot_cap & 3) || (ldu & 3)) return DPD_E_UNSUPPORTED;
+    const int Q = (pairs * N + 31) / 32 * 32;
+    if (!fits_gemm_offsets((size_t)(KP - 32), (size_t)ldu) || !fits_gemm_offsets((size_t)slot_cap, (size_t)H) || !fits_gemm_offsets((size_t)Q, (size_t)H))
+        return DPD_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = fwd_over_slots(Xu, ldu, slot_cap, Xt, uid, cnt + 1, Pu, maskr, Q, KP, H, p, h1, h2, h3, y, pred, s, true)) return rc;
+    if (!Dd) return 0;
+    StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)pairs * N * 12.0 + pairs * 4.0);
+    DPD_LAUNCH(pair_mean_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, (const float*)pred, N, pairs, Dd);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int dpd_decoder_out_asloss(const float* h3, const float* mask, int Q, int H, int BN, const dpd_decoder_params* p, float gscale,
                                       float* y, float* pred, float* loss_pred, float* dy, float* g3, float* scratch, void* stream) {
     return dpd_decoder_out_asloss_planes(h3, mask, Q, H, BN, p, gscale, y, pred, loss_pred, dy, g3, nullptr, scratch, stream);

@@ -1,4 +1,5 @@
-// Window gather for the ALL-PAIRS distance matrix (exact fp32, forward only; included by patch_rows.hip inside namespace dpd).
+// Window gather for the ALL-PAIRS distance matrix (exact fp32, the forward; its backward is cross_bwd.hip; included by patch_rows.hip inside
+// namespace dpd).
 //
 // Every cloud of one set (the SURFACE clouds, fv [Ca, m^3, 20]) against every query of the other set (q [Cb, N, 3]): row (i, j, n) of
 // the decoder is [window of surface i around the voxel of query (j, n) | q - centre | pad].  The voxel of a query does not depend on

@@ -70,6 +70,12 @@ SIGNATURES = {
     "dpd_cross_index": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "dpd_cross_gather": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 5),
     "dpd_decoder_fwd_cross": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int] * 4 + [POINTER(DecoderParams)] + [c_void_p] * 6),
+    "dpd_cross_bwd_workspace_bytes": (c_size_t, [c_int] * 7),
+    "dpd_cross_invert": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4),
+    "dpd_decoder_fwd_cross_keep": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int] * 4 + [POINTER(DecoderParams)] + [c_void_p] * 7),
+    "dpd_cross_slot_sum": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p] * 3),
+    "dpd_cross_scatter": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
+    "dpd_cross_bwd": (c_int, [c_void_p] * 10 + [c_int] * 8 + [POINTER(DecoderParams)] + [c_void_p] * 10),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

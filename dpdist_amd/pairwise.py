@@ -8,7 +8,12 @@ dpd_decoder_fwd_cross).
 which is `loss_pred` of the pair (A_i, B_j) as DPDistLoss computes it (utils/dpdist_util.py:976-979), for every pair.  Each set is
 encoded once; the queries of a set are indexed once per direction (their voxels do not depend on the surface cloud), so layer 1 of the
 decoder contracts the window columns once per (surface cloud, occupied voxel) and never sees a [rows, KP] row matrix.  Exact fp32,
-forward only, on the current stream, without a host synchronisation.  There is no fallback to the pair path.
+on the current stream, without a host synchronisation.  There is no fallback to the pair path.
+
+`dpdist_matrix` is the forward alone (no_grad).  `DPDistMatrix` is the same matrix as ONE autograd node in as-loss mode (the decoder is
+frozen, gradients go to the two cloud sets; dpd_cross_invert, dpd_decoder_fwd_cross_keep, dpd_cross_bwd): the node saves the clouds and
+recomputes every chunk in the backward, where the gradient rows that share a (surface cloud, occupied voxel) slot are summed before the
+layer-1 data gradient, the window scatter and the encoder backward.
 """
 import math
 
@@ -125,15 +130,9 @@ def _directed(lib, s, P, cp, m, fvS, Q, max_rows, chunks):
     return out
 
 
-@torch.no_grad()
-def dpdist_matrix(model_or_params, cloudsA, cloudsB=None, max_rows=16384, return_directed=False, Embedding_Size=None,
-                  sigma3dmfv=None):
-    """cloudsA [Ca,N,3], cloudsB [Cb,N,3] (None: cloudsA against itself, from one direction) -> D [Ca,Cb], or (D, D_AB, D_BA) with
-    return_directed.  model_or_params: a DPDistModel, or a DPDistParams with the grid (Embedding_Size = m^3, default 512) and sigma3dmfv
-    (default 0.125) given here; with a DPDistModel they are the model's, and different values given here raise.
-    max_rows bounds the decoder rows of one chunk of whole surface clouds (a chunk holds at least one): 16384 rows are two activation
-    buffers of 64 MB at H = 1024.  ValueError for a compute type other than exact fp32, CPU tensors, N differing between the sets and
-    shapes the C entries refuse."""
+def _prepare(model_or_params, cloudsA, cloudsB, max_rows, Embedding_Size, sigma3dmfv, report="dpd_cross_workspace_bytes"):
+    """every argument check of the matrix, and every chunk shape of both directions against `report` before anything is launched
+    -> (P, m, sigma, A, B)"""
     P, m, sigma = _resolve(model_or_params, Embedding_Size, sigma3dmfv)
     _check_shape(cloudsA, "cloudsA")
     if cloudsB is not None:
@@ -148,14 +147,24 @@ def dpdist_matrix(model_or_params, cloudsA, cloudsB=None, max_rows=16384, return
         raise ValueError("max_rows must be positive")
     if P.flat.device != A.device:
         raise ValueError("the decoder weights and the clouds must live on the same device")
-    lib = L.load()
-    # every chunk shape of both directions, before anything is launched (a chunk too large for the GEMMs' 32-bit offsets is refused here)
-    for Cs, Cq in ((A.shape[0], A.shape[0]),) if B is None else ((A.shape[0], B.shape[0]), (B.shape[0], A.shape[0])):
-        per = chunk_clouds(Cs, Cq * A.shape[1], max_rows)
+    check_chunks(L.load(), report, P, m, A.shape[0], None if B is None else B.shape[0], A.shape[1], max_rows)
+    return P, m, sigma, A, B
+
+
+def check_chunks(lib, report, P, m, Ca, Cb, N, max_rows):
+    """every chunk shape of both directions (Cb = None: a set against itself) against a workspace report, which allocates nothing: a
+    chunk too large for the GEMMs' 32-bit offsets is refused here"""
+    for Cs, Cq in ((Ca, Ca),) if Cb is None else ((Ca, Cb), (Cb, Ca)):
+        per = chunk_clouds(Cs, Cq * N, max_rows)
         for ca in {per, Cs % per} - {0}:
-            if not lib.dpd_cross_workspace_bytes(ca, Cq, A.shape[1], m, P.k, P.KP, P.H):
+            if not getattr(lib, report)(ca, Cq, N, m, P.k, P.KP, P.H):
                 raise ValueError("dpdist_matrix: shape not supported (%d x %d clouds per chunk, N %d, m %d, k %d, H %d; max_rows %d)"
-                                 % (ca, Cq, A.shape[1], m, P.k, P.H, max_rows))
+                                 % (ca, Cq, N, m, P.k, P.H, max_rows))
+
+
+def _forward(P, m, sigma, A, B, max_rows):
+    """the launches of dpdist_matrix -> (D, D_AB, D_BA)"""
+    lib = L.load()
     with torch.cuda.device(A.device):
         s, cp = L.cur_stream(), P.cparams()
         chunks = {}
@@ -168,4 +177,177 @@ def dpdist_matrix(model_or_params, cloudsA, cloudsB=None, max_rows=16384, return
             d_ab = _directed(lib, s, P, cp, m, fvA, B, max_rows, chunks)
             d_ba = _directed(lib, s, P, cp, m, fvB, A, max_rows, chunks).t()      # the same code with the sets swapped
         D = (d_ab + d_ba) / 2
-    return (D, d_ab, d_ba.contiguous()) if return_directed else D
+    return D, d_ab, d_ba.contiguous()
+
+
+@torch.no_grad()
+def dpdist_matrix(model_or_params, cloudsA, cloudsB=None, max_rows=16384, return_directed=False, Embedding_Size=None,
+                  sigma3dmfv=None):
+    """cloudsA [Ca,N,3], cloudsB [Cb,N,3] (None: cloudsA against itself, from one direction) -> D [Ca,Cb], or (D, D_AB, D_BA) with
+    return_directed.  model_or_params: a DPDistModel, or a DPDistParams with the grid (Embedding_Size = m^3, default 512) and sigma3dmfv
+    (default 0.125) given here; with a DPDistModel they are the model's, and different values given here raise.
+    max_rows bounds the decoder rows of one chunk of whole surface clouds (a chunk holds at least one): 16384 rows are two activation
+    buffers of 64 MB at H = 1024.  ValueError for a compute type other than exact fp32, CPU tensors, N differing between the sets and
+    shapes the C entries refuse.  Forward only: DPDistMatrix is the differentiable form."""
+    P, m, sigma, A, B = _prepare(model_or_params, cloudsA, cloudsB, max_rows, Embedding_Size, sigma3dmfv)
+    D, d_ab, d_ba = _forward(P, m, sigma, A, B, max_rows)
+    return (D, d_ab, d_ba) if return_directed else D
+
+
+# ---- the differentiable form ----
+class _BwdChunk:
+    """the buffers of one BACKWARD chunk of `ca` surface clouds, carved from one allocation in the order dpd_cross_bwd_workspace_bytes
+    states: the forward's buffers with three kept activations, then the gradient buffers"""
+
+    def __init__(self, lib, ca, Cb, N, m, P, dev):
+        nbytes = lib.dpd_cross_bwd_workspace_bytes(ca, Cb, N, m, P.k, P.KP, P.H)
+        self.cap = lib.dpd_cross_slot_capacity(ca, Cb, N, m)
+        if not nbytes or not self.cap:
+            raise ValueError("dpdist_matrix: shape not supported by the backward (clouds per chunk %d x %d, N %d, m %d, k %d, H %d)"
+                             % (ca, Cb, N, m, P.k, P.H))
+        self.ca = ca
+        rows_p = (ca * Cb * N + 31) // 32 * 32
+        act = rows_p * P.H * 4
+        self.arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        off = 0
+        self.ptr = {}
+        for name, size in (("Xu", (P.KP - 32) * self.cap * 4), ("Xt", rows_p * 32 * 4), ("uid", rows_p * 4), ("maskr", rows_p * 4), ("cnt", 16),
+                           ("Pu", self.cap * P.H * 4), ("h1", act), ("h2", act), ("h3", act), ("y", rows_p * 12), ("pred", rows_p * 12),
+                           ("dpred", rows_p * 12), ("dy", rows_p * 12), ("ga", act), ("gb", act), ("dq", rows_p * 12),
+                           ("gs", self.cap * P.H * 4), ("dXs", self.cap * P.KP * 4), ("dfv", ca * m ** 3 * F * 4)):
+            self.ptr[name] = self.arena.data_ptr() + off
+            off += (size + 255) // 256 * 256
+        if off != nbytes:
+            raise RuntimeError("dpd_cross_bwd_workspace_bytes and dpdist_amd.pairwise disagree on the layout (%d != %d)" % (off, nbytes))
+
+
+def _directed_bwd(lib, s, P, cp, m, sigma, S, fvS, Q, Gd, need_s, need_q, max_rows, chunks):
+    """one direction of the backward: surface clouds S [Cs, N, 3] (Fisher vectors fvS), queries Q [Cq, N, 3], upstream Gd [Cs, Cq] of that
+    direction's matrix -> (surface route [Cs, N, 3] | None, query route [Cq, N, 3] | None)"""
+    Cs, (Cq, N, _) = S.shape[0], Q.shape
+    dev = Q.device
+    G = m ** 3
+    mask = torch.empty(Cq * N, device=dev, dtype=torch.float32)
+    idx = torch.empty(Cq * N * 2 + 3 * G + 2, device=dev, dtype=torch.int32)     # vox, qlist, slot_of_vox + count, slot_start, slot_vox
+    vox, qlist, slot, start, svox = idx[:Cq * N], idx[Cq * N:2 * Cq * N], idx[2 * Cq * N:][:G + 1], idx[2 * Cq * N + G + 1:][:G + 1], idx[2 * Cq * N + 2 * G + 2:]
+    ucount = slot[G:]
+    _check(lib.dpd_cross_index(L.ptr(Q), Cq, N, m, L.ptr(mask), L.ptr(vox), L.ptr(slot), L.ptr(ucount), s), "dpd_cross_index")
+    _check(lib.dpd_cross_invert(L.ptr(vox), L.ptr(slot), L.ptr(ucount), Cq, N, m, L.ptr(start), L.ptr(qlist), L.ptr(svox), s), "dpd_cross_invert")
+    gS = torch.empty(Cs, N, 3, device=dev, dtype=torch.float32) if need_s else None
+    gQ = torch.zeros(Cq, N, 3, device=dev, dtype=torch.float32) if need_q else None
+    ws = torch.empty(lib.dpd_mfv3d_bwd_workspace_bytes(Cs, m), device=dev, dtype=torch.uint8) if need_s else None
+    per = chunk_clouds(Cs, Cq * N, max_rows)
+    for i0 in range(0, Cs, per):
+        ca = min(per, Cs - i0)
+        key = (ca, Cq)
+        ck = chunks.get(key)
+        if ck is None:
+            ck = chunks[key] = _BwdChunk(lib, ca, Cq, N, m, P, dev)
+        p = ck.ptr
+        _check(lib.dpd_cross_gather(L.ptr(Q), L.ptr(vox), L.ptr(mask), L.ptr(slot), L.ptr(ucount), L.ptr(fvS[i0:i0 + ca]), None, ca, Cq, N, m,
+                                     P.k, P.KP, p["Xu"], ck.cap, p["Xt"], p["uid"], p["maskr"], p["cnt"], s), "dpd_cross_gather")
+        _check(lib.dpd_decoder_fwd_cross_keep(p["Xu"], ck.cap, ck.cap, p["Xt"], p["uid"], p["cnt"], p["Pu"], p["maskr"], ca * Cq, N, P.KP, P.H,
+                                               cp, p["h1"], p["h2"], p["h3"], p["y"], p["pred"], None, s), "dpd_decoder_fwd_cross_keep")
+        _check(lib.dpd_cross_bwd(L.ptr(Gd[i0:i0 + ca]), p["maskr"], p["y"], p["h1"], p["h2"], p["h3"], p["cnt"], L.ptr(start), L.ptr(qlist),
+                                  L.ptr(svox), ca, Cq, N, m, P.k, P.KP, P.H, ck.cap, cp, p["dpred"], p["dy"], p["ga"], p["gb"], p["dq"],
+                                  p["gs"] if need_s else None, p["dXs"] if need_s else None, p["dfv"] if need_s else None, L.ptr(gQ), s),
+               "dpd_cross_bwd")
+        if need_s:
+            _check(lib.dpd_mfv3d_bwd(L.ptr(S[i0:i0 + ca]), p["dfv"], ca, N, m, sigma, L.ptr(gS[i0:i0 + ca]), L.ptr(ws), ws.numel(), s),
+                   "dpd_mfv3d_bwd")
+    return gS, gQ
+
+
+class _MatrixFn(torch.autograd.Function):
+    """(D, D_AB, D_BA) of two cloud sets as one autograd node; B is None for a set against itself"""
+
+    @staticmethod
+    def forward(ctx, A, B, P, m, sigma, max_rows):
+        ctx.cfg = (P, m, sigma, max_rows, B is None)
+        ctx.set_materialize_grads(False)
+        a = A.detach().contiguous()
+        b = None if B is None else B.detach().contiguous()
+        ctx.save_for_backward(*((a,) if b is None else (a, b)))        # activation checkpointing: the clouds only
+        return _forward(P, m, sigma, a, b, max_rows)
+
+    @staticmethod
+    def backward(ctx, gD, gAB, gBA):
+        P, m, sigma, max_rows, self_matrix = ctx.cfg
+        A = ctx.saved_tensors[0]
+        B = A if self_matrix else ctx.saved_tensors[1]
+        needA = ctx.needs_input_grad[0]
+        needB = (not self_matrix) and ctx.needs_input_grad[1]
+        if (gD is None and gAB is None and gBA is None) or not (needA or needB):
+            return (None,) * 6
+
+        def upstream(*terms):
+            """the sum of the upstreams that exist, as a contiguous fp32 matrix (None: no upstream at all)"""
+            terms = [t for t in terms if t is not None]
+            return sum(terms[1:], terms[0]).to(torch.float32).contiguous() if terms else None
+
+        # D = (D_AB + D_BA) / 2; D_BA is returned as [Ca, Cb], its direction's matrix (surface B, query A) is [Cb, Ca]
+        half = None if gD is None else gD / 2
+        half_t = None if gD is None else half.t()
+        gBA_t = None if gBA is None else gBA.t()
+        lib = L.load()
+        flat = P.flat
+        with torch.cuda.device(A.device), torch.no_grad():
+            s = L.cur_stream()
+            cp = L.make_params(*P.views(flat), *P.transposed(flat))
+            chunks = {}
+            gA = gB = None
+            if self_matrix:
+                # D_BA = D_AB^T: the matrix came from one direction, whose upstream is (G + G^T) / 2 plus the directed ones; both routes land in A
+                g = upstream(half, half_t, gAB, gBA_t)
+                fvA = _encode(lib, s, A, m, sigma)
+                gs_, gq_ = _directed_bwd(lib, s, P, cp, m, sigma, A, fvA, A, g, True, True, max_rows, chunks)
+                gA = gs_ + gq_
+            else:
+                g_ab, g_ba = upstream(half, gAB), upstream(half_t, gBA_t)
+                sA = qB = sB = qA = None
+                if g_ab is not None:
+                    fvA = _encode(lib, s, A, m, sigma)
+                    sA, qB = _directed_bwd(lib, s, P, cp, m, sigma, A, fvA, B, g_ab, needA, needB, max_rows, chunks)
+                if g_ba is not None:
+                    fvB = _encode(lib, s, B, m, sigma)
+                    sB, qA = _directed_bwd(lib, s, P, cp, m, sigma, B, fvB, A, g_ba, needB, needA, max_rows, chunks)
+                both = lambda x, y: y if x is None else (x if y is None else x + y)   # noqa: E731  (a direction without upstream gave None)
+                gA, gB = both(sA, qA), both(qB, sB)
+            del cp
+        return gA, gB, None, None, None, None
+
+
+class DPDistMatrix(torch.nn.Module):
+    """dpdist_matrix as a differentiable module in as-loss mode: the decoder is frozen, gradients go to cloudsA and cloudsB only (as in
+    DPDistLoss), under any upstream gradient of D [Ca, Cb] and, with return_directed, of D_AB and D_BA.  Exact fp32; the forward values
+    are bit for bit those of dpdist_matrix (the same launches on the same buffers).
+
+    One autograd node over the library, on the current stream, without a host synchronisation.  The node saves the clouds only and
+    recomputes every chunk in the backward (activation checkpointing: an all-pairs forward cannot keep h1..h3 of every chunk).  A backward
+    chunk of `rows_p` decoder rows holds three activation buffers and two gradient buffers of [rows_p, H] and y, beside the slot buffers
+    (Xu, Pu, gs, dXs over the slot capacity): the default max_rows = 16384 makes that five buffers of 64 MB at H = 1024.  The gradients do
+    not depend on max_rows (chunks hold whole surface clouds and the query-route sum is one chain across the chunks).
+
+    cloudsB = None: cloudsA against itself from one direction; its upstream is then (G + G^T) / 2 and both routes land in cloudsA.
+    A set that needs no gradient gets None and its share of the work is skipped.  Argument checks and errors as dpdist_matrix; every chunk
+    shape of forward and backward is checked before the first launch."""
+
+    def __init__(self, model_or_params, max_rows=16384, Embedding_Size=None, sigma3dmfv=None):
+        super().__init__()
+        self._src = (model_or_params, Embedding_Size, sigma3dmfv)
+        _resolve(model_or_params, Embedding_Size, sigma3dmfv)
+        if int(max_rows) < 1:
+            raise ValueError("max_rows must be positive")
+        self.max_rows = int(max_rows)
+
+    def forward(self, cloudsA, cloudsB=None, return_directed=False):
+        mp, es, sg = self._src
+        want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (cloudsA, cloudsB))
+        P, m, sigma, A, B = _prepare(mp, cloudsA, cloudsB, self.max_rows, es, sg,
+                                     "dpd_cross_bwd_workspace_bytes" if want_grad else "dpd_cross_workspace_bytes")
+        if not want_grad:
+            with torch.no_grad():
+                D, d_ab, d_ba = _forward(P, m, sigma, A, B, self.max_rows)
+        else:
+            D, d_ab, d_ba = _MatrixFn.apply(cloudsA, cloudsB, P, m, sigma, self.max_rows)
+        return (D, d_ab, d_ba) if return_directed else D

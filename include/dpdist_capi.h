@@ -186,7 +186,7 @@ int dpd_decoder_fwd_unique(const float* Xu, const float* Xt, const int32_t* uid,
                            float* pred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * All-pairs distance matrix (DPD_F32, forward only): every cloud of a set A [Ca,N,3] against every cloud of a set B [Cb,N,3],
+ * All-pairs distance matrix (DPD_F32; its backward is the block below): every cloud of a set A [Ca,N,3] against every cloud of a set B [Cb,N,3],
  *   D_AB[i,j] = mean_n pred(surface A_i ; query B_j[n])[0]
  * -- what get_emb_and_concat / get_pc_grid_binary_mask_from_centers (utils/dpdist_util.py:434-511), the decoder (:513-544), relu6/3 and
  * the mask (:690-698) and the mean of loss_pred (:976-979) give for the pair (A_i, B_j) -- without building the Ca Cb pairs: the
@@ -227,6 +227,50 @@ int dpd_cross_gather(const float* q, const int32_t* vox, const float* mask, cons
 int dpd_decoder_fwd_cross(const float* Xu, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
                           const float* maskr, int pairs, int N, int KP, int H, const dpd_decoder_params* p, float* act0, float* act1,
                           float* y, float* pred, float* Dd, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Backward of the all-pairs matrix (DPD_F32, as-loss mode: the decoder is frozen, gradients go to the two cloud sets).  Per direction
+ * and chunk of whole surface clouds, rows ordered (i, j, n) as in the forward; the layer-1 data gradient is linear, so the gradient rows
+ * of all queries that share a (surface, occupied voxel) slot are summed first and multiplied by W1p^T once per slot.  Deterministic: no
+ * float atomics, one summation order per element, independent of the launch shape.  The caller owns all memory; the host never reads U.
+ *
+ * dpd_cross_invert: the inverted index of dpd_cross_index's vox / slot_of_vox / ucount, once per direction (one launch, integer only):
+ *   slot_start [m^3 + 1]  start of slot s in qlist for s < U, Cb N for U <= s <= m^3;
+ *   qlist [Cb N]          the query ids sorted by slot, ascending query id inside a slot (a stable counting sort);
+ *   slot_vox [m^3]        the voxel id of slot s for s < U, -1 beyond.
+ * dpd_decoder_fwd_cross_keep: dpd_decoder_fwd_cross (same launches, same bits) with layers 1 to 3 kept in three distinct buffers h1, h2,
+ *   h3 [rows_p, H] for the backward.  Dd may be NULL (no pair means).
+ * dpd_cross_slot_sum: g1 [rows_p, H] streamed once; cnt / slot_cap as written by / given to dpd_cross_gather for this chunk.
+ *     gs [slot_cap, H]   row i U + s = the sum of the g1 rows of surface i whose query lies in slot s, added in list order; the DEAD rows
+ *                        Ca_chunk U <= t < slot_cap are written as ZEROS (the slot product runs over the capacity);
+ *     dq [rows, 3]       dq[r, c] = g1[r, :] . W1p[E + c, :], E = 20 k^3: the q - centre columns of dX; rows >= Ca_chunk Cb N untouched.
+ *   gs = NULL or dq = NULL (not both): that half is skipped.  H % 64 == 0, H <= 4096.
+ * dpd_cross_scatter: dXs [>= Ca_chunk U, KP] (row i U + s = the dX of that slot) -> dfv [Ca_chunk, m^3, 20]: dfv[i, v, ch] = the sum over
+ *   the slots of surface i whose window covers voxel v, in ascending slot order, of that window column; zero padding at the grid border.
+ * dpd_cross_bwd: one chunk: Gd [Ca_chunk Cb] (the direction's upstream of D_dir, chunk rows) -> dpred [rows_p, 3] = (Gd / N, 0, 0), 0 on
+ *   the pad rows; dpd_decoder_bwd_data (phases 7, no dX; p needs W2T / W3T, and W1pT when dfv is wanted) with g3 -> ga, g2 -> gb, g1 -> ga;
+ *   dpd_cross_slot_sum; dXs [slot_cap, KP] = gs W1pT (one NN GEMM over the capacity); dpd_cross_scatter -> dfv (feed it to dpd_mfv3d_bwd
+ *   with the chunk's surface clouds); gQ [Cb, N, 3] = gQ + sum_i dq[(i, j, n)] in ascending i (the caller zeroes gQ before the first chunk
+ *   of a direction: the chain is continued, so chunk boundaries change no bit).  dfv = NULL: the surface set needs no gradient (slot sum
+ *   of gs, slot product and scatter skipped; gs, dXs, slot_vox may be NULL); gQ = NULL: the query set needs none (dq may be NULL).
+ * dpd_cross_bwd_workspace_bytes: the bytes of one backward chunk -- Xu, Xt, uid, maskr, cnt, Pu, h1, h2, h3, y, pred (the forward's
+ *   buffers with three activations), then dpred, dy [rows_p, 3], ga, gb [rows_p, H], dq [rows_p, 3], gs [slot_cap, H], dXs [slot_cap, KP],
+ *   dfv [Ca_chunk, m^3, 20], in this order, each rounded up to 256 bytes; 0 for a refused shape: one the forward refuses, H > 4096, or
+ *   dXs beyond the 4 GiB the GEMMs address (DPD_E_UNSUPPORTED from the entries).                                                    */
+size_t dpd_cross_bwd_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H);
+int dpd_cross_invert(const int32_t* vox, const int32_t* slot_of_vox, const int32_t* ucount, int Cb, int N, int m, int32_t* slot_start,
+                     int32_t* qlist, int32_t* slot_vox, void* stream);
+int dpd_decoder_fwd_cross_keep(const float* Xu, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
+                               const float* maskr, int pairs, int N, int KP, int H, const dpd_decoder_params* p, float* h1, float* h2,
+                               float* h3, float* y, float* pred, float* Dd, void* stream);
+int dpd_cross_slot_sum(const float* g1, const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const float* W1p, int Ca_chunk,
+                       int Cb, int N, int m, int k, int KP, int H, int slot_cap, float* gs, float* dq, void* stream);
+int dpd_cross_scatter(const float* dXs, const int32_t* cnt, const int32_t* slot_vox, int Ca_chunk, int Cb, int N, int m, int k, int KP,
+                      float* dfv, void* stream);
+int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y, const float* h1, const float* h2, const float* h3, const int32_t* cnt,
+                  const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox, int Ca_chunk, int Cb, int N, int m, int k, int KP,
+                  int H, int slot_cap, const dpd_decoder_params* p, float* dpred, float* dy, float* ga, float* gb, float* dq, float* gs,
+                  float* dXs, float* dfv, float* gQ, void* stream);
 
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in

@@ -6,6 +6,9 @@ on synth.s2_modelnet_shaped clouds:
             points of pred_listAB / pred_listBA[..., 0]
 
     python tools/matrix_bench.py            # one JSON line
+    python tools/matrix_bench.py --grad     # forward + backward under a random upstream matrix G, loss = (G * D).sum():
+                                            #   cross   dpdist_amd.DPDistMatrix (one autograd node; the backward recomputes each chunk)
+                                            #   pairs   the frozen model on the hand-tiled pairs, 128 pairs at a time, each pair weighted by G
 
 The two forms alternate, five rounds after a warm-up, each timed with a device event pair; the two matrices must agree within the
 fp32 forward bar of the tests (1e-4 absolute).  The per-kernel split comes from a further pass of each form under the library's in-stream
@@ -20,11 +23,14 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dpdist_amd import dpdist_matrix, synth  # noqa: E402
+from dpdist_amd import DPDistMatrix, dpdist_matrix, synth  # noqa: E402
 from dpdist_amd import lib as L  # noqa: E402
 from dpdist_amd.model import DPDistModel  # noqa: E402
 
 STAGES = {1: "encoder", 2: "index_and_gather", 3: "output_layer", 5: "pair_mean", 7: "layer1_finish"}
+# --grad: the backward's launches record under the same tags (index + inverted index + gather + window scatter; pair means + upstream
+# spread + slot sum / query route + query-route reduction)
+STAGES_GRAD = {1: "encoder", 2: "index_gather_scatter", 3: "output_layer", 5: "spread_slotsum_reduce", 7: "layer1_finish"}
 
 
 def pair_matrix(model, A, B, batch=128):
@@ -42,6 +48,30 @@ def pair_matrix(model, A, B, batch=128):
     return (d_ab + d_ba) / 2, d_ab, d_ba
 
 
+def pair_grads(model, A, B, G, batch=128):
+    """d (G * D).sum() / d (A, B) through the pair path in as-loss mode (frozen decoder): forward and backward per batch of pairs"""
+    Ca, Cb, N = A.shape[0], B.shape[0], A.shape[1]
+    a, b = A.detach().requires_grad_(True), B.detach().requires_grad_(True)
+    a_t = a[:, None].expand(-1, Cb, -1, -1).reshape(Ca * Cb, N, 3)
+    b_t = b[None].expand(Ca, -1, -1, -1).reshape(Ca * Cb, N, 3)
+    g = G.reshape(-1)
+    loss = None
+    for p0 in range(0, Ca * Cb, batch):
+        ps = model(a_t[p0:p0 + batch].contiguous(), b_t[p0:p0 + batch].contiguous())
+        d = (ps["pred_listAB"][:, :, 0, 0].mean(1) + ps["pred_listBA"][:, :, 0, 0].mean(1)) / 2
+        part = (g[p0:p0 + batch] * d).sum()
+        part.backward()                     # per batch: the activations of one batch alive at a time, as in the forward
+        loss = part.detach() if loss is None else loss + part.detach()
+    return a.grad, b.grad, loss
+
+
+def cross_grads(mod, A, B, G):
+    a, b = A.detach().requires_grad_(True), B.detach().requires_grad_(True)
+    loss = (G * mod(a, b)).sum()
+    loss.backward()
+    return a.grad, b.grad, loss.detach()
+
+
 def timed(fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -51,7 +81,7 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
-def kernel_split(lib, fn):
+def kernel_split(lib, fn, stages=None):
     """ms per call of `fn` by kind of launch, from the library's in-stream profiler"""
     torch.cuda.synchronize()
     lib.dpd_prof_enable(2)
@@ -65,7 +95,7 @@ def kernel_split(lib, fn):
             out[name] = {"launches": n, "ms": round(ms.value, 4)}
             if form == 0:       # (the slot product records its flops by the slot CAPACITY, not the live count)
                 out[name]["tflops"] = round(x.value / (ms.value * 1e-3) / 1e12, 1)
-    for tag, name in STAGES.items():
+    for tag, name in (stages or STAGES).items():
         n = lib.dpd_prof_collect_stage(tag, ctypes.byref(ms), ctypes.byref(x))
         if n > 0:
             out[name] = {"launches": n, "ms": round(ms.value, 4)}
@@ -81,6 +111,7 @@ def main():
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--max-rows", type=int, default=16384)
+    ap.add_argument("--grad", action="store_true", help="forward + backward under a random upstream matrix")
     a = ap.parse_args()
     C, N, H = a.clouds, a.points, a.width
     dev = torch.device("cuda:0")
@@ -89,12 +120,25 @@ def main():
     B = torch.tensor(synth.s2_modelnet_shaped(C, N, 101)[1], device=dev)
     model = DPDistModel(Embedding_Size=512, k=5, localSNmlp=(H,) * 3, sigma3dmfv=0.125, device=dev)
     model.load_tf_state_dict(synth.make_weights("wide", mlp=(H,) * 3))
-    cross = lambda: dpdist_matrix(model, A, B, max_rows=a.max_rows, return_directed=True)   # noqa: E731
-    pairs = lambda: pair_matrix(model, A, B)                                                # noqa: E731
+    if a.grad:
+        for prm in model.parameters():
+            prm.requires_grad_(False)       # as-loss mode: the decoder is frozen in both forms
+        G = torch.tensor(np.random.default_rng(7).standard_normal((C, C)).astype(np.float32), device=dev)
+        mod = DPDistMatrix(model, max_rows=a.max_rows)
+        cross = lambda: cross_grads(mod, A, B, G)       # noqa: E731
+        pairs = lambda: pair_grads(model, A, B, G)      # noqa: E731
+    else:
+        cross = lambda: dpdist_matrix(model, A, B, max_rows=a.max_rows, return_directed=True)   # noqa: E731
+        pairs = lambda: pair_matrix(model, A, B)                                                # noqa: E731
     got, want = cross(), pairs()
     torch.cuda.synchronize()
     err = [float((x.double() - y.double()).abs().max()) for x, y in zip(got, want)]
-    if max(err) > 1e-4:
+    if a.grad:
+        # both gradients sit within the input-gradient bar of the tests of the same float64 value: 2e-4 max(1, max|g|) each
+        scale = max(1.0, max(float(x.abs().max()) for x in want[:2]))
+        if max(err[:2]) > 4e-4 * scale or err[2] > 1e-4 * C * C:
+            raise SystemExit("the two forms disagree: max |gA - gA_pairs|, gB, loss = %s" % err)
+    elif max(err) > 1e-4:
         raise SystemExit("the two forms disagree: max |D - D_pairs|, AB, BA = %s" % err)
     for _ in range(2):
         cross(), pairs()
@@ -108,14 +152,17 @@ def main():
         L.check(lib.dpd_cross_index(L.ptr(q), C, N, 8, *[L.ptr(x) for x in ix], L.cur_stream()), "dpd_cross_index")
         slots[name] = {"U": int(ix[3][0]), "slots": C * int(ix[3][0]), "rows": C * C * N}
     stat = lambda v: {"median_ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}   # noqa: E731
-    res = {"shape": {"Ca": C, "Cb": C, "N": N, "H": H, "m": 8, "k": 5, "max_rows": a.max_rows, "pair_batch": 128},
+    names = ("gA", "gB", "loss") if a.grad else ("D", "D_AB", "D_BA")
+    stages = STAGES_GRAD if a.grad else STAGES
+    res = {"mode": "forward+backward" if a.grad else "forward", "shape": {"Ca": C, "Cb": C, "N": N, "H": H, "m": 8, "k": 5, "max_rows": a.max_rows, "pair_batch": 128},
            "device": torch.cuda.get_device_name(0), "rounds": a.rounds,
            "cross": stat(t["cross"]), "pairs": stat(t["pairs"]),
            "speedup_median": round(float(np.median(t["pairs"]) / np.median(t["cross"])), 3),
-           "max_abs_diff": {"D": err[0], "D_AB": err[1], "D_BA": err[2]}, "live_slots": slots,
-           "kernels": {"cross": kernel_split(lib, cross), "pairs": kernel_split(lib, pairs)},
+           "max_abs_diff": dict(zip(names, err)), "live_slots": slots,
+           "kernels": {"cross": kernel_split(lib, cross, stages), "pairs": kernel_split(lib, pairs, stages)},
            "note": "kernels: one profiled call of each form (event pairs around every launch add ~2 us between launches); the pair path's "
-                   "output layer and its torch glue (tiling, means) are not bracketed"}
+                   "output layer and its torch glue (tiling, means) are not bracketed; --grad: nor are the encoder backward and the pair path's "
+                   "window-gather backward"}
     print(json.dumps(res))
 
 
