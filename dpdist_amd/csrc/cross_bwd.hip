@@ -8,6 +8,7 @@
 // are taken per row (dq [rows, 3], a dot product with three rows of W1p).  Rows are ordered (i, j, n) as in the forward.
 // Everything below is deterministic: no atomics on floats, one summation order per output element, whatever the launch holds.
 #include "common.h"
+#include "cross_chunk.h"
 #include "gemm_host.h"
 
 namespace dpd {
@@ -229,7 +230,6 @@ __global__ __launch_bounds__(256) void cross_qreduce_kernel(const float* __restr
 }  // namespace dpd
 
 namespace {
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 // THE shape predicate of the all-pairs backward: a chunk the forward takes (dpd_cross_workspace_bytes is cross_shape_ok, patch_rows.hip)
 // whose slot product dXs [slot_cap, KP] is addressable by the GEMM kernels, at a width slot_sum_kernel covers
 bool cross_bwd_shape_ok(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
@@ -242,14 +242,7 @@ bool cross_bwd_shape_ok(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H
 
 extern "C" size_t dpd_cross_bwd_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
     if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return 0;
-    const size_t cap = (size_t)dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
-    const size_t rows_p = ((size_t)Ca_chunk * Cb * N + 31) / 32 * 32;
-    const size_t G = (size_t)m * m * m;
-    // Xu, Xt, uid, maskr, cnt, Pu, h1, h2, h3, y, pred | dpred, dy, ga, gb, dq, gs, dXs, dfv -- in this order, each 256-byte aligned
-    return al256((size_t)(KP - 32) * cap * 4) + al256(rows_p * 32 * 4) + 2 * al256(rows_p * 4) + al256(16) + al256(cap * H * 4) +
-           3 * al256(rows_p * H * 4) + 2 * al256(rows_p * 12) +
-           2 * al256(rows_p * 12) + 2 * al256(rows_p * H * 4) + al256(rows_p * 12) + al256(cap * H * 4) + al256(cap * (size_t)KP * 4) +
-           al256((size_t)Ca_chunk * G * dpd::kCF * 4);
+    return dpd::cross_chunk_bytes(Ca_chunk, Cb, N, m, KP, H, true);
 }
 
 extern "C" int dpd_cross_invert(const int32_t* vox, const int32_t* slot_of_vox, const int32_t* ucount, int Cb, int N, int m,
@@ -272,7 +265,7 @@ extern "C" int dpd_cross_slot_sum(const float* g1, const int32_t* cnt, const int
     if (Ca_chunk <= 0 || Cb <= 0 || N <= 0 || slot_cap <= 0) return DPD_E_DIM;
     if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return DPD_E_UNSUPPORTED;
     if (slot_cap != dpd_cross_slot_capacity(Ca_chunk, Cb, N, m)) return DPD_E_DIM;
-    const int QN = Cb * N, G = m * m * m, ucap = G < QN ? G : QN;
+    const int QN = Cb * N, ucap = cross_ucap(Cb, N, m);
     const int rows = Ca_chunk * QN;
     StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)rows * H * 4.0 + (gs ? (double)slot_cap * H * 4.0 : 0.0) + (dq ? rows * 12.0 : 0.0) + QN * 4.0);
     // with gs = NULL only the live slots matter, but the live count is a device word: the dead workgroups return at once
@@ -288,7 +281,7 @@ extern "C" int dpd_cross_scatter(const float* dXs, const int32_t* cnt, const int
     if (!dXs || !cnt || !slot_vox || !dfv) return DPD_E_NULL;
     if (Ca_chunk <= 0 || Cb <= 0 || N <= 0) return DPD_E_DIM;
     if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, 64)) return DPD_E_UNSUPPORTED;
-    const int QN = Cb * N, G = m * m * m, ucap = G < QN ? G : QN;
+    const int G = m * m * m, ucap = cross_ucap(Cb, N, m);
     const int slices = (G * 5 + 255) / 256;      // one (voxel, channel group) item per thread
     StageProf prof(stream, DPD_STAGE_GATHER, (double)Ca_chunk * ucap * (k * k * k * kCF) * 4.0 + (double)Ca_chunk * G * kCF * 4.0);
     DPD_LAUNCH(cross_scatter_kernel, dim3(Ca_chunk * slices), dim3(256), 0, (hipStream_t)stream, dXs, cnt, slot_vox, dfv, m, k, KP, ucap, slices);
@@ -311,7 +304,7 @@ extern "C" int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y
     if (!cross_bwd_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return DPD_E_UNSUPPORTED;
     if (slot_cap != dpd_cross_slot_capacity(Ca_chunk, Cb, N, m)) return DPD_E_DIM;
     hipStream_t s = (hipStream_t)stream;
-    const int QN = Cb * N, rows = Ca_chunk * QN, rows_p = (rows + 31) / 32 * 32;
+    const int QN = Cb * N, rows = Ca_chunk * QN, rows_p = (int)cross_rows_p(Ca_chunk, Cb, N);
     // 2. upstream spread
     {
         StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)Ca_chunk * Cb * 4.0 + rows_p * 12.0);

@@ -11,6 +11,7 @@
 // = KP*4 written (+ 12 read; fv[c] = 40 KB per cloud is L2 resident and shared by the cloud's 64 rows).
 #include <cstdlib>
 
+#include "cross_chunk.h"
 #include "gemm_shared.h"
 #include "patch_rows_bwd.h"
 
@@ -663,9 +664,8 @@ bool cross_shape_ok(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
     const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
     for (int x = 0; x < k * k * k; ++x)
         if ((int)((x * mg_kk) >> 16) != x / (k * k) || (int)(((x % (k * k)) * mg_k) >> 16) != (x % (k * k)) / k) return false;
-    const size_t G = (size_t)m * m * m, qn = (size_t)Cb * N;
     if (cross_lds_bytes(m, KP) > 128 * 1024) return false;
-    const size_t cap = ((size_t)Ca_chunk * (G < qn ? G : qn) + 31) / 32 * 32, rows_p = ((size_t)Ca_chunk * qn + 31) / 32 * 32;
+    const size_t cap = (size_t)dpd_cross_slot_capacity(Ca_chunk, Cb, N, m), rows_p = dpd::cross_rows_p(Ca_chunk, Cb, N);
     if (!dpd::fits_gemm_offsets((size_t)(KP - 32), cap)) return false;
     if (H > 0 && ((H & 63) || !dpd::fits_gemm_offsets(cap, (size_t)H) || !dpd::fits_gemm_offsets(rows_p, (size_t)H))) return false;
     return true;
@@ -674,19 +674,34 @@ bool cross_shape_ok(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
 
 extern "C" int dpd_cross_slot_capacity(int Ca_chunk, int Cb, int N, int m) {
     if (Ca_chunk <= 0 || Cb <= 0 || N <= 0 || m < 1 || m > 10) return 0;
-    const long G = (long)m * m * m, qn = (long)Cb * N;
-    const long cap = ((long)Ca_chunk * (G < qn ? G : qn) + 31) / 32 * 32;
+    const long cap = ((long)Ca_chunk * dpd::cross_ucap(Cb, N, m) + 31) / 32 * 32;
     return cap > 0x7fffffffL ? 0 : (int)cap;
 }
 
 extern "C" size_t dpd_cross_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H) {
     if (H <= 0 || !cross_shape_ok(Ca_chunk, Cb, N, m, k, KP, H)) return 0;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t cap = (size_t)dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
-    const size_t rows_p = ((size_t)Ca_chunk * Cb * N + 31) / 32 * 32;
-    // Xu, Xt, uid, maskr, cnt, Pu, two activation buffers, y, pred, Dd -- in this order, each 256-byte aligned
-    return al((size_t)(KP - 32) * cap * 4) + al(rows_p * 32 * 4) + 2 * al(rows_p * 4) + al(16) + al(cap * H * 4) + 2 * al(rows_p * H * 4) +
-           2 * al(rows_p * 3 * 4) + al((size_t)Ca_chunk * Cb * 4);
+    return dpd::cross_chunk_bytes(Ca_chunk, Cb, N, m, KP, H, false);
+}
+
+extern "C" int dpd_cross_carve(void* mem, size_t bytes, int Ca_chunk, int Cb, int N, int m, int k, int KP, int H, int backward,
+                               dpd_cross_chunk* out) {
+    if (!mem || !out) return DPD_E_NULL;
+    *out = dpd_cross_chunk{};
+    const size_t need = (backward ? dpd_cross_bwd_workspace_bytes : dpd_cross_workspace_bytes)(Ca_chunk, Cb, N, m, k, KP, H);
+    if (!need) return DPD_E_UNSUPPORTED;
+    if (bytes < need) return DPD_E_WORKSPACE;
+    out->Ca_chunk = Ca_chunk; out->Cb = Cb; out->N = N; out->m = m; out->k = k; out->KP = KP; out->H = H;
+    out->slot_cap = dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
+    out->rows_p = (int)dpd::cross_rows_p(Ca_chunk, Cb, N);
+    out->bytes = need;
+    dpd::CrossMember mem_of[dpd::kCrossMembers];
+    const int n = dpd::cross_chunk_members(Ca_chunk, Cb, N, m, KP, H, backward != 0, mem_of);
+    char* c = (char*)mem;
+    for (int i = 0; i < n; ++i) {
+        out->*mem_of[i].field = c;
+        c += dpd::cross_al256(mem_of[i].bytes);
+    }
+    return 0;
 }
 
 extern "C" int dpd_cross_index(const float* q, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox, int32_t* ucount,
@@ -709,11 +724,11 @@ extern "C" int dpd_cross_gather(const float* q, const int32_t* vox, const float*
     if (Ca_chunk <= 0 || Cb <= 0 || N <= 0) return DPD_E_DIM;
     if (!cross_shape_ok(Ca_chunk, Cb, N, m, k, KP, 0)) return DPD_E_UNSUPPORTED;
     const size_t lds = cross_lds_bytes(m, KP);
-    const int QN = Cb * N, G = m * m * m, ucap = G < QN ? G : QN;
+    const int QN = Cb * N, G = m * m * m, ucap = cross_ucap(Cb, N, m);
     const int cap = dpd_cross_slot_capacity(Ca_chunk, Cb, N, m);
     if (!cap || ldu < cap) return DPD_E_DIM;
     if (!fits_gemm_offsets((size_t)(KP - 32), (size_t)ldu)) return DPD_E_UNSUPPORTED;
-    const int rows = Ca_chunk * QN, rows_p = (rows + 31) / 32 * 32;
+    const int rows_p = (int)cross_rows_p(Ca_chunk, Cb, N);
     const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
     // algorithmic bytes: the surface vectors and the queries in; the windows (an upper bound: the slot capacity) and the rows' tails out
     StageProf prof(stream, DPD_STAGE_GATHER,

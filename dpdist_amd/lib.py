@@ -48,6 +48,13 @@ class AsLoss(Structure):     # include/dpdist_capi.h: dpd_asloss (the as-loss en
                  ("planes", Planes), ("params", DecoderParams)])
 
 
+class CrossChunk(Structure):   # include/dpdist_capi.h: dpd_cross_chunk (carved by dpd_cross_carve; driven by dpdist_amd/pairwise.py)
+    BUFFERS = ("Xu", "Xt", "uid", "maskr", "cnt", "Pu", "act0", "act1", "Dd", "h1", "h2", "h3", "y", "pred",
+               "dpred", "dy", "ga", "gb", "dq", "gs", "dXs", "dfv")
+    _fields_ = ([(n, c_int) for n in ("Ca_chunk", "Cb", "N", "m", "k", "KP", "H", "slot_cap", "rows_p")] + [("bytes", c_size_t)] +
+                [(n, c_void_p) for n in BUFFERS])
+
+
 # name -> (restype, argtypes); mirrors include/dpdist_capi.h one to one
 SIGNATURES = {
     "dpd_version": (c_char_p, []),
@@ -67,6 +74,7 @@ SIGNATURES = {
     "dpd_decoder_fwd_unique": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, POINTER(DecoderParams)] + [c_void_p] * 6),
     "dpd_cross_slot_capacity": (c_int, [c_int] * 4),
     "dpd_cross_workspace_bytes": (c_size_t, [c_int] * 7),
+    "dpd_cross_carve": (c_int, [c_void_p, c_size_t] + [c_int] * 8 + [POINTER(CrossChunk)]),
     "dpd_cross_index": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "dpd_cross_gather": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 5),
     "dpd_decoder_fwd_cross": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int] * 4 + [POINTER(DecoderParams)] + [c_void_p] * 6),

@@ -71,29 +71,48 @@ def chunk_clouds(C, rows_per_cloud, max_rows):
 
 
 class _Chunk:
-    """the buffers of one chunk of `ca` surface clouds, carved from one allocation in the order dpd_cross_workspace_bytes states"""
+    """the buffers of one chunk of `ca` surface clouds (backward: of one BACKWARD chunk): one allocation of the size the workspace report
+    states, carved by the library (dpd_cross_carve) -- `ptr` holds the addresses of the members the form has, by name"""
 
-    def __init__(self, lib, ca, Cb, N, m, P, dev):
-        nbytes = lib.dpd_cross_workspace_bytes(ca, Cb, N, m, P.k, P.KP, P.H)
-        self.cap = lib.dpd_cross_slot_capacity(ca, Cb, N, m)
-        if not nbytes or not self.cap:
-            raise ValueError("dpdist_matrix: shape not supported (clouds per chunk %d x %d, N %d, m %d, k %d, H %d)" % (ca, Cb, N, m, P.k, P.H))
-        self.ca = ca
-        rows_p = (ca * Cb * N + 31) // 32 * 32
+    def __init__(self, lib, ca, Cb, N, m, P, dev, backward=False):
+        shape = (ca, Cb, N, m, P.k, P.KP, P.H)
+        nbytes = (lib.dpd_cross_bwd_workspace_bytes if backward else lib.dpd_cross_workspace_bytes)(*shape)
+        if not nbytes:
+            raise ValueError("dpdist_matrix: shape not supported%s (clouds per chunk %d x %d, N %d, m %d, k %d, H %d)"
+                             % (" by the backward" if backward else "", ca, Cb, N, m, P.k, P.H))
         self.arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        off = 0
-        self.ptr = {}
-        for name, size in (("Xu", (P.KP - 32) * self.cap * 4), ("Xt", rows_p * 32 * 4), ("uid", rows_p * 4), ("maskr", rows_p * 4), ("cnt", 16),
-                           ("Pu", self.cap * P.H * 4), ("act0", rows_p * P.H * 4), ("act1", rows_p * P.H * 4), ("y", rows_p * 12),
-                           ("pred", rows_p * 12), ("Dd", ca * Cb * 4)):
-            self.ptr[name] = self.arena.data_ptr() + off
-            off += (size + 255) // 256 * 256
-        if off != nbytes:
-            raise RuntimeError("dpd_cross_workspace_bytes and dpdist_amd.pairwise disagree on the layout (%d != %d)" % (off, nbytes))
-        self.Dd_off = self.ptr["Dd"] - self.arena.data_ptr()
+        self.c = L.CrossChunk()
+        L.check(lib.dpd_cross_carve(L.ptr(self.arena), nbytes, *shape, int(backward), self.c), "dpd_cross_carve")
+        self.ca, self.cap = ca, self.c.slot_cap
+        self.ptr = {n: getattr(self.c, n) for n in L.CrossChunk.BUFFERS if getattr(self.c, n) is not None}
 
     def Dd(self, n):
-        return self.arena[self.Dd_off:self.Dd_off + 4 * n].view(torch.float32)
+        off = self.ptr["Dd"] - self.arena.data_ptr()
+        return self.arena[off:off + 4 * n].view(torch.float32)
+
+
+def _index(lib, s, Q, m, extra=0):
+    """the queries Q [Cq, N, 3] indexed once per direction (dpd_cross_index) -> mask [Cq N], then of one int32 allocation vox [Cq N],
+    slot_of_vox [m^3] with the count behind it, the count alone, and `extra` words for the caller"""
+    QN, G = Q.shape[0] * Q.shape[1], m ** 3
+    mask = torch.empty(QN, device=Q.device, dtype=torch.float32)
+    idx = torch.empty(QN + G + 1 + extra, device=Q.device, dtype=torch.int32)
+    vox, slot, rest = idx[:QN], idx[QN:QN + G + 1], idx[QN + G + 1:]
+    ucount = slot[G:]
+    _check(lib.dpd_cross_index(L.ptr(Q), Q.shape[0], Q.shape[1], m, L.ptr(mask), L.ptr(vox), L.ptr(slot), L.ptr(ucount), s), "dpd_cross_index")
+    return mask, vox, slot, ucount, rest
+
+
+def _walk(lib, P, m, Cs, Q, max_rows, chunks, backward=False):
+    """the chunks of whole surface clouds of one direction -> (first cloud, clouds, the chunk's buffers: cached in `chunks` by shape)"""
+    Cq, N, _ = Q.shape
+    per = chunk_clouds(Cs, Cq * N, max_rows)
+    for i0 in range(0, Cs, per):
+        ca = min(per, Cs - i0)
+        ck = chunks.get((ca, Cq))
+        if ck is None:
+            ck = chunks[ca, Cq] = _Chunk(lib, ca, Cq, N, m, P, Q.device, backward)
+        yield i0, ca, ck
 
 
 def _encode(lib, s, pts, m, sigma):
@@ -107,20 +126,9 @@ def _encode(lib, s, pts, m, sigma):
 def _directed(lib, s, P, cp, m, fvS, Q, max_rows, chunks):
     """[Cs, Cq]: every surface cloud (Fisher vectors fvS [Cs, m^3, 20]) against the queries Q [Cq, N, 3]"""
     Cs, (Cq, N, _) = fvS.shape[0], Q.shape
-    dev = Q.device
-    mask = torch.empty(Cq * N, device=dev, dtype=torch.float32)
-    vox = torch.empty(Cq * N, device=dev, dtype=torch.int32)
-    slot = torch.empty(m ** 3 + 1, device=dev, dtype=torch.int32)          # slot_of_vox, then the count
-    ucount = slot[m ** 3:]
-    _check(lib.dpd_cross_index(L.ptr(Q), Cq, N, m, L.ptr(mask), L.ptr(vox), L.ptr(slot), L.ptr(ucount), s), "dpd_cross_index")
-    out = torch.empty(Cs, Cq, device=dev, dtype=torch.float32)
-    per = chunk_clouds(Cs, Cq * N, max_rows)
-    for i0 in range(0, Cs, per):
-        ca = min(per, Cs - i0)
-        key = (ca, Cq)
-        ck = chunks.get(key)
-        if ck is None:
-            ck = chunks[key] = _Chunk(lib, ca, Cq, N, m, P, dev)
+    mask, vox, slot, ucount, _ = _index(lib, s, Q, m)
+    out = torch.empty(Cs, Cq, device=Q.device, dtype=torch.float32)
+    for i0, ca, ck in _walk(lib, P, m, Cs, Q, max_rows, chunks):
         p = ck.ptr
         _check(lib.dpd_cross_gather(L.ptr(Q), L.ptr(vox), L.ptr(mask), L.ptr(slot), L.ptr(ucount), L.ptr(fvS[i0:i0 + ca]), None, ca, Cq, N, m,
                                      P.k, P.KP, p["Xu"], ck.cap, p["Xt"], p["uid"], p["maskr"], p["cnt"], s), "dpd_cross_gather")
@@ -195,54 +203,19 @@ def dpdist_matrix(model_or_params, cloudsA, cloudsB=None, max_rows=16384, return
 
 
 # ---- the differentiable form ----
-class _BwdChunk:
-    """the buffers of one BACKWARD chunk of `ca` surface clouds, carved from one allocation in the order dpd_cross_bwd_workspace_bytes
-    states: the forward's buffers with three kept activations, then the gradient buffers"""
-
-    def __init__(self, lib, ca, Cb, N, m, P, dev):
-        nbytes = lib.dpd_cross_bwd_workspace_bytes(ca, Cb, N, m, P.k, P.KP, P.H)
-        self.cap = lib.dpd_cross_slot_capacity(ca, Cb, N, m)
-        if not nbytes or not self.cap:
-            raise ValueError("dpdist_matrix: shape not supported by the backward (clouds per chunk %d x %d, N %d, m %d, k %d, H %d)"
-                             % (ca, Cb, N, m, P.k, P.H))
-        self.ca = ca
-        rows_p = (ca * Cb * N + 31) // 32 * 32
-        act = rows_p * P.H * 4
-        self.arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        off = 0
-        self.ptr = {}
-        for name, size in (("Xu", (P.KP - 32) * self.cap * 4), ("Xt", rows_p * 32 * 4), ("uid", rows_p * 4), ("maskr", rows_p * 4), ("cnt", 16),
-                           ("Pu", self.cap * P.H * 4), ("h1", act), ("h2", act), ("h3", act), ("y", rows_p * 12), ("pred", rows_p * 12),
-                           ("dpred", rows_p * 12), ("dy", rows_p * 12), ("ga", act), ("gb", act), ("dq", rows_p * 12),
-                           ("gs", self.cap * P.H * 4), ("dXs", self.cap * P.KP * 4), ("dfv", ca * m ** 3 * F * 4)):
-            self.ptr[name] = self.arena.data_ptr() + off
-            off += (size + 255) // 256 * 256
-        if off != nbytes:
-            raise RuntimeError("dpd_cross_bwd_workspace_bytes and dpdist_amd.pairwise disagree on the layout (%d != %d)" % (off, nbytes))
-
-
 def _directed_bwd(lib, s, P, cp, m, sigma, S, fvS, Q, Gd, need_s, need_q, max_rows, chunks):
     """one direction of the backward: surface clouds S [Cs, N, 3] (Fisher vectors fvS), queries Q [Cq, N, 3], upstream Gd [Cs, Cq] of that
     direction's matrix -> (surface route [Cs, N, 3] | None, query route [Cq, N, 3] | None)"""
     Cs, (Cq, N, _) = S.shape[0], Q.shape
     dev = Q.device
     G = m ** 3
-    mask = torch.empty(Cq * N, device=dev, dtype=torch.float32)
-    idx = torch.empty(Cq * N * 2 + 3 * G + 2, device=dev, dtype=torch.int32)     # vox, qlist, slot_of_vox + count, slot_start, slot_vox
-    vox, qlist, slot, start, svox = idx[:Cq * N], idx[Cq * N:2 * Cq * N], idx[2 * Cq * N:][:G + 1], idx[2 * Cq * N + G + 1:][:G + 1], idx[2 * Cq * N + 2 * G + 2:]
-    ucount = slot[G:]
-    _check(lib.dpd_cross_index(L.ptr(Q), Cq, N, m, L.ptr(mask), L.ptr(vox), L.ptr(slot), L.ptr(ucount), s), "dpd_cross_index")
+    mask, vox, slot, ucount, rest = _index(lib, s, Q, m, Cq * N + 2 * G + 1)
+    qlist, start, svox = rest[:Cq * N], rest[Cq * N:][:G + 1], rest[Cq * N + G + 1:]
     _check(lib.dpd_cross_invert(L.ptr(vox), L.ptr(slot), L.ptr(ucount), Cq, N, m, L.ptr(start), L.ptr(qlist), L.ptr(svox), s), "dpd_cross_invert")
     gS = torch.empty(Cs, N, 3, device=dev, dtype=torch.float32) if need_s else None
     gQ = torch.zeros(Cq, N, 3, device=dev, dtype=torch.float32) if need_q else None
     ws = torch.empty(lib.dpd_mfv3d_bwd_workspace_bytes(Cs, m), device=dev, dtype=torch.uint8) if need_s else None
-    per = chunk_clouds(Cs, Cq * N, max_rows)
-    for i0 in range(0, Cs, per):
-        ca = min(per, Cs - i0)
-        key = (ca, Cq)
-        ck = chunks.get(key)
-        if ck is None:
-            ck = chunks[key] = _BwdChunk(lib, ca, Cq, N, m, P, dev)
+    for i0, ca, ck in _walk(lib, P, m, Cs, Q, max_rows, chunks, backward=True):
         p = ck.ptr
         _check(lib.dpd_cross_gather(L.ptr(Q), L.ptr(vox), L.ptr(mask), L.ptr(slot), L.ptr(ucount), L.ptr(fvS[i0:i0 + ca]), None, ca, Cq, N, m,
                                      P.k, P.KP, p["Xu"], ck.cap, p["Xt"], p["uid"], p["maskr"], p["cnt"], s), "dpd_cross_gather")

@@ -215,11 +215,28 @@ int dpd_decoder_fwd_unique(const float* Xu, const float* Xt, const int32_t* uid,
  *   Needs H % 64 == 0, KP % 32 == 0, slot_cap % 4 == 0, ldu % 4 == 0.
  * dpd_cross_workspace_bytes: the bytes of one chunk's buffers -- Xu (ldu = the slot capacity), Xt, uid, maskr, cnt, Pu, act0, act1, y,
  *   pred, Dd, in this order, each rounded up to 256 bytes; 0 for a shape the entries refuse.
+ * dpd_cross_carve: the library owns that layout (and the backward's, dpd_cross_bwd_workspace_bytes below): one caller-owned allocation
+ *   `mem` of at least the matching report's bytes -> the chunk's shape, slot capacity, rows_p, total bytes and one pointer per buffer, at
+ *   offsets that are multiples of 256 (mem itself need not be aligned).  backward = 0: the forward's buffers, h1..h3 and every gradient
+ *   buffer NULL; backward != 0: the backward's, act0, act1 and Dd NULL.  Host-side pointer arithmetic only (no device call, nothing but
+ *   `out` is dereferenced).  DPD_E_NULL for a null mem / out, DPD_E_UNSUPPORTED exactly where the matching report returns 0,
+ *   DPD_E_WORKSPACE for bytes below the report; on any error every member of *out is zero.
  * Size limit: the GEMMs address their matrices with 32-bit byte offsets, so Xu [KP - 32, ldu], Pu [slot_cap, H] and the activation
  *   buffers [rows_p, H] must each stay below 4 GiB (DPD_E_UNSUPPORTED from the gather and the decoder, 0 from the workspace report):
  *   take fewer surface clouds per chunk.                                                                                          */
 int dpd_cross_slot_capacity(int Ca_chunk, int Cb, int N, int m);
 size_t dpd_cross_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H);
+typedef struct dpd_cross_chunk {
+    int Ca_chunk, Cb, N, m, k, KP, H;
+    int slot_cap, rows_p;       /* dpd_cross_slot_capacity; Ca_chunk Cb N rounded up to 32 */
+    size_t bytes;               /* the matching workspace report */
+    void *Xu, *Xt, *uid, *maskr, *cnt, *Pu;      /* both forms */
+    void *act0, *act1, *Dd;                      /* the forward only */
+    void *h1, *h2, *h3;                          /* the backward only, as the buffers below */
+    void *y, *pred;                              /* both forms */
+    void *dpred, *dy, *ga, *gb, *dq, *gs, *dXs, *dfv;
+} dpd_cross_chunk;
+int dpd_cross_carve(void* mem, size_t bytes, int Ca_chunk, int Cb, int N, int m, int k, int KP, int H, int backward, dpd_cross_chunk* out);
 int dpd_cross_index(const float* q, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox, int32_t* ucount, void* stream);
 int dpd_cross_gather(const float* q, const int32_t* vox, const float* mask, const int32_t* slot_of_vox, const int32_t* ucount,
                      const float* fv, const float* ssq, int Ca_chunk, int Cb, int N, int m, int k, int KP, float* Xu, int ldu, float* Xt,
@@ -255,8 +272,8 @@ int dpd_decoder_fwd_cross(const float* Xu, int ldu, int slot_cap, const float* X
  *   of gs, slot product and scatter skipped; gs, dXs, slot_vox may be NULL); gQ = NULL: the query set needs none (dq may be NULL).
  * dpd_cross_bwd_workspace_bytes: the bytes of one backward chunk -- Xu, Xt, uid, maskr, cnt, Pu, h1, h2, h3, y, pred (the forward's
  *   buffers with three activations), then dpred, dy [rows_p, 3], ga, gb [rows_p, H], dq [rows_p, 3], gs [slot_cap, H], dXs [slot_cap, KP],
- *   dfv [Ca_chunk, m^3, 20], in this order, each rounded up to 256 bytes; 0 for a refused shape: one the forward refuses, H > 4096, or
- *   dXs beyond the 4 GiB the GEMMs address (DPD_E_UNSUPPORTED from the entries).                                                    */
+ *   dfv [Ca_chunk, m^3, 20], in this order, each rounded up to 256 bytes (dpd_cross_carve with backward = 1 hands the pointers out); 0 for a
+ *   refused shape: one the forward refuses, H > 4096, or dXs beyond the 4 GiB the GEMMs address (DPD_E_UNSUPPORTED from the entries). */
 size_t dpd_cross_bwd_workspace_bytes(int Ca_chunk, int Cb, int N, int m, int k, int KP, int H);
 int dpd_cross_invert(const int32_t* vox, const int32_t* slot_of_vox, const int32_t* ucount, int Cb, int N, int m, int32_t* slot_start,
                      int32_t* qlist, int32_t* slot_vox, void* stream);

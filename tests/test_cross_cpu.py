@@ -93,18 +93,95 @@ def test_cross_workspace_report(lib):
 
 
 def test_python_layout_matches_the_report(lib):
-    """dpdist_amd.pairwise carves one allocation in the order the header states: the two must agree on the total"""
+    """dpdist_amd.pairwise has the library carve one allocation (dpd_cross_carve): every member at the running sum of the sizes that
+    test_cross_workspace_report spells out, so two equal-sized members swapped on either side are caught"""
     from dpdist_amd import pairwise
 
     class _P:
         k, KP, H = 5, KP, 256
 
-    ck = pairwise._Chunk(lib, 2, 3, 36, 8, _P, "cpu")
+    ck = pairwise._Chunk(lib, 2, 3, 36, 8, _P, "cpu", backward=False)
     base = ck.arena.data_ptr()
     assert ck.cap == 224 and ck.ptr["Xu"] == base and all((v - base) % 256 == 0 for v in ck.ptr.values())
     order = ["Xu", "Xt", "uid", "maskr", "cnt", "Pu", "act0", "act1", "y", "pred", "Dd"]
     assert [n for n, _ in sorted(ck.ptr.items(), key=lambda kv: kv[1])] == order
+    al = lambda b: (b + 255) // 256 * 256      # noqa: E731
+    rows_p, c, H = 224, 224, 256
+    sizes = [al((KP - 32) * c * 4), al(rows_p * 128), al(rows_p * 4), al(rows_p * 4), 256, al(c * H * 4), al(rows_p * H * 4), al(rows_p * H * 4),
+             al(rows_p * 12), al(rows_p * 12), al(6 * 4)]
+    off = 0
+    for name, size in zip(order, sizes):
+        assert ck.ptr[name] - base == off, name
+        off += size
+    assert off == ck.arena.numel() == lib.dpd_cross_workspace_bytes(2, 3, 36, 8, 5, KP, 256)
     assert ck.Dd(6).numel() == 6 and ck.Dd(6).data_ptr() == ck.ptr["Dd"]
+    with pytest.raises(ValueError, match="not supported"):
+        pairwise._Chunk(lib, 2, 3, 36, 11, _P, "cpu")
+
+
+SHAPES = [(2, 3, 36, 8, 5, KP, 256), (3, 2, 64, 8, 5, KP, 256), (1, 1, 1, 8, 5, KP, 64), (8, 32, 64, 8, 5, KP, 1024)]
+FORWARD_ONLY, BACKWARD_ONLY = ("act0", "act1", "Dd"), ("h1", "h2", "h3", "dpred", "dy", "ga", "gb", "dq", "gs", "dXs", "dfv")
+BASE = (1 << 30) + 16                                     # a fake, unaligned "device address": nothing is dereferenced
+
+
+def _carve(lib, shape, backward, nbytes=None, base=BASE):
+    from dpdist_amd import lib as L
+    ck = L.CrossChunk()
+    for n in L.CrossChunk.BUFFERS:                        # stale pointers: a refusal must leave none
+        setattr(ck, n, 1 << 20)
+    report = lib.dpd_cross_bwd_workspace_bytes if backward else lib.dpd_cross_workspace_bytes
+    rc = lib.dpd_cross_carve(ctypes.c_void_p(base), report(*shape) if nbytes is None else nbytes, *shape, backward, ck)
+    return rc, ck, {n: getattr(ck, n) for n in L.CrossChunk.BUFFERS if getattr(ck, n) is not None}
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_carve_ends_at_the_report(lib, shape, backward):
+    """both forms: offsets are multiples of 256 from an unaligned base, the members the form lacks are NULL, the last member's offset
+    plus its padded size is the matching report, and the struct carries the shape, the slot capacity and rows_p"""
+    Ca, Cb, N, m, k, kp, H = shape
+    rc, ck, ptr = _carve(lib, shape, backward)
+    assert rc == 0
+    assert set(ptr) == set(ck.BUFFERS) - set(FORWARD_ONLY if backward else BACKWARD_ONLY)
+    assert min(ptr.values()) == ptr["Xu"] == BASE and all((v - BASE) % 256 == 0 for v in ptr.values())
+    report = (lib.dpd_cross_bwd_workspace_bytes if backward else lib.dpd_cross_workspace_bytes)(*shape)
+    last, last_bytes = ("dfv", Ca * m ** 3 * 20 * 4) if backward else ("Dd", Ca * Cb * 4)
+    assert max(ptr, key=ptr.get) == last and ptr[last] - BASE + (last_bytes + 255) // 256 * 256 == report == ck.bytes
+    assert (ck.Ca_chunk, ck.Cb, ck.N, ck.m, ck.k, ck.KP, ck.H) == shape
+    assert ck.slot_cap == lib.dpd_cross_slot_capacity(Ca, Cb, N, m) and ck.rows_p == (Ca * Cb * N + 31) // 32 * 32
+
+
+REFUSED = [(3, 2, 64, 8, 4, KP, 256), (3, 2, 64, 11, 5, KP, 256), (3, 2, 64, 8, 5, KP - 32, 256), (3, 2, 64, 8, 5, KP, 200),
+           (0, 2, 64, 8, 5, KP, 256), (512, 32, 64, 8, 5, KP, 1024), (841, 32, 64, 8, 5, KP, 64)]
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+def test_carve_refuses_what_the_reports_refuse(lib, backward):
+    """DPD_E_UNSUPPORTED exactly where the matching report returns 0, and no pointer left set; the neighbours that fit are carved"""
+    report = lib.dpd_cross_bwd_workspace_bytes if backward else lib.dpd_cross_workspace_bytes
+    refused = REFUSED + ([(830, 32, 64, 8, 5, KP, 64), (3, 2, 64, 8, 5, KP, 4160)] if backward else [])
+    for shape in refused:
+        assert report(*shape) == 0, shape
+        rc, ck, ptr = _carve(lib, shape, backward, nbytes=1 << 62)
+        assert rc == -3 and not ptr and ck.bytes == 0, shape
+    fits = [(511, 32, 64, 8, 5, KP, 1024), (829 if backward else 840, 32, 64, 8, 5, KP, 64)]
+    for shape in fits + ([] if backward else [(830, 32, 64, 8, 5, KP, 64), (3, 2, 64, 8, 5, KP, 4160)]):
+        rc, ck, ptr = _carve(lib, shape, backward)
+        assert rc == 0 and ck.bytes == report(*shape) > 0, shape
+    if not backward:
+        assert _carve(lib, (840, 32, 64, 8, 5, KP, 64), 1)[0] == -3      # the backward's limit is 829 clouds
+
+
+@pytest.mark.parametrize("backward", [0, 1])
+def test_carve_checks_its_arguments(lib, backward):
+    from dpdist_amd import lib as L
+    shape = SHAPES[0]
+    report = (lib.dpd_cross_bwd_workspace_bytes if backward else lib.dpd_cross_workspace_bytes)(*shape)
+    rc, ck, ptr = _carve(lib, shape, backward, nbytes=report - 1)
+    assert rc == -4 and not ptr
+    assert _carve(lib, shape, backward, nbytes=report)[0] == 0
+    assert lib.dpd_cross_carve(None, report, *shape, backward, L.CrossChunk()) == -1
+    assert lib.dpd_cross_carve(ctypes.c_void_p(BASE), report, *shape, backward, None) == -1
 
 
 def test_shapes_beyond_the_gemms_32_bit_offsets_are_refused(lib):

@@ -10,7 +10,7 @@ import torch
 KP = 2528
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("dpd_cross_bwd_workspace_bytes", "dpd_cross_invert", "dpd_decoder_fwd_cross_keep", "dpd_cross_slot_sum", "dpd_cross_scatter",
-       "dpd_cross_bwd")
+       "dpd_cross_bwd", "dpd_cross_carve")
 
 
 @pytest.fixture(scope="module")
@@ -76,21 +76,31 @@ def test_backward_workspace_report(lib):
 
 
 def test_python_layout_matches_the_report(lib):
-    """dpdist_amd.pairwise carves one allocation in the order the header states: the two must agree on the total"""
+    """dpdist_amd.pairwise has the library carve one allocation (dpd_cross_carve): every member at the running sum of the sizes that
+    test_backward_workspace_report spells out, so two equal-sized members swapped on either side are caught"""
     from dpdist_amd import pairwise
 
     class _P:
         k, KP, H = 5, KP, 256
 
-    ck = pairwise._BwdChunk(lib, 2, 3, 36, 8, _P, "cpu")
+    ck = pairwise._Chunk(lib, 2, 3, 36, 8, _P, "cpu", backward=True)
     base = ck.arena.data_ptr()
     assert ck.cap == 224 and ck.ptr["Xu"] == base and all((v - base) % 256 == 0 for v in ck.ptr.values())
     order = ["Xu", "Xt", "uid", "maskr", "cnt", "Pu", "h1", "h2", "h3", "y", "pred", "dpred", "dy", "ga", "gb", "dq", "gs", "dXs", "dfv"]
     assert [n for n, _ in sorted(ck.ptr.items(), key=lambda kv: kv[1])] == order
-    assert ck.arena.numel() == lib.dpd_cross_bwd_workspace_bytes(2, 3, 36, 8, 5, KP, 256)
+    al = lambda b: (b + 255) // 256 * 256      # noqa: E731
+    rows_p, c, H = 224, 224, 256
+    act, row3 = al(rows_p * H * 4), al(rows_p * 12)
+    sizes = [al((KP - 32) * c * 4), al(rows_p * 128), al(rows_p * 4), al(rows_p * 4), 256, al(c * H * 4), act, act, act, row3, row3,
+             row3, row3, act, act, row3, al(c * H * 4), al(c * KP * 4), al(2 * 512 * 20 * 4)]
+    off = 0
+    for name, size in zip(order, sizes):
+        assert ck.ptr[name] - base == off, name
+        off += size
+    assert off == ck.arena.numel() == lib.dpd_cross_bwd_workspace_bytes(2, 3, 36, 8, 5, KP, 256)
     assert ck.ptr["dfv"] + 2 * 512 * 20 * 4 <= base + ck.arena.numel()
     with pytest.raises(ValueError, match="not supported"):
-        pairwise._BwdChunk(lib, 2, 3, 36, 11, _P, "cpu")
+        pairwise._Chunk(lib, 2, 3, 36, 11, _P, "cpu", backward=True)
 
 
 def test_chunks_beyond_the_gemms_32_bit_offsets_are_refused(lib):
