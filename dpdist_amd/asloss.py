@@ -141,6 +141,9 @@ def acquire(P, flat, B, N, m, k, sigma, device):
         return None
     if L.DTYPES[P.compute_dtype] != 0 and not PLANES:
         return None                 # A/B reference of round 4: the plane types without persistent planes
+    from . import ops
+    if ops.encoder_tiled(N, m) or (m <= 8 and ops.encoder_tiled(N, m, ops.FITS_BWD_SLICED)):
+        return None                 # clouds the plain encoder entries cannot hold in LDS: the engine calls those, the allocating path tiles
     private = _private is not None
     pool = _private if private else P.__dict__.setdefault("_asloss_engines", {})
     key = (B, N, m, k, float(sigma), L.DTYPES[P.compute_dtype], str(device), 0 if private else torch.cuda.current_stream(device).cuda_stream)

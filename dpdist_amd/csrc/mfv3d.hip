@@ -12,6 +12,7 @@
 //   lane>>3 <-> one eighth of the points, 20 running statistics (sum/max/min) in registers, the eight point groups merged with
 //   three __shfl_xor; power-1/2 values staged through LDS and written with coalesced float4 stores; a second small kernel
 //   applies the per-channel L2 norm over the Gaussian axis.  Backward: sliced over the POINTS (two launches) or one launch.
+//   Clouds whose tables do not fit the LDS (N > 705 at m = 8): the same grids walking the points in TILES (the *_tiled_kernel forms below).
 #include <cstdlib>
 
 #include "common.h"
@@ -1123,6 +1124,370 @@ static int set_lds(size_t lds) {
     return ensure_dyn_lds(lds_opt, (const void*)Kern, lds);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The encoder over TILES of points (dpd_mfv3d_fwd_tiled / dpd_mfv3d_bwd_tiled): the kernels above stage the tables of ALL N points of a
+// cloud (or of a point slice) in LDS, which caps N at 705 (forward, m = 8), 402 / 1636 (backward).  Every Fisher-vector statistic is a
+// sum, a max or a min over the points, so the kernels below walk the points in tiles of at most `tile`, rebuild the tables {z, e/S} for
+// the tile's points only and carry the statistics in REGISTERS across the tiles; everything after the point loop (merge of the point
+// groups, power-1/2, coalesced store, mfv3d_norm_kernel; combine kernel of the backward) runs once, as in the kernels above.
+// Same expressions per (point, Gaussian); the sums are taken in another order (tile by tile), so the results differ from the plain
+// entries in the last bits and are held to the same bars against the float64 oracle.
+//
+// Forward: the eight-point-group formulation of mfv3d_fwd_kernel (any N, any tile).  Grid and Gaussian slices as there.
+//   * the 0/0 flag accumulates over ALL tiles (s_bad is cleared once, before the first tile);
+//   * the mean's 1 / N and dpi_den = sqrt(w) N use the cloud's N (MfvConst), never the tile's;
+//   * a ragged last tile (down to one point) leaves some of the eight point groups empty: they add nothing to the running statistics,
+//     which start at 0 / -inf / +inf;
+//   * m = 9, 10: a slice holds 183 / 250 Gaussians, more than the 16 waves x 8 of one batch.  NB = 2 keeps ONE STATISTICS SET PER BATCH
+//     in registers (2 x 20 running values per lane) instead of making the batch the outer loop, which would rebuild every table twice:
+//     the kernel has 128 VGPRs per lane at 1024 threads and needs 93 for both sets, 66 for one (resource table in DESIGN section 3), no scratch.
+// dynamic LDS (floats): zq[3*tile*m*2] | S[3*tile] | minz2[3*tile] | stage[slice*21] | flag
+// ------------------------------------------------------------------------------------------------------
+template <int NB>
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_tiled_kernel(const float* __restrict__ pts, float* __restrict__ fv, MfvConst k,
+                                                                       int gslice, int tile) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int N = k.N, G = k.G, m = k.m;
+    float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][np_][m], np_ <= tile
+    float* s_S = sm + 6 * tile * m;                 // [3][np_]
+    float* s_mz = s_S + 3 * tile;                   // [3][np_] min_i z^2
+    float* s_stage = s_mz + 3 * tile;               // [gslice][21]
+    int* s_bad = reinterpret_cast<int*>(s_stage + gslice * kFP);
+
+    const int tid = threadIdx.x, c = blockIdx.x / kSlices, sl = blockIdx.x % kSlices;
+    const int g0 = sl * gslice, gcount = max(0, min(G, g0 + gslice) - g0);
+    const int lane = tid & 63, wave = tid >> 6, grp = lane >> 3;
+    const int lg_m = lg_or_neg(m);
+    if (tid == 0) *s_bad = 0;
+
+    // this lane's Gaussian of every batch: centre (x,y,z) = (l[j], l[i], l[t])  (:47-48)
+    int gl[NB], gi[NB], gj[NB], gt[NB];
+    bool live[NB], act[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int gbase = wave * 8 + b * 16 * 8;
+        act[b] = gbase < gcount;                    // wave-uniform
+        gl[b] = gbase + (lane & 7);
+        live[b] = gl[b] < gcount;
+        const int gg = live[b] ? g0 + gl[b] : 0;
+        const int gm = qdiv(gg, m, lg_m);
+        gt[b] = gg - gm * m; gi[b] = qdiv(gm, m, lg_m); gj[b] = gm - gi[b] * m;
+    }
+    float pi_s[NB], pi_mx[NB], mu_s[NB][3], mu_mx[NB][3], mu_mn[NB][3], sg_s[NB][3], sg_mx[NB][3], sg_mn[NB][3];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        pi_s[b] = 0.f; pi_mx[b] = -INFINITY;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            mu_s[b][d] = 0.f; mu_mx[b][d] = -INFINITY; mu_mn[b][d] = INFINITY;
+            sg_s[b][d] = 0.f; sg_mx[b][d] = -INFINITY; sg_mn[b][d] = INFINITY;
+        }
+    }
+    const float inv_dpi = 1.0f / k.dpi_den;
+
+    for (int t0 = 0; t0 < N; t0 += tile) {
+        const int np_ = min(tile, N - t0);
+        const float* p = pts + ((size_t)c * N + t0) * 3;
+        const int lg_np = lg_or_neg(np_);
+        // ---- tables of the tile's points: the passes of mfv3d_fwd_kernel ---------------------------------------------
+        for (int e = tid; e < 3 * np_ * m; e += kFwdThreads) {
+            const int em = qdiv(e, m, lg_m), i = e - em * m, a = qdiv(em, np_, lg_np), n = em - a * np_;
+            const float z = (p[n * 3 + a] - k.ax.c[i]) / k.sigma;      // (batch_points - batch_mu) / batch_sig  (:87)
+            s_zq[e] = make_float2(z, expf(-0.5f * (z * z)));
+        }
+        __syncthreads();
+        for (int e = tid; e < 3 * np_; e += kFwdThreads) {             // e = a*np_ + n
+            float S = 0.f, mz = INFINITY;
+            for (int i = 0; i < m; ++i) {
+                const float2 v = s_zq[e * m + i];
+                S += v.y;
+                mz = fminf(mz, v.x * v.x);
+                if (v.x != v.x) mz = v.x;
+            }
+            s_S[e] = S;
+            s_mz[e] = mz;
+        }
+        __syncthreads();
+        for (int e = tid; e < 3 * np_ * m; e += kFwdThreads) s_zq[e].y = s_zq[e].y / s_S[qdiv(e, m, lg_m)];
+        for (int n = tid; n < np_; n += kFwdThreads) {
+            // the reference's 0/0: every w*p_ng == 0  <=>  the largest one is (p is monotone in -|z|^2); over ALL tiles
+            const float pmax = pdf(k, sqrtf(s_mz[n]), sqrtf(s_mz[np_ + n]), sqrtf(s_mz[2 * np_ + n]));
+            if (!(pmax * k.w > 0.f)) atomicOr(s_bad, 1);               // also catches NaN inputs
+        }
+        __syncthreads();
+        const float2* zqx = s_zq;
+        const float2* zqy = s_zq + np_ * m;
+        const float2* zqz = s_zq + 2 * np_ * m;
+        // ---- the tile's share of the running statistics: lane & 7 <-> Gaussian, lane >> 3 <-> an eighth of the TILE's points ----
+        const int npg = (np_ + 7) / 8;
+        const int n1 = min(np_, (grp + 1) * npg);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (!act[b]) continue;
+            for (int n = grp * npg; n < n1; ++n) {
+                const float2 vx = zqx[n * m + gj[b]], vy = zqy[n * m + gi[b]], vz = zqz[n * m + gt[b]];
+                const float z[3] = {vx.x, vy.x, vz.x};
+                const float Q = (vx.y * vy.y) * vz.y;                              // :73-74, factorised
+                const float dpi = (Q - k.w) * inv_dpi;                             // :78
+                pi_s[b] += dpi;
+                pi_mx[b] = fmaxf(pi_mx[b], dpi);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const float a = Q * z[d];                                       // :87
+                    const float bb = Q * (z[d] * z[d] - 1.0f);                      // :100
+                    mu_s[b][d] += a; mu_mx[b][d] = fmaxf(mu_mx[b][d], a); mu_mn[b][d] = fminf(mu_mn[b][d], a);
+                    sg_s[b][d] += bb; sg_mx[b][d] = fmaxf(sg_mx[b][d], bb); sg_mn[b][d] = fminf(sg_mn[b][d], bb);
+                }
+            }
+        }
+        __syncthreads();        // the next tile overwrites the tables
+    }
+
+    // ---- once, after the last tile: merge the eight point groups (as in mfv3d_fwd_kernel: DPP row rotate, ds_swizzle, v_permlane32_swap) ----
+    const float invN = 1.0f / (float)N;
+    auto x8 = [](float v) { return dpp_move<0x128>(v); };                                                  // row_ror:8 = lane ^ 8
+    auto x16 = [](float v) { return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F)); };   // bit mode: xor 16
+    auto sumg = [&](float v) { v += x8(v); v += x16(v); return sum_x32(v); };
+    auto maxg = [&](float v) { v = fmaxf(v, x8(v)); v = fmaxf(v, x16(v)); return max_x32(v); };
+    auto ming = [&](float v) { v = fminf(v, x8(v)); v = fminf(v, x16(v)); return min_x32(v); };
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (!act[b]) continue;
+        float v[kF];
+        v[0] = sumg(pi_s[b]) * invN;                                            // :81 reduce_mean over the CLOUD's N
+        v[1] = maxg(pi_mx[b]);                                                  // :80
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {                                           // :89-98, :102-109
+            v[2 + d] = (sumg(mu_s[b][d]) * invN) * k.mu_scale;
+            v[5 + d] = maxg(mu_mx[b][d]) * k.mu_scale;
+            v[8 + d] = ming(mu_mn[b][d]) * k.mu_scale;
+            v[11 + d] = (sumg(sg_s[b][d]) * invN) * k.sig_scale;
+            v[14 + d] = maxg(sg_mx[b][d]) * k.sig_scale;
+            v[17 + d] = ming(sg_mn[b][d]) * k.sig_scale;
+        }
+        if (live[b] && grp == 0) {
+#pragma unroll
+            for (int f = 0; f < kF; ++f) s_stage[gl[b] * kFP + f] = v[f];
+        }
+    }
+    __syncthreads();
+    // power-1/2 normalisation (:119-121) and coalesced store of the slice, as in mfv3d_fwd_kernel
+    float* out = fv + ((size_t)c * G + g0) * kF;
+    const bool bad = *s_bad != 0;
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int i4 = tid; i4 < gcount * kF / 4; i4 += kFwdThreads) {
+        const int e = i4 * 4, g = e / kF, f = e % kF;
+        const float* sp = s_stage + g * kFP + f;
+        float4 o = make_float4(pnorm(sp[0]), pnorm(sp[1]), pnorm(sp[2]), pnorm(sp[3]));
+        if (bad) o = make_float4(qnan, qnan, qnan, qnan);   // 0/0 at :74 poisons every statistic of the cloud
+        *reinterpret_cast<float4*>(out + e) = o;
+    }
+}
+
+// Backward over tiles: the three-launch structure and the workspace layout of the sliced form (kSlices records of kRec rows per cloud;
+// mfv3d_bwd_combine_kernel runs unchanged in between).  Each of the kSlices point slices walks its ceil(N / kSlices) points in tiles.
+//   statistics: tiles once for the sums / maxima / minima, tiles AGAIN for the 13 tie counts against the slice's extrema (tables rebuilt by
+//               the same code, the same eval_pq expressions: equality is exact), one record per slice;
+//   apply:      per tile tables -> T_n -> dx_n of the tile's points -> store; a tile needs nothing of the other tiles beyond the combined record.
+// All sums in a fixed order, no float atomics.  An empty slice (or tile count 0) writes the -inf / +inf / 0 record, as the sliced form does.
+// dynamic LDS (floats): statistics zq[6*tile*m] | S[3*tile]; apply zq[6*tile*m] | S[3*tile] | T[tile] | part[16*tile*3]
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_stats_tiled_kernel(const float* __restrict__ pts, float* __restrict__ part,
+                                                                             MfvConst k, int nslice, int tile) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int N = k.N, G = k.G, m = k.m;
+    const int c = blockIdx.x / kSlices, sl = blockIdx.x % kSlices;
+    const int n0 = min(N, sl * nslice), np_ = min(N, n0 + nslice) - n0;
+    float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][tp][m], tp <= tile
+    float* s_S = sm + 6 * tile * m;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
+    const float* p = pts + (size_t)c * N * 3;
+    const int g = wave * 32 + (lane & 31);
+    const bool live = g < G;
+    const int gg = live ? g : 0;
+    const int gi = gg / (m * m), gj = (gg / m) % m, gt = gg % m;
+    const float inv_dpi = 1.0f / k.dpi_den;
+    float rec[kRec];
+    {
+        float pi_s = 0.f, pi_mx = -INFINITY;
+        float mu_s[3] = {0.f, 0.f, 0.f}, mu_mx[3] = {-INFINITY, -INFINITY, -INFINITY}, mu_mn[3] = {INFINITY, INFINITY, INFINITY};
+        float sg_s[3] = {0.f, 0.f, 0.f}, sg_mx[3] = {-INFINITY, -INFINITY, -INFINITY}, sg_mn[3] = {INFINITY, INFINITY, INFINITY};
+        for (int t0 = 0; t0 < np_; t0 += tile) {
+            const int tp = min(tile, np_ - t0);
+            build_tables(p, n0 + t0, tp, k, s_zq, s_S, tid);
+            const float2* zqx = s_zq;
+            const float2* zqy = s_zq + tp * m;
+            const float2* zqz = s_zq + 2 * tp * m;
+            const int hpts = (tp + 1) / 2;
+            const int nbeg = half * hpts, nend = min(tp, (half + 1) * hpts);
+            for (int n = nbeg; n < nend; ++n) {
+                const PQ q = eval_pq(zqx[n * m + gj], zqy[n * m + gi], zqz[n * m + gt], k.w, inv_dpi);
+                pi_s += q.dpi; pi_mx = fmaxf(pi_mx, q.dpi);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    mu_s[d] += q.a[d]; mu_mx[d] = fmaxf(mu_mx[d], q.a[d]); mu_mn[d] = fminf(mu_mn[d], q.a[d]);
+                    sg_s[d] += q.b[d]; sg_mx[d] = fmaxf(sg_mx[d], q.b[d]); sg_mn[d] = fminf(sg_mn[d], q.b[d]);
+                }
+            }
+            __syncthreads();    // the next tile overwrites the tables
+        }
+        rec[0] = sum_x32(pi_s);            // SUMS here (the mean's 1/N is applied after the combine)
+        rec[1] = max_x32(pi_mx);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            rec[2 + d] = sum_x32(mu_s[d]);
+            rec[5 + d] = max_x32(mu_mx[d]);
+            rec[8 + d] = min_x32(mu_mn[d]);
+            rec[11 + d] = sum_x32(sg_s[d]);
+            rec[14 + d] = max_x32(sg_mx[d]);
+            rec[17 + d] = min_x32(sg_mn[d]);
+        }
+    }
+    {
+        float cnt[13];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) cnt[i] = 0.f;
+        for (int t0 = 0; t0 < np_; t0 += tile) {
+            const int tp = min(tile, np_ - t0);
+            build_tables(p, n0 + t0, tp, k, s_zq, s_S, tid);
+            const float2* zqx = s_zq;
+            const float2* zqy = s_zq + tp * m;
+            const float2* zqz = s_zq + 2 * tp * m;
+            const int hpts = (tp + 1) / 2;
+            const int nbeg = half * hpts, nend = min(tp, (half + 1) * hpts);
+            for (int n = nbeg; n < nend; ++n) {
+                const PQ q = eval_pq(zqx[n * m + gj], zqy[n * m + gi], zqz[n * m + gt], k.w, inv_dpi);
+                cnt[0] += (q.dpi == rec[1]) ? 1.f : 0.f;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    cnt[1 + d] += (q.a[d] == rec[5 + d]) ? 1.f : 0.f;
+                    cnt[4 + d] += (q.a[d] == rec[8 + d]) ? 1.f : 0.f;
+                    cnt[7 + d] += (q.b[d] == rec[14 + d]) ? 1.f : 0.f;
+                    cnt[10 + d] += (q.b[d] == rec[17 + d]) ? 1.f : 0.f;
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < 13; ++i) rec[20 + i] = sum_x32(cnt[i]);
+    }
+    if (live && half == 0) {
+        float* out = part + ((size_t)(c * kSlices + sl) * kRec) * G + g;
+#pragma unroll
+        for (int i = 0; i < kRec; ++i) out[(size_t)i * G] = rec[i];
+    }
+}
+
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_apply_tiled_kernel(const float* __restrict__ pts, const float* __restrict__ comb,
+                                                                             float* __restrict__ dpts, MfvConst k, int nslice, int tile) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int N = k.N, G = k.G, m = k.m;
+    const int c = blockIdx.x / kSlices, sl = blockIdx.x % kSlices;
+    const int n0 = min(N, sl * nslice), np_ = min(N, n0 + nslice) - n0;
+    float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][tp][m]
+    float* s_S = sm + 6 * tile * m;                 // [3][tile]
+    float* s_T = s_S + 3 * tile;                    // [tile]
+    float* s_part = s_T + tile;                     // [16][tile][3]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
+    const float* p = pts + (size_t)c * N * 3;
+    const int g = wave * 32 + (lane & 31);
+    const bool live = g < G;
+    const int gg = live ? g : 0;
+    const int gi = gg / (m * m), gj = (gg / m) % m, gt = gg % m;
+    const float inv_dpi = 1.0f / k.dpi_den;
+    // d raw statistic and the global extrema of this lane's Gaussian, from mfv3d_bwd_combine_kernel
+    float dr[kF], raw[kF];
+    {
+        const float* pc = comb + (size_t)c * kSlices * kRec * G + gg;
+        const int mm[13] = {1, 5, 6, 7, 8, 9, 10, 14, 15, 16, 17, 18, 19};
+#pragma unroll
+        for (int f = 0; f < kF; ++f) { dr[f] = live ? pc[(size_t)f * G] : 0.f; raw[f] = 0.f; }
+#pragma unroll
+        for (int i = 0; i < 13; ++i) raw[mm[i]] = pc[(size_t)(20 + i) * G];
+    }
+    for (int t0 = 0; t0 < np_; t0 += tile) {
+        const int tp = min(tile, np_ - t0);
+        build_tables(p, n0 + t0, tp, k, s_zq, s_S, tid);
+        const float2* zqx = s_zq;
+        const float2* zqy = s_zq + tp * m;
+        const float2* zqz = s_zq + 2 * tp * m;
+        const int hpts = (tp + 1) / 2;
+        const int nbeg = half * hpts, nend = min(tp, (half + 1) * hpts);
+        // ---- T_n and dz for the tile's points (as P3 / P4 of mfv3d_bwd_kernel) ----------------------------------
+        for (int n = nbeg; n < nend; ++n) {
+            const PQ q = eval_pq(zqx[n * m + gj], zqy[n * m + gi], zqz[n * m + gt], k.w, inv_dpi);
+            float dQ = (dr[0] + ((q.dpi == raw[1]) ? dr[1] : 0.f)) * inv_dpi;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const float ga = dr[2 + d] + ((q.a[d] == raw[5 + d]) ? dr[5 + d] : 0.f) + ((q.a[d] == raw[8 + d]) ? dr[8 + d] : 0.f);
+                const float gb = dr[11 + d] + ((q.b[d] == raw[14 + d]) ? dr[14 + d] : 0.f) + ((q.b[d] == raw[17 + d]) ? dr[17 + d] : 0.f);
+                dQ += ga * q.z[d] + gb * (q.z[d] * q.z[d] - 1.0f);
+            }
+            const float t = half_sum32_hi(live ? dQ * q.Q : 0.f);
+            if ((lane & 31) == 31) s_part[wave * tile + n] = t;
+        }
+        __syncthreads();
+        for (int n = tid; n < tp; n += kFwdThreads) {
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) t += s_part[w * tile + n];
+            s_T[n] = t;
+        }
+        __syncthreads();
+        for (int n = nbeg; n < nend; ++n) {
+            const PQ q = eval_pq(zqx[n * m + gj], zqy[n * m + gi], zqz[n * m + gt], k.w, inv_dpi);
+            float dQ = (dr[0] + ((q.dpi == raw[1]) ? dr[1] : 0.f)) * inv_dpi;
+            float ga[3], gb[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                ga[d] = dr[2 + d] + ((q.a[d] == raw[5 + d]) ? dr[5 + d] : 0.f) + ((q.a[d] == raw[8 + d]) ? dr[8 + d] : 0.f);
+                gb[d] = dr[11 + d] + ((q.b[d] == raw[14 + d]) ? dr[14 + d] : 0.f) + ((q.b[d] == raw[17 + d]) ? dr[17 + d] : 0.f);
+                dQ += ga[d] * q.z[d] + gb[d] * (q.z[d] * q.z[d] - 1.0f);
+            }
+            const float u = dQ - s_T[n];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const float dz = live ? q.Q * (ga[d] + 2.0f * gb[d] * q.z[d]) - q.z[d] * q.Q * u : 0.f;
+                const float t = half_sum32_hi(dz);
+                if ((lane & 31) == 31) s_part[(wave * tile + n) * 3 + d] = t;
+            }
+        }
+        __syncthreads();
+        float* out = dpts + ((size_t)c * N + n0 + t0) * 3;
+        for (int i = tid; i < tp * 3; i += kFwdThreads) {
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) t += s_part[w * tile * 3 + i];
+            out[i] = t / k.sigma;   // z = (x - mu)/sigma
+        }
+        __syncthreads();        // the next tile overwrites the tables and the partial sums
+    }
+}
+
+static size_t fwd_tiled_lds_bytes(int tile, int m, int gslice) {
+    return (size_t)(6 * tile * m + 6 * tile + gslice * kFP + 4) * sizeof(float);
+}
+static size_t bwd_tiled_stats_lds_bytes(int tile, int m) { return (size_t)(6 * tile * m + 3 * tile + 4) * sizeof(float); }
+
+// The library's choice of tile: the largest multiple of 8 whose dynamic LDS stays at or under 64 KiB -- no opt-in attribute, two
+// workgroups per CU (m = 8: 248 forward, 160 backward; m = 10: 168 forward).  0 where there is none (m outside 1..10; backward: m > 8).
+static int default_tile(int m, bool backward) {
+    if (m < 1 || m > 10 || (backward && m > 8)) return 0;
+    const int gslice = (m * m * m + kSlices - 1) / kSlices;
+    int t = 0;
+    while ((backward ? bwd_sliced_lds_bytes(t + 8, m) : fwd_tiled_lds_bytes(t + 8, m, gslice)) <= 64 * 1024) t += 8;
+    return t;
+}
+
+// explicit tile: a multiple of 8, >= 8; 0: the library's.  Clamped to the points there are (rounded up to 8): the tables are sized by it.
+static int resolve_tile(int tile, int m, bool backward, int npoints, int& T) {
+    if (tile < 0 || (tile != 0 && (tile < 8 || tile % 8))) return DPD_E_UNSUPPORTED;
+    T = tile ? tile : default_tile(m, backward);
+    if (T < 8) return DPD_E_UNSUPPORTED;
+    const int cap = (npoints + 7) / 8 * 8;
+    if (T > cap) T = cap;
+    return 0;
+}
+
 }  // namespace dpd
 
 // round-4 forward kernel (pairs of points on the packed VALU, four point groups) where N % 8 == 0; the round-3 kernel otherwise
@@ -1210,6 +1575,72 @@ extern "C" int dpd_mfv3d_bwd(const float* pts, const float* dfv, int C, int N, i
     const size_t lds = bwd_lds_bytes(N, m);
     if (int rc = set_lds<mfv3d_bwd_kernel>(lds)) return rc;
     DPD_LAUNCH(mfv3d_bwd_kernel, dim3(C), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, dfv, dpts, k);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the tiled entries: any 1 <= N <= 4096 (the plain entries above are unchanged and keep their LDS caps) ----
+extern "C" int dpd_mfv3d_fits(int N, int m, int which) {
+    using namespace dpd;
+    if (N < 1 || N > 4096 || m < 1 || m > 10) return 0;
+    const int G = m * m * m;
+    const size_t cap = 160 * 1024;
+    if (which == 0) return fwd_lds_bytes(N, m, (G + kSlices - 1) / kSlices) <= cap;
+    if (G > 512) return 0;
+    if (which == 1 || (which == 2 && N < 2 * kSlices)) return bwd_lds_bytes(N, m) <= cap;
+    if (which == 2) return bwd_sliced_lds_bytes((N + kSlices - 1) / kSlices, m) <= cap;
+    return 0;
+}
+
+extern "C" int dpd_mfv3d_tile(int m, int which) { return dpd::default_tile(m, which != 0); }
+
+extern "C" int dpd_mfv3d_fwd_tiled(const float* pts, int C, int N, int m, float sigma, int tile, float* fv, void* stream) {
+    using namespace dpd;
+    if (!pts || !fv) return DPD_E_NULL;
+    if (C <= 0) return DPD_E_DIM;
+    MfvConst k{};
+    if (int rc = make_const(N, m, sigma, k)) return rc;
+    const int gslice = (k.G + kSlices - 1) / kSlices;
+    if (tile > 0 && fwd_tiled_lds_bytes(tile, m, gslice) > 160 * 1024) return DPD_E_UNSUPPORTED;    // the tile as given must fit
+    int T = 0;
+    if (int rc = resolve_tile(tile, m, false, N, T)) return rc;
+    const size_t lds = fwd_tiled_lds_bytes(T, m, gslice);
+    StageProf prof(stream, DPD_STAGE_ENCODER, (double)C * (N * 12.0 * kSlices + k.G * 80.0));      // every Gaussian slice reads the points
+    if (gslice > 16 * 8) {      // m = 9, 10: two batches of Gaussians per wave
+        if (int rc = set_lds<mfv3d_fwd_tiled_kernel<2>>(lds)) return rc;
+        DPD_LAUNCH(mfv3d_fwd_tiled_kernel<2>, dim3(C * kSlices), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, fv, k, gslice, T);
+    } else {
+        if (int rc = set_lds<mfv3d_fwd_tiled_kernel<1>>(lds)) return rc;
+        DPD_LAUNCH(mfv3d_fwd_tiled_kernel<1>, dim3(C * kSlices), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, fv, k, gslice, T);
+    }
+    DPD_CHECK_LAUNCH();
+    DPD_LAUNCH(mfv3d_norm_kernel, dim3(C), dim3(1024), 0, (hipStream_t)stream, fv, k.G, gslice);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_mfv3d_bwd_tiled(const float* pts, const float* dfv, int C, int N, int m, float sigma, int tile, float* dpts, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    using namespace dpd;
+    if (!pts || !dfv || !dpts) return DPD_E_NULL;
+    if (C <= 0) return DPD_E_DIM;
+    MfvConst k{};
+    if (int rc = make_const(N, m, sigma, k)) return rc;
+    if (k.G > 512) return DPD_E_UNSUPPORTED;   // per-Gaussian gradient record lives in registers: one Gaussian per lane pair
+    if (tile > 0 && bwd_sliced_lds_bytes(tile, m) > 160 * 1024) return DPD_E_UNSUPPORTED;          // the tile as given must fit
+    const int nslice = (N + kSlices - 1) / kSlices;
+    int T = 0;
+    if (int rc = resolve_tile(tile, m, true, nslice, T)) return rc;
+    if (!ws || ws_bytes < dpd_mfv3d_bwd_workspace_bytes(C, m)) return DPD_E_WORKSPACE;
+    const size_t l1 = bwd_tiled_stats_lds_bytes(T, m), l2 = bwd_sliced_lds_bytes(T, m);
+    if (int rc = set_lds<mfv3d_bwd_stats_tiled_kernel>(l1)) return rc;
+    if (int rc = set_lds<mfv3d_bwd_apply_tiled_kernel>(l2)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DPD_LAUNCH(mfv3d_bwd_stats_tiled_kernel, dim3(C * kSlices), dim3(kFwdThreads), l1, s, pts, (float*)ws, k, nslice, T);
+    DPD_CHECK_LAUNCH();
+    DPD_LAUNCH(mfv3d_bwd_combine_kernel, dim3(C * 4), dim3(512), 0, s, dfv, (float*)ws, k);
+    DPD_CHECK_LAUNCH();
+    DPD_LAUNCH(mfv3d_bwd_apply_tiled_kernel, dim3(C * kSlices), dim3(kFwdThreads), l2, s, pts, (const float*)ws, dpts, k, nslice, T);
     DPD_CHECK_LAUNCH();
     return 0;
 }

@@ -3,6 +3,8 @@
 All tensors are torch CUDA float32 (int32 for `vox`), contiguous; outputs are allocated with torch's
 caching allocator and the kernels are enqueued on torch's current HIP stream.
 """
+import functools
+
 import torch
 
 from . import lib as L
@@ -14,24 +16,55 @@ def padded_width(k):
     return L.load().dpd_padded_width(int(k))
 
 
+FITS_FWD, FITS_BWD_ONE, FITS_BWD_SLICED = 0, 1, 2      # include/dpdist_capi.h: dpd_mfv3d_fits
+
+
+@functools.lru_cache(maxsize=None)          # asked once per evaluation of the as-loss node: keep its host path as short as it was
+def encoder_tiled(N, m, which=FITS_FWD):
+    """True where the encoder has to walk the points in tiles: a size the entries take (1 <= N <= 4096, m <= 10) whose tables the plain
+    entry `which` cannot hold in LDS.  Every other shape -- the ones the plain entry runs, and the ones nothing takes, whose refusal is
+    the plain entry's to state -- keeps the plain entry and its launches."""
+    lib = L.load()
+    return 1 <= N <= 4096 and lib.dpd_mfv3d_tile(m, 0) > 0 and not lib.dpd_mfv3d_fits(N, m, which)
+
+
+def encode(lib, pts, C, N, m, sigma, fv, s):
+    """dpd_mfv3d_fwd, or dpd_mfv3d_fwd_tiled at its default tile for the clouds whose tables the plain entry cannot hold
+    -> (return code, name of the entry); pts / fv: ctypes pointers"""
+    if encoder_tiled(N, m):
+        return lib.dpd_mfv3d_fwd_tiled(pts, C, N, m, float(sigma), 0, fv, s), "dpd_mfv3d_fwd_tiled"
+    return lib.dpd_mfv3d_fwd(pts, C, N, m, float(sigma), fv, s), "dpd_mfv3d_fwd"
+
+
+def encode_bwd(lib, pts, dfv, C, N, m, sigma, dpts, ws, ws_bytes, s, which=FITS_BWD_SLICED):
+    """dpd_mfv3d_bwd, or dpd_mfv3d_bwd_tiled (which needs the workspace) beyond the caps of the plain form `which` -> (return code, name)"""
+    if m <= 8 and encoder_tiled(N, m, which):
+        return lib.dpd_mfv3d_bwd_tiled(pts, dfv, C, N, m, float(sigma), 0, dpts, ws, ws_bytes, s), "dpd_mfv3d_bwd_tiled"
+    return lib.dpd_mfv3d_bwd(pts, dfv, C, N, m, float(sigma), dpts, ws, ws_bytes, s), "dpd_mfv3d_bwd"
+
+
 def mfv3d_fwd(pts, m, sigma):
-    """pts [C,N,3] -> fv [C,m^3,20]   (utils/dpdist_util.py:22-141)"""
+    """pts [C,N,3] -> fv [C,m^3,20]   (utils/dpdist_util.py:22-141); any 1 <= N <= 4096: over tiles of points beyond the plain entry's
+    LDS cap (N > 705 at m = 8)"""
     L.req(pts, name="pts")
     C, N, _ = pts.shape
     fv = torch.empty(C, m ** 3, F, device=pts.device, dtype=torch.float32)
-    L.check(L.load().dpd_mfv3d_fwd(L.ptr(pts), C, N, m, float(sigma), L.ptr(fv), L.cur_stream()), "dpd_mfv3d_fwd")
+    L.check(*encode(L.load(), L.ptr(pts), C, N, m, sigma, L.ptr(fv), L.cur_stream()))
     return fv
 
 
 def mfv3d_bwd(pts, dfv, m, sigma, sliced=True):
-    """dfv [C,m^3,20] -> dpts [C,N,3]; sliced: 4 workgroups per cloud through a small workspace (default)."""
+    """dfv [C,m^3,20] -> dpts [C,N,3]; sliced: 4 workgroups per cloud through a small workspace (default).  Beyond the caps of the form
+    asked for (N > 1636 sliced, N > 402 in one launch, at m = 8) the backward runs over tiles of points, with a workspace."""
     L.req(pts, name="pts"), L.req(dfv, name="dfv")
     C, N, _ = pts.shape
     dpts = torch.empty_like(pts)
     lib = L.load()
-    ws = torch.empty(lib.dpd_mfv3d_bwd_workspace_bytes(C, m) // 4, device=pts.device, dtype=torch.float32) if sliced else None
-    L.check(lib.dpd_mfv3d_bwd(L.ptr(pts), L.ptr(dfv), C, N, m, float(sigma), L.ptr(dpts), L.ptr(ws),
-                              ws.numel() * 4 if ws is not None else 0, L.cur_stream()), "dpd_mfv3d_bwd")
+    which = FITS_BWD_SLICED if sliced else FITS_BWD_ONE
+    tiled = m <= 8 and encoder_tiled(N, m, which)
+    ws = torch.empty(lib.dpd_mfv3d_bwd_workspace_bytes(C, m) // 4, device=pts.device, dtype=torch.float32) if sliced or tiled else None
+    L.check(*encode_bwd(lib, L.ptr(pts), L.ptr(dfv), C, N, m, sigma, L.ptr(dpts), L.ptr(ws), ws.numel() * 4 if ws is not None else 0,
+                        L.cur_stream(), which))
     return dpts
 
 
@@ -45,6 +78,10 @@ def front_end(pcA, pcB, noise, m, sigma, k, KP=None):
     B, N, _ = pcA.shape
     dev, lib, s = pcA.device, L.load(), L.cur_stream()
     KP = KP or padded_width(k)
+    if encoder_tiled(N, m):
+        # clouds whose tables the stacked kernel cannot hold: the four-launch form (stack, encoder over tiles, norm, gather) of the module API
+        pts, q = stack_clouds(pcA, pcB, noise)
+        return (pts,) + patch_rows_fwd(q, mfv3d_fwd(pts, m, sigma), m, k, KP)
     f = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)   # noqa: E731
     pts, q, fv, ssq = f(2 * B, N, 3), f(2 * B, N, 3), f(2 * B, m ** 3, F), f(2 * B, 4, F)
     X, mask, vox = f(2 * B * N, KP), f(2 * B * N), torch.empty(2 * B * N, device=dev, dtype=torch.int32)
@@ -174,8 +211,14 @@ def front_end_planes(pcA, pcB, m, sigma, k, planes):
     B, N, _ = pcA.shape
     dev, lib, s = pcA.device, L.load(), L.cur_stream()
     f = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)   # noqa: E731
-    pts, q, fv, ssq = f(2 * B, N, 3), f(2 * B, N, 3), f(2 * B, m ** 3, F), f(2 * B, 4, F)
     mask, vox = f(2 * B * N), torch.empty(2 * B * N, device=dev, dtype=torch.int32)
+    if encoder_tiled(N, m):       # as in front_end: stack, encoder over tiles (normalised fv), gather without the per-slice norms
+        pts, q = stack_clouds(pcA, pcB)
+        fv = mfv3d_fwd(pts, m, sigma)
+        L.check(lib.dpd_patch_rows_fwd_scaled(L.ptr(q), L.ptr(fv), None, 2 * B, N, m, k, planes.KP, None, L.ptr(mask), L.ptr(vox),
+                                              planes.c, s), "dpd_patch_rows_fwd_scaled")
+        return pts, mask, vox
+    pts, q, fv, ssq = f(2 * B, N, 3), f(2 * B, N, 3), f(2 * B, m ** 3, F), f(2 * B, 4, F)
     L.check(lib.dpd_mfv3d_fwd_stacked(L.ptr(pcA), L.ptr(pcB), None, B, N, m, float(sigma), L.ptr(pts), L.ptr(q), L.ptr(fv), L.ptr(ssq), s),
             "dpd_mfv3d_fwd_stacked")
     L.check(lib.dpd_patch_rows_fwd_scaled(L.ptr(q), L.ptr(fv), L.ptr(ssq), 2 * B, N, m, k, planes.KP, None, L.ptr(mask), L.ptr(vox),

@@ -20,6 +20,7 @@ import math
 import torch
 
 from . import lib as L
+from . import ops
 
 F = 20
 
@@ -119,7 +120,7 @@ def _encode(lib, s, pts, m, sigma):
     """pts [C,N,3] -> fv [C,m^3,20], once per set"""
     C, N, _ = pts.shape
     fv = torch.empty(C, m ** 3, F, device=pts.device, dtype=torch.float32)
-    _check(lib.dpd_mfv3d_fwd(L.ptr(pts), C, N, m, sigma, L.ptr(fv), s), "dpd_mfv3d_fwd")
+    _check(*ops.encode(lib, L.ptr(pts), C, N, m, sigma, L.ptr(fv), s))        # over tiles of points beyond the plain entry's LDS cap
     return fv
 
 
@@ -226,8 +227,7 @@ def _directed_bwd(lib, s, P, cp, m, sigma, S, fvS, Q, Gd, need_s, need_q, max_ro
                                   p["gs"] if need_s else None, p["dXs"] if need_s else None, p["dfv"] if need_s else None, L.ptr(gQ), s),
                "dpd_cross_bwd")
         if need_s:
-            _check(lib.dpd_mfv3d_bwd(L.ptr(S[i0:i0 + ca]), p["dfv"], ca, N, m, sigma, L.ptr(gS[i0:i0 + ca]), L.ptr(ws), ws.numel(), s),
-                   "dpd_mfv3d_bwd")
+            _check(*ops.encode_bwd(lib, L.ptr(S[i0:i0 + ca]), p["dfv"], ca, N, m, sigma, L.ptr(gS[i0:i0 + ca]), L.ptr(ws), ws.numel(), s))
     return gS, gQ
 
 

@@ -86,6 +86,40 @@ int dpd_mfv3d_bwd(const float* pts, const float* dfv, int C, int N, int m, float
 size_t dpd_mfv3d_bwd_workspace_bytes(int C, int m);
 
 /* ---------------------------------------------------------------------------------------------
+ * The encoder over TILES of points: clouds of any size 1 <= N <= 4096 (the reference registers clouds of 256 .. 2048 points,
+ * pcrnet-registration/iterative_PCRNet_ours.py:40,103-104).  Every statistic of utils/dpdist_util.py:78-109 is a sum, a max or a
+ * min over the points, so the kernels walk the points in tiles of at most `tile`, rebuild the tables of the tile's points only
+ * (their dynamic LDS depends on the tile, not on N) and carry the running statistics in registers across the tiles.  Same maths
+ * as the plain entries above, sums in another order: last-bit differences, the same bars against the float64 oracle.  The plain
+ * entries, their kernels and their LDS caps are unchanged; callers route to the tiled ones for the shapes those refuse.
+ *
+ * dpd_mfv3d_fits: 1 if the PLAIN entry takes (N, m), else 0.  which = 0: dpd_mfv3d_fwd; 1: dpd_mfv3d_bwd without a workspace (one
+ *   launch); 2: dpd_mfv3d_bwd with a workspace (sliced; N < 8 runs the one-launch kernel there as well).  Host only: the library's own
+ *   statement of the LDS caps quoted above, so that no caller restates the formulas.  0 for sizes no entry takes and for any other
+ *   `which`.
+ * dpd_mfv3d_tile: the tile the tiled entries choose for tile = 0 -- the largest multiple of 8 whose dynamic LDS (below) stays at or
+ *   under 64 KiB, i.e. no opt-in attribute and two workgroups per CU.  which = 0 forward (m = 8: 248, m = 10: 168), otherwise
+ *   backward (m = 8: 160).  0 where the entry takes no such m.  Host only.
+ * dpd_mfv3d_fwd_tiled: pts [C,N,3] -> the NORMALISED fv [C,m^3,20] (per-channel L2 norm applied, as dpd_mfv3d_fwd does; two launches).
+ *   1 <= N <= 4096 and 1 <= m <= 10, else DPD_E_UNSUPPORTED; sigma > 0 (not NaN) and C >= 1, else DPD_E_DIM.
+ *   tile: 0 = the library's choice; otherwise a multiple of 8, >= 8, whose dynamic LDS fits 160 KiB:
+ *       4 * (6*tile*m + 6*tile + 21*ceil(m^3 / 4) + 4) bytes <= 163840
+ *   else DPD_E_UNSUPPORTED.  A tile larger than the cloud is cut to N rounded up to 8.  Every refusal happens before anything is
+ *   launched and leaves fv untouched.  A point that underflows every pdf (0/0 at :74) yields NaN throughout, in whichever tile it sits.
+ * dpd_mfv3d_bwd_tiled: dfv [C,m^3,20] -> dpts [C,N,3] (overwritten), three launches: each of the 4 point slices of the sliced form
+ *   (n = ceil(N / 4) points; record layout and merge as there, empty slices included) walks its points in tiles.  m <= 8 as
+ *   dpd_mfv3d_bwd; any 1 <= N <= 4096.  ws is REQUIRED: dpd_mfv3d_bwd_workspace_bytes(C, m) bytes, else DPD_E_WORKSPACE.  tile as
+ *   above with
+ *       4 * (6*tile*m + 52*tile + 4) bytes <= 163840
+ *   and cut to n rounded up to 8.  The tie count of a max / min is taken over the whole cloud, across tiles and slices.  Refusals
+ *   leave dpts and ws untouched.                                                                                                 */
+int dpd_mfv3d_fits(int N, int m, int which);
+int dpd_mfv3d_tile(int m, int which);
+int dpd_mfv3d_fwd_tiled(const float* pts, int C, int N, int m, float sigma, int tile, float* fv, void* stream);
+int dpd_mfv3d_bwd_tiled(const float* pts, const float* dfv, int C, int N, int m, float sigma, int tile, float* dpts, void* ws,
+                        size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Query -> voxel lookup + local-window gather.  Replaces local_z_3d (utils/dpdist_util.py:911-930),
  * get_pc_grid_binary_mask_from_centers (:459-492) and get_emb_and_concat (:434-457) WITHOUT
  * materialising the [C,m^3,k^3*20] window tensor.
