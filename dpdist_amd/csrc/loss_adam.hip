@@ -134,7 +134,8 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(float* __restrict__ p, 
             // the lane's own values; an R8 chunk (8 rows of one column) is this lane's four rows plus the four of lane +- 32: one
             // v_permlane32_swap per packed dword gives the lower half the chunks of columns 0, 2 and the upper half those of 1, 3
             // (same exchange as the plane GEMM epilogue, gemm_x3.hip).  33.6 -> 33.0 us: the kernel moves its 150 MB of mixed traffic at ~4.5 TB/s
-            // with or without the LDS tile (DPD_ADAM_LDS_TILES=1 keeps the tile form as an A/B reference).
+            // with or without the LDS tile.  The tile form below stays for every other descriptor: a matrix with a transposed copy
+            // (WT), one whose cols are a multiple of 64 but not of 128, and NP = 0.
             const int lane = tid & 63, l31 = lane & 31, half = lane >> 5, segs = cols >> 7;
             const int u = t * 4 + (tid >> 6);
             if (u >= (rows >> 3) * segs) return;
