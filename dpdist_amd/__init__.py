@@ -16,7 +16,7 @@ def __getattr__(name):
     if name in ("get_model", "get_loss", "DPDistModel", "DPDistLoss", "placeholder_inputs"):
         from . import model
         return getattr(model, name)
-    if name in ("dpdist_matrix", "DPDistMatrix"):
+    if name in ("dpdist_matrix", "DPDistMatrix", "pad_clouds"):
         from . import pairwise
         return getattr(pairwise, name)
     raise AttributeError(name)

@@ -89,14 +89,29 @@ __global__ __launch_bounds__(1024) void cross_invert_kernel(const int32_t* __res
     }
 }
 
-// Upstream spread, the inverse of pair_mean_kernel: dpred[r] = (Gd[pair of r] / N, 0, 0) for the real rows, 0 for the pad rows
-__global__ __launch_bounds__(256) void cross_spread_kernel(const float* __restrict__ Gd, int N, int rows, int rows_p, float* __restrict__ dpred) {
+// Upstream spread, the inverse of pair_mean_kernel: dpred[r] = (Gd[pair of r] / N, 0, 0) for the real rows, 0 for the pad rows.
+// CNT (dpd_cross_bwd_counts): row (i, j, n) gets Gd[i, j] / qcounts[j] for n < qcounts[j] (clamped into [1, N]) and 0 otherwise.
+template <bool CNT>
+__device__ __forceinline__ void cross_spread_block(const float* __restrict__ Gd, int N, int rows, int rows_p, float* __restrict__ dpred,
+                                                   const int32_t* __restrict__ qcounts, int Cb) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= rows_p) return;
-    const float v = r < rows ? Gd[r / N] / (float)N : 0.f;
+    float v = 0.f;
+    if (r < rows) {
+        const int pr = r / N;
+        const int n1 = CNT ? min(max(qcounts[pr % Cb], 1), N) : N;
+        if (!CNT || r - pr * N < n1) v = Gd[pr] / (float)n1;
+    }
     dpred[(size_t)r * 3] = v;
     dpred[(size_t)r * 3 + 1] = 0.f;
     dpred[(size_t)r * 3 + 2] = 0.f;
+}
+__global__ __launch_bounds__(256) void cross_spread_kernel(const float* __restrict__ Gd, int N, int rows, int rows_p, float* __restrict__ dpred) {
+    cross_spread_block<false>(Gd, N, rows, rows_p, dpred, nullptr, 1);
+}
+__global__ __launch_bounds__(256) void cross_spread_counts_kernel(const float* __restrict__ Gd, const int32_t* __restrict__ qcounts, int N, int Cb,
+                                                                  int rows, int rows_p, float* __restrict__ dpred) {
+    cross_spread_block<true>(Gd, N, rows, rows_p, dpred, qcounts, Cb);
 }
 
 // Slot sum + query route: g1 [rows_p, H] is streamed once.  Workgroup t < Ca U owns slot (i, s) = (t / U, t % U): wave w owns the
@@ -289,10 +304,12 @@ extern "C" int dpd_cross_scatter(const float* dXs, const int32_t* cnt, const int
     return 0;
 }
 
-extern "C" int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y, const float* h1, const float* h2, const float* h3,
-                             const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox, int Ca_chunk, int Cb,
-                             int N, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dpred, float* dy, float* ga,
-                             float* gb, float* dq, float* gs, float* dXs, float* dfv, float* gQ, void* stream) {
+// qcounts = NULL: dpd_cross_bwd; otherwise the upstream spread over each query cloud's own count (everything after it is unchanged: a
+// padded query is a masked query of voxel 0 since dpd_cross_index_counts)
+static int cross_bwd(const float* Gd, const float* maskr, const int32_t* qcounts, const float* y, const float* h1, const float* h2,
+                     const float* h3, const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox, int Ca_chunk,
+                     int Cb, int N, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dpred, float* dy, float* ga,
+                     float* gb, float* dq, float* gs, float* dXs, float* dfv, float* gQ, void* stream) {
     using namespace dpd;
     const bool surface = dfv != nullptr, query = gQ != nullptr;
     if (!Gd || !maskr || !y || !h1 || !h2 || !h3 || !cnt || !slot_start || !qlist || !p || !dpred || !dy || !ga || !gb) return DPD_E_NULL;
@@ -308,7 +325,10 @@ extern "C" int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y
     // 2. upstream spread
     {
         StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)Ca_chunk * Cb * 4.0 + rows_p * 12.0);
-        DPD_LAUNCH(cross_spread_kernel, dim3((rows_p + 255) / 256), dim3(256), 0, s, Gd, N, rows, rows_p, dpred);
+        if (qcounts)
+            DPD_LAUNCH(cross_spread_counts_kernel, dim3((rows_p + 255) / 256), dim3(256), 0, s, Gd, qcounts, N, Cb, rows, rows_p, dpred);
+        else
+            DPD_LAUNCH(cross_spread_kernel, dim3((rows_p + 255) / 256), dim3(256), 0, s, Gd, N, rows, rows_p, dpred);
         DPD_CHECK_LAUNCH();
     }
     // 3. layers 4..2: g3 -> ga, g2 -> gb, g1 -> ga (masked queries and pad rows: exact zeros through the mask)
@@ -337,4 +357,22 @@ extern "C" int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y
         DPD_CHECK_LAUNCH();
     }
     return 0;
+}
+
+extern "C" int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y, const float* h1, const float* h2, const float* h3,
+                             const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox, int Ca_chunk, int Cb,
+                             int N, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dpred, float* dy, float* ga,
+                             float* gb, float* dq, float* gs, float* dXs, float* dfv, float* gQ, void* stream) {
+    return cross_bwd(Gd, maskr, nullptr, y, h1, h2, h3, cnt, slot_start, qlist, slot_vox, Ca_chunk, Cb, N, m, k, KP, H, slot_cap, p, dpred, dy, ga,
+                     gb, dq, gs, dXs, dfv, gQ, stream);
+}
+
+extern "C" int dpd_cross_bwd_counts(const float* Gd, const float* maskr, const int32_t* qcounts, const float* y, const float* h1, const float* h2,
+                                    const float* h3, const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist,
+                                    const int32_t* slot_vox, int Ca_chunk, int Cb, int N, int m, int k, int KP, int H, int slot_cap,
+                                    const dpd_decoder_params* p, float* dpred, float* dy, float* ga, float* gb, float* dq, float* gs, float* dXs,
+                                    float* dfv, float* gQ, void* stream) {
+    if (!qcounts) return DPD_E_NULL;
+    return cross_bwd(Gd, maskr, qcounts, y, h1, h2, h3, cnt, slot_start, qlist, slot_vox, Ca_chunk, Cb, N, m, k, KP, H, slot_cap, p, dpred, dy,
+                     ga, gb, dq, gs, dXs, dfv, gQ, stream);
 }

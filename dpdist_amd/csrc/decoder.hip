@@ -1009,14 +1009,26 @@ __global__ __launch_bounds__(256) void l1_finish_kernel(const float* __restrict_
 
 // All-pairs distance matrix (dpd_decoder_fwd_cross): Dd[p] = mean over the N rows of pair p of pred[:, 0].  One wave per pair: lane l
 // adds rows l, l + 64, ... in order, then the fixed tree of wave_sum -- the same order for every pair, whatever the launch holds.
-__global__ __launch_bounds__(256) void pair_mean_kernel(const float* __restrict__ pred, int N, int pairs, float* __restrict__ Dd) {
+// CNT (dpd_decoder_fwd_cross_counts): pair p = (i, j) sums the first qcounts[j] of its N rows (clamped into [1, N]) and divides by that
+// count; the same lane order and tree.
+template <bool CNT>
+__device__ __forceinline__ void pair_mean_block(const float* __restrict__ pred, int N, int pairs, float* __restrict__ Dd,
+                                                const int32_t* __restrict__ qcounts, int Cb) {
     const int lane = threadIdx.x & 63, pr = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pr >= pairs) return;
     const float* src = pred + (size_t)pr * N * 3;
+    const int n1 = CNT ? min(max(qcounts[pr % Cb], 1), N) : N;
     float a = 0.f;
-    for (int n = lane; n < N; n += 64) a += src[(size_t)n * 3];
+    for (int n = lane; n < n1; n += 64) a += src[(size_t)n * 3];
     a = wave_sum(a);
-    if (lane == 0) Dd[pr] = a / (float)N;
+    if (lane == 0) Dd[pr] = a / (float)n1;
+}
+__global__ __launch_bounds__(256) void pair_mean_kernel(const float* __restrict__ pred, int N, int pairs, float* __restrict__ Dd) {
+    pair_mean_block<false>(pred, N, pairs, Dd, nullptr, 1);
+}
+__global__ __launch_bounds__(256) void pair_mean_counts_kernel(const float* __restrict__ pred, const int32_t* __restrict__ qcounts, int N,
+                                                               int pairs, int Cb, float* __restrict__ Dd) {
+    pair_mean_block<true>(pred, N, pairs, Dd, qcounts, Cb);
 }
 
 }  // namespace dpd
@@ -1237,13 +1249,14 @@ extern "C" int dpd_decoder_fwd_unique(const float* Xu /* k-major */, const float
     return fwd_over_slots(Xu, Q + 32, Q + 32, Xt, uid, cnt + 1, Pu, mask, Q, KP, H, p, h1, h2, h3, y, pred, (hipStream_t)stream, false);
 }
 
-extern "C" int dpd_decoder_fwd_cross(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt,
-                                     float* Pu, const float* maskr, int pairs, int N, int KP, int H, const dpd_decoder_params* p, float* act0,
-                                     float* act1, float* y, float* pred, float* Dd, void* stream) {
+// qcounts = NULL: dpd_decoder_fwd_cross; otherwise the pair means over each query cloud's own count (pairs = surface clouds x Cb)
+static int fwd_cross(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
+                     const float* maskr, const int32_t* qcounts, int pairs, int Cb, int N, int KP, int H, const dpd_decoder_params* p,
+                     float* act0, float* act1, float* y, float* pred, float* Dd, void* stream) {
     using namespace dpd;
-    if (!Xu || !Xt || !uid || !cnt || !Pu || !maskr || !p || !act0 || !act1 || !y || !pred || !Dd) return DPD_E_NULL;
     if (!p->W1p || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4) return DPD_E_NULL;
     if (pairs <= 0 || N <= 0 || KP <= 0 || H <= 0 || slot_cap <= 0 || ldu < slot_cap || (long)pairs * N > (1L << 30)) return DPD_E_DIM;
+    if (qcounts && (Cb <= 0 || pairs % Cb)) return DPD_E_DIM;
     if ((H & 63) || (KP & 31) || KP < 64 || (slot_cap & 3) || (ldu & 3)) return DPD_E_UNSUPPORTED;
     const int Q = (pairs * N + 31) / 32 * 32;       // the rows and their pad rows
     // (the GEMMs address Xu, Pu and the activations with 32-bit byte offsets)
@@ -1253,9 +1266,27 @@ extern "C" int dpd_decoder_fwd_cross(const float* Xu /* k-major */, int ldu, int
     // h1 -> act0, h2 -> act1, h3 -> act0: nothing is kept for a backward pass
     if (int rc = fwd_over_slots(Xu, ldu, slot_cap, Xt, uid, cnt + 1, Pu, maskr, Q, KP, H, p, act0, act1, act0, y, pred, s, true)) return rc;
     StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)pairs * N * 12.0 + pairs * 4.0);
-    DPD_LAUNCH(pair_mean_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, (const float*)pred, N, pairs, Dd);
+    if (qcounts)
+        DPD_LAUNCH(pair_mean_counts_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, (const float*)pred, qcounts, N, pairs, Cb, Dd);
+    else
+        DPD_LAUNCH(pair_mean_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, (const float*)pred, N, pairs, Dd);
     DPD_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dpd_decoder_fwd_cross(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt,
+                                     float* Pu, const float* maskr, int pairs, int N, int KP, int H, const dpd_decoder_params* p, float* act0,
+                                     float* act1, float* y, float* pred, float* Dd, void* stream) {
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !maskr || !p || !act0 || !act1 || !y || !pred || !Dd) return DPD_E_NULL;
+    return fwd_cross(Xu, ldu, slot_cap, Xt, uid, cnt, Pu, maskr, nullptr, pairs, 0, N, KP, H, p, act0, act1, y, pred, Dd, stream);
+}
+
+extern "C" int dpd_decoder_fwd_cross_counts(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid,
+                                            const int32_t* cnt, float* Pu, const float* maskr, const int32_t* qcounts, int pairs, int Cb, int N,
+                                            int KP, int H, const dpd_decoder_params* p, float* act0, float* act1, float* y, float* pred,
+                                            float* Dd, void* stream) {
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !maskr || !qcounts || !p || !act0 || !act1 || !y || !pred || !Dd) return DPD_E_NULL;
+    return fwd_cross(Xu, ldu, slot_cap, Xt, uid, cnt, Pu, maskr, qcounts, pairs, Cb, N, KP, H, p, act0, act1, y, pred, Dd, stream);
 }
 
 // dpd_decoder_fwd_cross with the three activations kept for dpd_cross_bwd: the same launches on the same operands, so the same bits

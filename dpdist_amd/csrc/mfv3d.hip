@@ -1006,6 +1006,20 @@ __global__ __launch_bounds__(512) void mfv3d_bwd_combine_kernel(const float* __r
         default: mfv3d_bwd_combine_quarter<15>(dfv, part, k, c, s_chred, s_ch); break;
     }
 }
+// dpd_mfv3d_bwd_counts: the same quarters with the cloud's own (clamped) count behind the mean statistics' 1 / N
+__global__ __launch_bounds__(512) void mfv3d_bwd_combine_counts_kernel(const float* __restrict__ dfv, const int32_t* __restrict__ counts,
+                                                                       float* __restrict__ part, MfvConst k) {
+    __shared__ float s_chred[8 * 2 * 5];
+    __shared__ float s_ch[2 * 5];
+    const int c = blockIdx.x >> 2;
+    k.N = min(max(counts[c], 1), k.N);
+    switch (blockIdx.x & 3) {
+        case 0: mfv3d_bwd_combine_quarter<0>(dfv, part, k, c, s_chred, s_ch); break;
+        case 1: mfv3d_bwd_combine_quarter<5>(dfv, part, k, c, s_chred, s_ch); break;
+        case 2: mfv3d_bwd_combine_quarter<10>(dfv, part, k, c, s_chred, s_ch); break;
+        default: mfv3d_bwd_combine_quarter<15>(dfv, part, k, c, s_chred, s_ch); break;
+    }
+}
 
 // FINAL (as-loss backward): instead of dpts, the evaluation's two input gradients leave this kernel (= dpd_asloss_combine on its output):
 //   clouds c < B are pcA, queried by the BA half of the rows; c >= B are pcB, queried by the AB half (models/dpdist_and_aue.py:56-69):
@@ -1143,11 +1157,15 @@ static int set_lds(size_t lds) {
 //     the kernel has 128 VGPRs per lane at 1024 threads and needs 93 for both sets, 66 for one (resource table in DESIGN section 3), no scratch.
 // dynamic LDS (floats): zq[3*tile*m*2] | S[3*tile] | minz2[3*tile] | stage[slice*21] | flag
 // ------------------------------------------------------------------------------------------------------
-template <int NB>
-__global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_tiled_kernel(const float* __restrict__ pts, float* __restrict__ fv, MfvConst k,
-                                                                       int gslice, int tile) {
+// CNT (the *_counts entries): cloud c holds its first counts[c] points of a row of k.N (clamped into [1, k.N] here: the host never reads
+// the device words); N below is then the cloud's own count -- loop bound, the mean's 1 / N and sqrt(w) N (sqw = the host's sqrt(w), the
+// product formed as make_const forms it) -- and the row stride stays k.N.  The padding is never read.  CNT = false: the code as it was.
+template <int NB, bool CNT>
+__device__ __forceinline__ void mfv3d_fwd_tiled_body(const float* __restrict__ pts, float* __restrict__ fv, const MfvConst& k, int gslice,
+                                                     int tile, const int32_t* __restrict__ counts, float sqw) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int N = k.N, G = k.G, m = k.m;
+    const int G = k.G, m = k.m;
+    const int N = CNT ? min(max(counts[blockIdx.x / kSlices], 1), k.N) : k.N;
     float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][np_][m], np_ <= tile
     float* s_S = sm + 6 * tile * m;                 // [3][np_]
     float* s_mz = s_S + 3 * tile;                   // [3][np_] min_i z^2
@@ -1183,11 +1201,11 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_tiled_kernel(const floa
             sg_s[b][d] = 0.f; sg_mx[b][d] = -INFINITY; sg_mn[b][d] = INFINITY;
         }
     }
-    const float inv_dpi = 1.0f / k.dpi_den;
+    const float inv_dpi = 1.0f / (CNT ? sqw * (float)N : k.dpi_den);
 
     for (int t0 = 0; t0 < N; t0 += tile) {
         const int np_ = min(tile, N - t0);
-        const float* p = pts + ((size_t)c * N + t0) * 3;
+        const float* p = pts + ((size_t)c * k.N + t0) * 3;
         const int lg_np = lg_or_neg(np_);
         // ---- tables of the tile's points: the passes of mfv3d_fwd_kernel ---------------------------------------------
         for (int e = tid; e < 3 * np_ * m; e += kFwdThreads) {
@@ -1284,6 +1302,17 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_tiled_kernel(const floa
     }
 }
 
+template <int NB>
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_tiled_kernel(const float* __restrict__ pts, float* __restrict__ fv, MfvConst k,
+                                                                       int gslice, int tile) {
+    mfv3d_fwd_tiled_body<NB, false>(pts, fv, k, gslice, tile, nullptr, 0.f);
+}
+template <int NB>
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_counts_kernel(const float* __restrict__ pts, const int32_t* __restrict__ counts,
+                                                                        float* __restrict__ fv, MfvConst k, int gslice, int tile, float sqw) {
+    mfv3d_fwd_tiled_body<NB, true>(pts, fv, k, gslice, tile, counts, sqw);
+}
+
 // Backward over tiles: the three-launch structure and the workspace layout of the sliced form (kSlices records of kRec rows per cloud;
 // mfv3d_bwd_combine_kernel runs unchanged in between).  Each of the kSlices point slices walks its ceil(N / kSlices) points in tiles.
 //   statistics: tiles once for the sums / maxima / minima, tiles AGAIN for the 13 tie counts against the slice's extrema (tables rebuilt by
@@ -1291,21 +1320,26 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_fwd_tiled_kernel(const floa
 //   apply:      per tile tables -> T_n -> dx_n of the tile's points -> store; a tile needs nothing of the other tiles beyond the combined record.
 // All sums in a fixed order, no float atomics.  An empty slice (or tile count 0) writes the -inf / +inf / 0 record, as the sliced form does.
 // dynamic LDS (floats): statistics zq[6*tile*m] | S[3*tile]; apply zq[6*tile*m] | S[3*tile] | T[tile] | part[16*tile*3]
-__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_stats_tiled_kernel(const float* __restrict__ pts, float* __restrict__ part,
-                                                                             MfvConst k, int nslice, int tile) {
+// CNT (dpd_mfv3d_bwd_counts): as in the forward, N is the cloud's clamped count; its point slices are ceil(N / kSlices) points each (the
+// slices a cloud of that size has alone), the row stride stays k.N, and the apply kernel writes +0.0 over the padded rows of dpts.
+template <bool CNT>
+__device__ __forceinline__ void mfv3d_bwd_stats_tiled_body(const float* __restrict__ pts, float* __restrict__ part, const MfvConst& k,
+                                                           int nslice_full, int tile, const int32_t* __restrict__ counts, float sqw) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int N = k.N, G = k.G, m = k.m;
+    const int G = k.G, m = k.m;
     const int c = blockIdx.x / kSlices, sl = blockIdx.x % kSlices;
+    const int N = CNT ? min(max(counts[c], 1), k.N) : k.N;
+    const int nslice = CNT ? (N + kSlices - 1) / kSlices : nslice_full;
     const int n0 = min(N, sl * nslice), np_ = min(N, n0 + nslice) - n0;
     float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][tp][m], tp <= tile
     float* s_S = sm + 6 * tile * m;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
-    const float* p = pts + (size_t)c * N * 3;
+    const float* p = pts + (size_t)c * k.N * 3;
     const int g = wave * 32 + (lane & 31);
     const bool live = g < G;
     const int gg = live ? g : 0;
     const int gi = gg / (m * m), gj = (gg / m) % m, gt = gg % m;
-    const float inv_dpi = 1.0f / k.dpi_den;
+    const float inv_dpi = 1.0f / (CNT ? sqw * (float)N : k.dpi_den);
     float rec[kRec];
     {
         float pi_s = 0.f, pi_mx = -INFINITY;
@@ -1377,23 +1411,41 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_stats_tiled_kernel(cons
     }
 }
 
-__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_apply_tiled_kernel(const float* __restrict__ pts, const float* __restrict__ comb,
-                                                                             float* __restrict__ dpts, MfvConst k, int nslice, int tile) {
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_stats_tiled_kernel(const float* __restrict__ pts, float* __restrict__ part,
+                                                                             MfvConst k, int nslice, int tile) {
+    mfv3d_bwd_stats_tiled_body<false>(pts, part, k, nslice, tile, nullptr, 0.f);
+}
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_stats_counts_kernel(const float* __restrict__ pts, const int32_t* __restrict__ counts,
+                                                                              float* __restrict__ part, MfvConst k, int nslice, int tile,
+                                                                              float sqw) {
+    mfv3d_bwd_stats_tiled_body<true>(pts, part, k, nslice, tile, counts, sqw);
+}
+
+template <bool CNT>
+__device__ __forceinline__ void mfv3d_bwd_apply_tiled_body(const float* __restrict__ pts, const float* __restrict__ comb,
+                                                           float* __restrict__ dpts, const MfvConst& k, int nslice_full, int tile,
+                                                           const int32_t* __restrict__ counts, float sqw) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int N = k.N, G = k.G, m = k.m;
+    const int G = k.G, m = k.m;
     const int c = blockIdx.x / kSlices, sl = blockIdx.x % kSlices;
+    const int N = CNT ? min(max(counts[c], 1), k.N) : k.N;
+    const int nslice = CNT ? (N + kSlices - 1) / kSlices : nslice_full;
     const int n0 = min(N, sl * nslice), np_ = min(N, n0 + nslice) - n0;
     float2* s_zq = reinterpret_cast<float2*>(sm);   // [3][tp][m]
     float* s_S = sm + 6 * tile * m;                 // [3][tile]
     float* s_T = s_S + 3 * tile;                    // [tile]
     float* s_part = s_T + tile;                     // [16][tile][3]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
-    const float* p = pts + (size_t)c * N * 3;
+    const float* p = pts + (size_t)c * k.N * 3;
     const int g = wave * 32 + (lane & 31);
     const bool live = g < G;
     const int gg = live ? g : 0;
     const int gi = gg / (m * m), gj = (gg / m) % m, gt = gg % m;
-    const float inv_dpi = 1.0f / k.dpi_den;
+    const float inv_dpi = 1.0f / (CNT ? sqw * (float)N : k.dpi_den);
+    if (CNT) {      // the padded rows of this cloud, shared among its kSlices workgroups: +0.0
+        float* pad = dpts + (size_t)c * k.N * 3;
+        for (int i = N * 3 + sl * kFwdThreads + tid; i < k.N * 3; i += kSlices * kFwdThreads) pad[i] = 0.f;
+    }
     // d raw statistic and the global extrema of this lane's Gaussian, from mfv3d_bwd_combine_kernel
     float dr[kF], raw[kF];
     {
@@ -1452,7 +1504,7 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_apply_tiled_kernel(cons
             }
         }
         __syncthreads();
-        float* out = dpts + ((size_t)c * N + n0 + t0) * 3;
+        float* out = dpts + ((size_t)c * k.N + n0 + t0) * 3;
         for (int i = tid; i < tp * 3; i += kFwdThreads) {
             float t = 0.f;
 #pragma unroll
@@ -1461,6 +1513,16 @@ __global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_apply_tiled_kernel(cons
         }
         __syncthreads();        // the next tile overwrites the tables and the partial sums
     }
+}
+
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_apply_tiled_kernel(const float* __restrict__ pts, const float* __restrict__ comb,
+                                                                             float* __restrict__ dpts, MfvConst k, int nslice, int tile) {
+    mfv3d_bwd_apply_tiled_body<false>(pts, comb, dpts, k, nslice, tile, nullptr, 0.f);
+}
+__global__ __launch_bounds__(kFwdThreads) void mfv3d_bwd_apply_counts_kernel(const float* __restrict__ pts, const int32_t* __restrict__ counts,
+                                                                              const float* __restrict__ comb, float* __restrict__ dpts,
+                                                                              MfvConst k, int nslice, int tile, float sqw) {
+    mfv3d_bwd_apply_tiled_body<true>(pts, comb, dpts, k, nslice, tile, counts, sqw);
 }
 
 static size_t fwd_tiled_lds_bytes(int tile, int m, int gslice) {
@@ -1594,9 +1656,9 @@ extern "C" int dpd_mfv3d_fits(int N, int m, int which) {
 
 extern "C" int dpd_mfv3d_tile(int m, int which) { return dpd::default_tile(m, which != 0); }
 
-extern "C" int dpd_mfv3d_fwd_tiled(const float* pts, int C, int N, int m, float sigma, int tile, float* fv, void* stream) {
+// the tiled entries and their per-cloud-count twins (counts = NULL: the tiled entry, its kernels and its bits)
+static int fwd_tiled(const float* pts, const int32_t* counts, int C, int N, int m, float sigma, int tile, float* fv, void* stream) {
     using namespace dpd;
-    if (!pts || !fv) return DPD_E_NULL;
     if (C <= 0) return DPD_E_DIM;
     MfvConst k{};
     if (int rc = make_const(N, m, sigma, k)) return rc;
@@ -1605,37 +1667,61 @@ extern "C" int dpd_mfv3d_fwd_tiled(const float* pts, int C, int N, int m, float 
     int T = 0;
     if (int rc = resolve_tile(tile, m, false, N, T)) return rc;
     const size_t lds = fwd_tiled_lds_bytes(T, m, gslice);
+    const float sqw = sqrtf(k.w);
+    const dim3 grid(C * kSlices), block(kFwdThreads);
+    hipStream_t s = (hipStream_t)stream;
     StageProf prof(stream, DPD_STAGE_ENCODER, (double)C * (N * 12.0 * kSlices + k.G * 80.0));      // every Gaussian slice reads the points
     if (gslice > 16 * 8) {      // m = 9, 10: two batches of Gaussians per wave
-        if (int rc = set_lds<mfv3d_fwd_tiled_kernel<2>>(lds)) return rc;
-        DPD_LAUNCH(mfv3d_fwd_tiled_kernel<2>, dim3(C * kSlices), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, fv, k, gslice, T);
+        if (counts) {
+            if (int rc = set_lds<mfv3d_fwd_counts_kernel<2>>(lds)) return rc;
+            DPD_LAUNCH(mfv3d_fwd_counts_kernel<2>, grid, block, lds, s, pts, counts, fv, k, gslice, T, sqw);
+        } else {
+            if (int rc = set_lds<mfv3d_fwd_tiled_kernel<2>>(lds)) return rc;
+            DPD_LAUNCH(mfv3d_fwd_tiled_kernel<2>, grid, block, lds, s, pts, fv, k, gslice, T);
+        }
     } else {
-        if (int rc = set_lds<mfv3d_fwd_tiled_kernel<1>>(lds)) return rc;
-        DPD_LAUNCH(mfv3d_fwd_tiled_kernel<1>, dim3(C * kSlices), dim3(kFwdThreads), lds, (hipStream_t)stream, pts, fv, k, gslice, T);
+        if (counts) {
+            if (int rc = set_lds<mfv3d_fwd_counts_kernel<1>>(lds)) return rc;
+            DPD_LAUNCH(mfv3d_fwd_counts_kernel<1>, grid, block, lds, s, pts, counts, fv, k, gslice, T, sqw);
+        } else {
+            if (int rc = set_lds<mfv3d_fwd_tiled_kernel<1>>(lds)) return rc;
+            DPD_LAUNCH(mfv3d_fwd_tiled_kernel<1>, grid, block, lds, s, pts, fv, k, gslice, T);
+        }
     }
     DPD_CHECK_LAUNCH();
-    DPD_LAUNCH(mfv3d_norm_kernel, dim3(C), dim3(1024), 0, (hipStream_t)stream, fv, k.G, gslice);
+    DPD_LAUNCH(mfv3d_norm_kernel, dim3(C), dim3(1024), 0, s, fv, k.G, gslice);
     DPD_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int dpd_mfv3d_bwd_tiled(const float* pts, const float* dfv, int C, int N, int m, float sigma, int tile, float* dpts, void* ws,
-                                   size_t ws_bytes, void* stream) {
+static int bwd_tiled(const float* pts, const int32_t* counts, const float* dfv, int C, int N, int m, float sigma, int tile, float* dpts,
+                     void* ws, size_t ws_bytes, void* stream) {
     using namespace dpd;
-    if (!pts || !dfv || !dpts) return DPD_E_NULL;
     if (C <= 0) return DPD_E_DIM;
     MfvConst k{};
     if (int rc = make_const(N, m, sigma, k)) return rc;
     if (k.G > 512) return DPD_E_UNSUPPORTED;   // per-Gaussian gradient record lives in registers: one Gaussian per lane pair
     if (tile > 0 && bwd_sliced_lds_bytes(tile, m) > 160 * 1024) return DPD_E_UNSUPPORTED;          // the tile as given must fit
-    const int nslice = (N + kSlices - 1) / kSlices;
+    const int nslice = (N + kSlices - 1) / kSlices;      // (with counts: the largest slice there can be; the kernels take each cloud's own)
     int T = 0;
     if (int rc = resolve_tile(tile, m, true, nslice, T)) return rc;
     if (!ws || ws_bytes < dpd_mfv3d_bwd_workspace_bytes(C, m)) return DPD_E_WORKSPACE;
     const size_t l1 = bwd_tiled_stats_lds_bytes(T, m), l2 = bwd_sliced_lds_bytes(T, m);
+    const float sqw = sqrtf(k.w);
+    hipStream_t s = (hipStream_t)stream;
+    if (counts) {
+        if (int rc = set_lds<mfv3d_bwd_stats_counts_kernel>(l1)) return rc;
+        if (int rc = set_lds<mfv3d_bwd_apply_counts_kernel>(l2)) return rc;
+        DPD_LAUNCH(mfv3d_bwd_stats_counts_kernel, dim3(C * kSlices), dim3(kFwdThreads), l1, s, pts, counts, (float*)ws, k, nslice, T, sqw);
+        DPD_CHECK_LAUNCH();
+        DPD_LAUNCH(mfv3d_bwd_combine_counts_kernel, dim3(C * 4), dim3(512), 0, s, dfv, counts, (float*)ws, k);
+        DPD_CHECK_LAUNCH();
+        DPD_LAUNCH(mfv3d_bwd_apply_counts_kernel, dim3(C * kSlices), dim3(kFwdThreads), l2, s, pts, counts, (const float*)ws, dpts, k, nslice, T, sqw);
+        DPD_CHECK_LAUNCH();
+        return 0;
+    }
     if (int rc = set_lds<mfv3d_bwd_stats_tiled_kernel>(l1)) return rc;
     if (int rc = set_lds<mfv3d_bwd_apply_tiled_kernel>(l2)) return rc;
-    hipStream_t s = (hipStream_t)stream;
     DPD_LAUNCH(mfv3d_bwd_stats_tiled_kernel, dim3(C * kSlices), dim3(kFwdThreads), l1, s, pts, (float*)ws, k, nslice, T);
     DPD_CHECK_LAUNCH();
     DPD_LAUNCH(mfv3d_bwd_combine_kernel, dim3(C * 4), dim3(512), 0, s, dfv, (float*)ws, k);
@@ -1643,6 +1729,30 @@ extern "C" int dpd_mfv3d_bwd_tiled(const float* pts, const float* dfv, int C, in
     DPD_LAUNCH(mfv3d_bwd_apply_tiled_kernel, dim3(C * kSlices), dim3(kFwdThreads), l2, s, pts, (const float*)ws, dpts, k, nslice, T);
     DPD_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dpd_mfv3d_fwd_tiled(const float* pts, int C, int N, int m, float sigma, int tile, float* fv, void* stream) {
+    if (!pts || !fv) return DPD_E_NULL;
+    return fwd_tiled(pts, nullptr, C, N, m, sigma, tile, fv, stream);
+}
+
+extern "C" int dpd_mfv3d_bwd_tiled(const float* pts, const float* dfv, int C, int N, int m, float sigma, int tile, float* dpts, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    if (!pts || !dfv || !dpts) return DPD_E_NULL;
+    return bwd_tiled(pts, nullptr, dfv, C, N, m, sigma, tile, dpts, ws, ws_bytes, stream);
+}
+
+// ---- ragged sets: cloud c is the first counts[c] points of its row of N (include/dpdist_capi.h) ----
+extern "C" int dpd_mfv3d_fwd_counts(const float* pts, const int32_t* counts, int C, int N, int m, float sigma, int tile, float* fv,
+                                    void* stream) {
+    if (!pts || !counts || !fv) return DPD_E_NULL;
+    return fwd_tiled(pts, counts, C, N, m, sigma, tile, fv, stream);
+}
+
+extern "C" int dpd_mfv3d_bwd_counts(const float* pts, const int32_t* counts, const float* dfv, int C, int N, int m, float sigma, int tile,
+                                    float* dpts, void* ws, size_t ws_bytes, void* stream) {
+    if (!pts || !counts || !dfv || !dpts) return DPD_E_NULL;
+    return bwd_tiled(pts, counts, dfv, C, N, m, sigma, tile, dpts, ws, ws_bytes, stream);
 }
 
 // The non-GEMM tail of an as-loss backward in THREE launches instead of six (dpd_patch_rows_bwd + dpd_mfv3d_bwd's three + dpd_asloss_combine):

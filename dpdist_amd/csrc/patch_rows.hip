@@ -704,16 +704,31 @@ extern "C" int dpd_cross_carve(void* mem, size_t bytes, int Ca_chunk, int Cb, in
     return 0;
 }
 
-extern "C" int dpd_cross_index(const float* q, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox, int32_t* ucount,
-                               void* stream) {
+static int cross_index(const float* q, const int32_t* counts, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox,
+                       int32_t* ucount, void* stream) {
     using namespace dpd;
-    if (!q || !mask || !vox || !slot_of_vox || !ucount) return DPD_E_NULL;
     if (Cb <= 0 || N <= 0 || (long)Cb * N > (1L << 24)) return DPD_E_DIM;
     if (m < 1 || m > 10) return DPD_E_UNSUPPORTED;
     StageProf prof(stream, DPD_STAGE_GATHER, (double)Cb * N * 20.0 + (double)m * m * m * 4.0);
-    DPD_LAUNCH(cross_index_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, q, Cb * N, m, make_axis(m), mask, vox, slot_of_vox, ucount);
+    if (counts)
+        DPD_LAUNCH(cross_index_counts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, q, counts, Cb * N, N, m, make_axis(m), mask, vox,
+                   slot_of_vox, ucount);
+    else
+        DPD_LAUNCH(cross_index_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, q, Cb * N, m, make_axis(m), mask, vox, slot_of_vox, ucount);
     DPD_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dpd_cross_index(const float* q, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox, int32_t* ucount,
+                               void* stream) {
+    if (!q || !mask || !vox || !slot_of_vox || !ucount) return DPD_E_NULL;
+    return cross_index(q, nullptr, Cb, N, m, mask, vox, slot_of_vox, ucount, stream);
+}
+
+extern "C" int dpd_cross_index_counts(const float* q, const int32_t* counts, int Cb, int N, int m, float* mask, int32_t* vox,
+                                      int32_t* slot_of_vox, int32_t* ucount, void* stream) {
+    if (!q || !counts || !mask || !vox || !slot_of_vox || !ucount) return DPD_E_NULL;
+    return cross_index(q, counts, Cb, N, m, mask, vox, slot_of_vox, ucount, stream);
 }
 
 extern "C" int dpd_cross_gather(const float* q, const int32_t* vox, const float* mask, const int32_t* slot_of_vox, const int32_t* ucount,

@@ -16,9 +16,12 @@
 
 // One workgroup: voxel and mask of every query (the cell rule of patch_rows_fwd_kernel), then the occupied voxels in ascending id.
 // An occupancy flag per voxel in LDS (plain stores of 1), a ballot prefix over the flags: integer only, one order.
-__global__ __launch_bounds__(1024) void cross_index_kernel(const float* __restrict__ q, int QN, int m, GridAxis ax, float* __restrict__ mask,
-                                                           int32_t* __restrict__ vox, int32_t* __restrict__ slot_of_vox,
-                                                           int32_t* __restrict__ ucount) {
+// CNT (dpd_cross_index_counts): query cloud j holds its first counts[j] queries of a row of N (clamped into [1, N] here); a padded query
+// is not read and is treated exactly like a query outside the cube, so nothing downstream knows about padding but the denominators.
+template <bool CNT>
+__device__ __forceinline__ void cross_index_block(const float* __restrict__ q, int QN, int m, const GridAxis& ax, float* __restrict__ mask,
+                                                  int32_t* __restrict__ vox, int32_t* __restrict__ slot_of_vox, int32_t* __restrict__ ucount,
+                                                  const int32_t* __restrict__ counts, int N) {
     __shared__ int s_occ[1024];      // m <= 10: m^3 <= 1000
     __shared__ int s_wsum[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -26,8 +29,16 @@ __global__ __launch_bounds__(1024) void cross_index_kernel(const float* __restri
     s_occ[tid] = 0;
     __syncthreads();
     for (int r = tid; r < QN; r += 1024) {
-        const float qx = q[(size_t)r * 3], qy = q[(size_t)r * 3 + 1], qz = q[(size_t)r * 3 + 2];
-        int ix = cell_of(ax, m, qx), iy = cell_of(ax, m, qy), iz = cell_of(ax, m, qz);
+        bool real = true;
+        if (CNT) {
+            const int j = r / N;
+            real = r - j * N < min(max(counts[j], 1), N);
+        }
+        int ix = -1, iy = -1, iz = -1;
+        if (real) {
+            const float qx = q[(size_t)r * 3], qy = q[(size_t)r * 3 + 1], qz = q[(size_t)r * 3 + 2];
+            ix = cell_of(ax, m, qx); iy = cell_of(ax, m, qy); iz = cell_of(ax, m, qz);
+        }
         const bool valid = (ix >= 0) && (iy >= 0) && (iz >= 0);
         if (!valid) { ix = 0; iy = 0; iz = 0; }      // a masked query shares the window of voxel 0 (patch_rows_fwd_kernel)
         const int v = (iy * m + ix) * m + iz;
@@ -48,6 +59,17 @@ __global__ __launch_bounds__(1024) void cross_index_kernel(const float* __restri
     }
     if (tid < G) slot_of_vox[tid] = occ ? before + __popcll(b & ((1ull << lane) - 1ull)) : -1;
     if (tid == 0) ucount[0] = all;
+}
+
+__global__ __launch_bounds__(1024) void cross_index_kernel(const float* __restrict__ q, int QN, int m, GridAxis ax, float* __restrict__ mask,
+                                                           int32_t* __restrict__ vox, int32_t* __restrict__ slot_of_vox,
+                                                           int32_t* __restrict__ ucount) {
+    cross_index_block<false>(q, QN, m, ax, mask, vox, slot_of_vox, ucount, nullptr, 0);
+}
+__global__ __launch_bounds__(1024) void cross_index_counts_kernel(const float* __restrict__ q, const int32_t* __restrict__ counts, int QN, int N,
+                                                                  int m, GridAxis ax, float* __restrict__ mask, int32_t* __restrict__ vox,
+                                                                  int32_t* __restrict__ slot_of_vox, int32_t* __restrict__ ucount) {
+    cross_index_block<true>(q, QN, m, ax, mask, vox, slot_of_vox, ucount, counts, N);
 }
 
 // patch_rows_fwd_unique_kernel for one surface cloud against all queries: kCrossChunks workgroups per surface cloud, each with the

@@ -88,6 +88,12 @@ SIGNATURES = {
     "dpd_cross_slot_sum": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p] * 3),
     "dpd_cross_scatter": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
     "dpd_cross_bwd": (c_int, [c_void_p] * 10 + [c_int] * 8 + [POINTER(DecoderParams)] + [c_void_p] * 10),
+    # ragged sets: the per-cloud-count twins (counts / qcounts: int32 device memory)
+    "dpd_mfv3d_fwd_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "dpd_mfv3d_bwd_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dpd_cross_index_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
+    "dpd_decoder_fwd_cross_counts": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int] * 5 + [POINTER(DecoderParams)] + [c_void_p] * 6),
+    "dpd_cross_bwd_counts": (c_int, [c_void_p] * 11 + [c_int] * 8 + [POINTER(DecoderParams)] + [c_void_p] * 10),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

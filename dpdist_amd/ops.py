@@ -43,6 +43,17 @@ def encode_bwd(lib, pts, dfv, C, N, m, sigma, dpts, ws, ws_bytes, s, which=FITS_
     return lib.dpd_mfv3d_bwd(pts, dfv, C, N, m, float(sigma), dpts, ws, ws_bytes, s), "dpd_mfv3d_bwd"
 
 
+def encode_counts(lib, pts, counts, C, N, m, sigma, fv, s):
+    """dpd_mfv3d_fwd_counts at its default tile: a ragged set (cloud c = its first counts[c] points) is always encoded over tiles
+    -> (return code, name of the entry)"""
+    return lib.dpd_mfv3d_fwd_counts(pts, counts, C, N, m, float(sigma), 0, fv, s), "dpd_mfv3d_fwd_counts"
+
+
+def encode_bwd_counts(lib, pts, counts, dfv, C, N, m, sigma, dpts, ws, ws_bytes, s):
+    """dpd_mfv3d_bwd_counts at its default tile (needs the workspace; writes +0.0 over the padded rows of dpts) -> (return code, name)"""
+    return lib.dpd_mfv3d_bwd_counts(pts, counts, dfv, C, N, m, float(sigma), 0, dpts, ws, ws_bytes, s), "dpd_mfv3d_bwd_counts"
+
+
 def mfv3d_fwd(pts, m, sigma):
     """pts [C,N,3] -> fv [C,m^3,20]   (utils/dpdist_util.py:22-141); any 1 <= N <= 4096: over tiles of points beyond the plain entry's
     LDS cap (N > 705 at m = 8)"""

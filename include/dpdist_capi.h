@@ -323,6 +323,41 @@ int dpd_cross_bwd(const float* Gd, const float* maskr, const float* y, const flo
                   int H, int slot_cap, const dpd_decoder_params* p, float* dpred, float* dy, float* ga, float* gb, float* dq, float* gs,
                   float* dXs, float* dfv, float* gQ, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * RAGGED sets: clouds of different sizes inside a set, for the all-pairs matrix.  A ragged set is a padded tensor pts [C,N,3] plus
+ * counts [C] (int32, DEVICE memory): cloud c consists of its first counts[c] points, 1 <= counts[c] <= N; the rest of its row is padding.
+ * The five entries below are the per-cloud-count twins of existing entries and run the same device code with a per-cloud bound: the
+ * un-counted entries, their kernels and their bits are unchanged.  Rules for all five:
+ *   - the host never reads a device word, so an out-of-range count cannot be refused: the KERNELS clamp every count into [1, N], and
+ *     an out-of-range count causes no out-of-bounds access;
+ *   - counts (qcounts) = NULL is DPD_E_NULL; every other refusal is that of the un-counted twin, happens before anything is launched and
+ *     leaves the outputs untouched.
+ * dpd_mfv3d_fwd_counts: dpd_mfv3d_fwd_tiled with n = counts[c] per cloud: the point loop runs to n, the mean's 1 / n and sqrt(w) n use
+ *   the cloud's count, the row stride is N.  Sizes, tile rules (the tile is cut to N rounded up to 8), the dynamic-LDS formula, the
+ *   normalisation and the NaN-on-0/0 behaviour are those of dpd_mfv3d_fwd_tiled.  The padding is never read.  Cloud c gets the bits
+ *   dpd_mfv3d_fwd_tiled gives for it alone ([1, n, 3]) at the same tile.
+ * dpd_mfv3d_bwd_counts: dpd_mfv3d_bwd_tiled with the 4 point slices taken per cloud (ceil(n / 4) points each, empty slices as there) and
+ *   the combine's 1 / n per cloud.  dpts [C,N,3]: rows n >= counts[c] are WRITTEN as +0.0 (no memset needed).  m <= 8; ws is REQUIRED
+ *   (dpd_mfv3d_bwd_workspace_bytes(C, m)).  The bits of dpd_mfv3d_bwd_tiled on the cloud alone at the same tile.
+ * dpd_cross_index_counts: dpd_cross_index where a padded query (n >= counts[j]) is treated exactly like a query outside the cube: mask 0,
+ *   voxel 0, voxel 0 marked occupied; it is not read.  Gather, slot logic, dpd_cross_invert, slot sum and scatter need no twin.
+ * dpd_decoder_fwd_cross_counts: dpd_decoder_fwd_cross with Dd[i, j] = (sum over n < qcounts[j] of pred[(i, j, n), 0]) / qcounts[j], in the
+ *   lane order and tree of the un-counted mean.  pairs = surface clouds x Cb; Cb < 1 or pairs % Cb != 0 is DPD_E_DIM.
+ *   (dpd_decoder_fwd_cross_keep needs no twin: the backward passes Dd = NULL.)
+ * dpd_cross_bwd_counts: dpd_cross_bwd with dpred[(i, j, n)] = (Gd[i, j] / qcounts[j], 0, 0) for n < qcounts[j] and 0 otherwise.       */
+int dpd_mfv3d_fwd_counts(const float* pts, const int32_t* counts, int C, int N, int m, float sigma, int tile, float* fv, void* stream);
+int dpd_mfv3d_bwd_counts(const float* pts, const int32_t* counts, const float* dfv, int C, int N, int m, float sigma, int tile, float* dpts,
+                         void* ws, size_t ws_bytes, void* stream);
+int dpd_cross_index_counts(const float* q, const int32_t* counts, int Cb, int N, int m, float* mask, int32_t* vox, int32_t* slot_of_vox,
+                           int32_t* ucount, void* stream);
+int dpd_decoder_fwd_cross_counts(const float* Xu, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
+                                 const float* maskr, const int32_t* qcounts, int pairs, int Cb, int N, int KP, int H,
+                                 const dpd_decoder_params* p, float* act0, float* act1, float* y, float* pred, float* Dd, void* stream);
+int dpd_cross_bwd_counts(const float* Gd, const float* maskr, const int32_t* qcounts, const float* y, const float* h1, const float* h2,
+                         const float* h3, const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox,
+                         int Ca_chunk, int Cb, int N, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dpred,
+                         float* dy, float* ga, float* gb, float* dq, float* gs, float* dXs, float* dfv, float* gQ, void* stream);
+
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in
  *               dpd_decoder_fwd / dpd_decoder_bwd_data (ws may be NULL);

@@ -10,6 +10,11 @@ on synth.s2_modelnet_shaped clouds:
                                             #   cross   dpdist_amd.DPDistMatrix (one autograd node; the backward recomputes each chunk)
                                             #   pairs   the frozen model on the hand-tiled pairs, 128 pairs at a time, each pair weighted by G
 
+    python tools/matrix_bench.py --ragged   # ragged sets (counts drawn uniformly in [N/4, N]): the counted matrix, forward and
+                                            #   forward + backward, beside the full sets of the same padded width; then, at N = 2048
+                                            #   (both calls encode over tiles: the same kernels), the counted call with all counts = N
+                                            #   beside the un-counted call, three repetitions; written to profiles/ragged_matrix_bench.txt
+
 The two forms alternate, five rounds after a warm-up, each timed with a device event pair; the two matrices must agree within the
 fp32 forward bar of the tests (1e-4 absolute).  The per-kernel split comes from a further pass of each form under the library's in-stream
 stage profiler (event pairs around every launch: dpd_prof_enable(2))."""
@@ -104,6 +109,70 @@ def kernel_split(lib, fn, stages=None):
     return out
 
 
+def ragged(a, dev, model):
+    """--ragged: what per-cloud counts cost.  (1) counts uniform in [N/4, N] against the full sets of the same padded width (the padded
+    rows still pay their GEMM work: the two should be close); (2) at N = 2048, counts all N against the call without counts, three
+    repetitions of `rounds` calls each, alternating -- the spread of the un-counted medians is the yardstick"""
+    C, N, H = a.clouds, a.points, a.width
+    rng = np.random.default_rng(9)
+    lines = ["# tools/matrix_bench.py --ragged --clouds %d --points %d --width %d --rounds %d --max-rows %d" % (C, N, H, a.rounds, a.max_rows),
+             "# device: %s; exact fp32; times in ms per call (device event pairs), median [min .. max] of %d calls after 2 warm-up calls"
+             % (torch.cuda.get_device_name(0), a.rounds), ""]
+    mod = DPDistMatrix(model, max_rows=a.max_rows)
+
+    def sets(c, n):
+        return (torch.tensor(synth.s2_modelnet_shaped(c, n, 100)[0], device=dev), torch.tensor(synth.s2_modelnet_shaped(c, n, 101)[1], device=dev))
+
+    def forms(A, B, cA, cB):
+        kw = {} if cA is None else {"countsA": cA, "countsB": cB}
+        G = torch.tensor(np.random.default_rng(7).standard_normal((A.shape[0], B.shape[0])).astype(np.float32), device=dev)
+
+        def grad():
+            x, y = A.detach().requires_grad_(True), B.detach().requires_grad_(True)
+            (G * mod(x, y, **kw)).sum().backward()
+        return (lambda: dpdist_matrix(model, A, B, max_rows=a.max_rows, **kw)), grad
+
+    def med(fn):
+        for _ in range(2):
+            fn()
+        v = [timed(fn) for _ in range(a.rounds)]
+        return float(np.median(v)), "%9.3f [%9.3f .. %9.3f]" % (float(np.median(v)), min(v), max(v))
+
+    # (1) ragged against full, same padded width
+    A, B = sets(C, N)
+    cA, cB = (torch.tensor(rng.integers(max(1, N // 4), N + 1, size=C), dtype=torch.int32, device=dev) for _ in range(2))
+    lines.append("(1) Ca = Cb = %d, padded width N = %d, H = %d; counts uniform in [%d, %d]: mean %.1f (A), %.1f (B)"
+                 % (C, N, H, max(1, N // 4), N, float(cA.float().mean()), float(cB.float().mean())))
+    for name, (fwd, grad) in (("full sets, no counts", forms(A, B, None, None)), ("ragged sets, counts", forms(A, B, cA, cB))):
+        lines.append("    %-24s forward %s   forward+backward %s" % (name, med(fwd)[1], med(grad)[1]))
+    lines.append("    (the padded rows are not compacted out of the decoder GEMMs: a ragged set pays for its padded width)")
+    # (2) counts == N against no counts where both encode over tiles
+    N2, C2 = 2048, min(C, 8)
+    A, B = sets(C2, N2)
+    full = torch.full((C2,), N2, dtype=torch.int32, device=dev)
+    lines += ["", "(2) Ca = Cb = %d, N = %d, H = %d: all counts = N beside the call without counts (both encode over tiles), 3 repetitions" % (C2, N2, H)]
+    un, co = forms(A, B, None, None), forms(A, B, full, full)
+    same = all(torch.equal(x, y) for x, y in zip(dpdist_matrix(model, A, B, return_directed=True, max_rows=a.max_rows),
+                                                 dpdist_matrix(model, A, B, return_directed=True, max_rows=a.max_rows, countsA=full, countsB=full)))
+    lines.append("    the two forward results are bit for bit equal: %s" % same)
+    for k, what in ((0, "forward"), (1, "forward+backward")):
+        m_un, m_co = [], []
+        for rep_ in range(3):
+            u, c = med(un[k]), med(co[k])
+            m_un.append(u[0]), m_co.append(c[0])
+            lines.append("    %-16s rep %d   no counts %s   counts = N %s" % (what, rep_, u[1], c[1]))
+        spread = max(m_un) - min(m_un)
+        diff = float(np.median(m_co)) - float(np.median(m_un))
+        lines.append("    %-16s median of medians: no counts %.3f, counts = N %.3f; difference %+.3f ms; spread of the three un-counted medians %.3f ms"
+                     " -> %s" % (what, float(np.median(m_un)), float(np.median(m_co)), diff, spread,
+                                 "equal within that spread" if abs(diff) <= spread else "NOT within that spread"))
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clouds", type=int, default=32)
@@ -112,6 +181,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--max-rows", type=int, default=16384)
     ap.add_argument("--grad", action="store_true", help="forward + backward under a random upstream matrix")
+    ap.add_argument("--ragged", action="store_true", help="ragged sets: what per-cloud counts cost (writes --out)")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ragged_matrix_bench.txt"))
     a = ap.parse_args()
     C, N, H = a.clouds, a.points, a.width
     dev = torch.device("cuda:0")
@@ -120,6 +191,10 @@ def main():
     B = torch.tensor(synth.s2_modelnet_shaped(C, N, 101)[1], device=dev)
     model = DPDistModel(Embedding_Size=512, k=5, localSNmlp=(H,) * 3, sigma3dmfv=0.125, device=dev)
     model.load_tf_state_dict(synth.make_weights("wide", mlp=(H,) * 3))
+    if a.ragged:
+        for prm in model.parameters():
+            prm.requires_grad_(False)
+        return ragged(a, dev, model)
     if a.grad:
         for prm in model.parameters():
             prm.requires_grad_(False)       # as-loss mode: the decoder is frozen in both forms
