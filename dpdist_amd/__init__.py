@@ -19,4 +19,7 @@ def __getattr__(name):
     if name in ("dpdist_matrix", "DPDistMatrix", "pad_clouds"):
         from . import pairwise
         return getattr(pairwise, name)
+    if name in ("dpdist_pairs", "DPDistPairs"):
+        from . import pairs
+        return getattr(pairs, name)
     raise AttributeError(name)

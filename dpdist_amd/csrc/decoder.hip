@@ -1031,6 +1031,102 @@ __global__ __launch_bounds__(256) void pair_mean_counts_kernel(const float* __re
     pair_mean_block<true>(pred, N, pairs, Dd, qcounts, Cb);
 }
 
+// Paired distances of clouds of different sizes (dpd_decoder_out_pairs).  Row layout of P pairs: the AB half first (row b Wb + n: query
+// B_b[n], Wb rows per pair, real while n < countsB[b]), then the BA half at P Wb (row P Wb + b Wa + n: query A_b[n], real while
+// n < countsA[b]).  A segment = one (direction, pair): its rows are contiguous, its length is the query set's width, and neither its
+// start nor its length is aligned with anything (widths like 37, 5, 1; the two halves differ).
+struct PairSeg {
+    int b, n, cnt;      // pair, query index inside the segment, the segment's real queries (clamped into [1, width])
+    long row0;          // first row of the segment
+};
+__device__ __forceinline__ int pair_count(const int32_t* __restrict__ counts, int b, int W) { return counts ? min(max(counts[b], 1), W) : W; }
+__device__ __forceinline__ PairSeg pair_seg_of_row(long row, int P, int Wa, int Wb, const int32_t* __restrict__ cA,
+                                                   const int32_t* __restrict__ cB) {
+    const long nab = (long)P * Wb;
+    const bool ba = row >= nab;
+    const long rr = ba ? row - nab : row;
+    const int W = ba ? Wa : Wb;
+    PairSeg s;
+    s.b = (int)(rr / W);
+    s.n = (int)(rr - (long)s.b * W);
+    s.cnt = pair_count(ba ? cA : cB, s.b, W);
+    s.row0 = row - s.n;
+    return s;
+}
+
+// One wave per row: y / pred through out_row_dot (the bits of out_fwd_kernel), and -- with dy -- the output-layer backward of
+// sum_b (D_AB[b] + D_BA[b]): unit upstream per directed distance, 1 / count of the row's own segment on channel 0, as out_asloss_kernel
+// forms it.  The row of a padded query (n >= count) is written as +0.0 in dy and g3, whatever the sign of W4.
+__global__ __launch_bounds__(256) void out_pairs_kernel(const float* __restrict__ h3, const float* __restrict__ W4,
+                                                         const float* __restrict__ b4, const float* __restrict__ mask,
+                                                         float* __restrict__ y, float* __restrict__ pred, float* __restrict__ dy,
+                                                         float* __restrict__ g3, int P, int Wa, int Wb, const int32_t* __restrict__ cA,
+                                                         const int32_t* __restrict__ cB, int H) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long)P * ((long)Wa + Wb)) return;
+    const float* h = h3 + (size_t)row * H;
+    float a[3];
+    OutRowRegs rr;
+    out_row_dot(h, W4, H, lane, a, &rr);
+    const float mk = mask[row];
+    float yv[3], pv[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        yv[c] = a[c] + b4[c];
+        pv[c] = fminf(fmaxf(yv[c], 0.f), 6.f) / 3.0f * mk;
+    }
+    if (lane < 3) {
+        y[(size_t)row * 3 + lane] = lane == 0 ? yv[0] : (lane == 1 ? yv[1] : yv[2]);
+        pred[(size_t)row * 3 + lane] = lane == 0 ? pv[0] : (lane == 1 ? pv[1] : pv[2]);
+    }
+    if (!dy) return;
+    const PairSeg sg = pair_seg_of_row(row, P, Wa, Wb, cA, cB);
+    const bool real = sg.n < sg.cnt;
+    const float d0 = (real && yv[0] > 0.f && yv[0] < 6.f) ? (1.0f / (float)sg.cnt) * mk / 3.0f : 0.f;
+    if (lane < 3) dy[(size_t)row * 3 + lane] = lane == 0 ? d0 : 0.f;
+    float* g = g3 + (size_t)row * H;
+    if (out_row_fast(W4, H)) {
+#pragma unroll
+        for (int i = 0; i < kOutMaxI; ++i) {
+            const int k = 4 * lane + 256 * i;
+            if (k < H) {
+                const float4 x = rr.h[i];
+                float4 o;
+                o.x = (real && x.x > 0.f) ? d0 * rr.w0[i][0] : 0.f;
+                o.y = (real && x.y > 0.f) ? d0 * rr.w0[i][1] : 0.f;
+                o.z = (real && x.z > 0.f) ? d0 * rr.w0[i][2] : 0.f;
+                o.w = (real && x.w > 0.f) ? d0 * rr.w0[i][3] : 0.f;
+                *reinterpret_cast<float4*>(g + k) = o;
+            }
+        }
+    } else {
+        for (int k = lane; k < H; k += 64) g[k] = (real && h[k] > 0.f) ? d0 * W4[k * 3] : 0.f;
+    }
+}
+
+// Dd [2, P]: one workgroup per segment.  Thread t adds pred[:, 0] of the segment's real rows t, t + 256, ... in 2^-32 fixed point
+// (pred lies in [0, 2]: at most 2^33 per row), the 256 partial sums are added in a tree through LDS: integer addition, so the sum is
+// exact, the same on every run and independent of what else the launch holds.  One rounding to double, one division, one to float.
+__global__ __launch_bounds__(256) void pairs_mean_kernel(const float* __restrict__ pred, int P, int Wa, int Wb,
+                                                          const int32_t* __restrict__ cA, const int32_t* __restrict__ cB,
+                                                          float* __restrict__ Dd) {
+    __shared__ unsigned long long s_part[256];
+    const int ba = blockIdx.x >= (unsigned)P, b = ba ? blockIdx.x - P : blockIdx.x;
+    const int W = ba ? Wa : Wb;
+    const int cnt = pair_count(ba ? cA : cB, b, W);
+    const float* src = pred + ((size_t)(ba ? (long)P * Wb : 0L) + (size_t)b * W) * 3;
+    unsigned long long acc = 0;
+    for (int n = threadIdx.x; n < cnt; n += 256) acc += (unsigned long long)__double2ll_rn((double)src[(size_t)n * 3] * 4294967296.0);
+    s_part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) s_part[threadIdx.x] += s_part[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) Dd[blockIdx.x] = (float)((double)s_part[0] * (1.0 / 4294967296.0) / (double)cnt);
+}
+
 }  // namespace dpd
 
 extern "C" int dpd_set_gemm_plan(int op, int tile, int split_k) {
@@ -1335,6 +1431,26 @@ extern "C" int dpd_decoder_out_asloss_planes(const float* h3, const float* mask,
     // W4 -> wave sums -> stores -> the atomic's return), not a throughput problem
     DPD_LAUNCH(out_asloss_kernel<2>, dim3((Q + 7) / 8), dim3(256), 0, (hipStream_t)stream, h3, p->W4, p->b4, mask, y, pred, dy, g3, Q, H, BN, gv,
                loss_pred, (unsigned long long*)scratch, g3_rc, g3_rc ? (long)Q * H : 0L, g3_rc ? pl->np : 0);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_decoder_out_pairs(const float* h3, const float* mask, int P, int Wa, int Wb, const int32_t* countsA, const int32_t* countsB,
+                                     int H, const dpd_decoder_params* p, float* y, float* pred, float* Dd, float* dy, float* g3, void* stream) {
+    using namespace dpd;
+    if (!h3 || !mask || !p || !p->W4 || !p->b4 || !y || !pred || !Dd || (!dy != !g3)) return DPD_E_NULL;
+    if (P <= 0 || Wa <= 0 || Wb <= 0 || H <= 0 || (long)P * ((long)Wa + Wb) > (1L << 30)) return DPD_E_DIM;
+    if (((uintptr_t)h3 & 15) || ((uintptr_t)g3 & 15)) return DPD_E_UNSUPPORTED;      // the rows are read and written 16 bytes per lane
+    hipStream_t s = (hipStream_t)stream;
+    const long Q = (long)P * ((long)Wa + Wb);
+    {
+        StageProf prof(stream, DPD_STAGE_OUT_LAYER, (double)Q * H * 4.0 * (g3 ? 2.0 : 1.0) + Q * (dy ? 40.0 : 28.0) + H * 12.0);
+        DPD_LAUNCH(out_pairs_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, h3, p->W4, p->b4, mask, y, pred, dy, g3, P, Wa, Wb, countsA,
+                   countsB, H);
+        DPD_CHECK_LAUNCH();
+    }
+    StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)Q * 12.0 + P * 8.0);
+    DPD_LAUNCH(pairs_mean_kernel, dim3(2 * P), dim3(256), 0, s, (const float*)pred, P, Wa, Wb, countsA, countsB, Dd);
     DPD_CHECK_LAUNCH();
     return 0;
 }

@@ -507,6 +507,80 @@ __global__ __launch_bounds__(256) void asloss_combine_kernel(const float* __rest
     (which ? gB : gA)[(size_t)r * 3 + c] = v;
 }
 
+// Paired distances of clouds of different sizes (dpd_patch_rows_fwd_counts): patch_rows_fwd_kernel with a per-cloud query count.  Query
+// n >= counts[c] (clamped into [1, N]) is padding: it is not read, its row is KP zeros, its mask 0 and its voxel 0.  A real query's row
+// is a copy of the cloud's (normalised) Fisher vectors, so it has the bits of every form of the un-counted gather.
+__global__ __launch_bounds__(256) void patch_rows_fwd_counts_kernel(const float* __restrict__ q, const int32_t* __restrict__ qcounts,
+                                                                     const float* __restrict__ fv, float* __restrict__ X,
+                                                                     float* __restrict__ mask, int32_t* __restrict__ vox, int N, int m,
+                                                                     int k, int KP, GridAxis ax, int Q) {
+    const int r = blockIdx.x * 2 + (threadIdx.x >> 7), tid = threadIdx.x & 127;   // two rows per workgroup, 128 threads each
+    if (r >= Q) return;
+    const int c = r / N, n = r - c * N;
+    float* xr = X + (size_t)r * KP;
+    if (n >= min(max(qcounts[c], 1), N)) {
+        for (int j = tid; j < KP / 4; j += 128) *reinterpret_cast<float4*>(xr + j * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid == 0) {
+            mask[r] = 0.f;
+            vox[r] = 0;
+        }
+        return;
+    }
+    const int G = m * m * m, h = (k - 1) / 2;
+    const float qx = q[(size_t)r * 3], qy = q[(size_t)r * 3 + 1], qz = q[(size_t)r * 3 + 2];
+    int ix = cell_of(ax, m, qx), iy = cell_of(ax, m, qy), iz = cell_of(ax, m, qz);
+    const bool valid = (ix >= 0) && (iy >= 0) && (iz >= 0);
+    if (!valid) { ix = 0; iy = 0; iz = 0; }
+    const int E4 = k * k * k * (kF / 4);
+    const float* fvc = fv + (size_t)c * G * kF;
+    for (int j = tid; j < E4; j += 128) {
+        const int nb = j / 5, part = j % 5;
+        const int d0 = nb / (k * k), d1 = (nb / k) % k, d2 = nb % k;
+        const int g0 = iy + d0 - h, g1 = ix + d1 - h, g2 = iz + d2 - h;   // grid axes are (y, x, z), slowest first
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if ((unsigned)g0 < (unsigned)m && (unsigned)g1 < (unsigned)m && (unsigned)g2 < (unsigned)m)
+            v = *reinterpret_cast<const float4*>(fvc + (size_t)((g0 * m + g1) * m + g2) * kF + part * 4);
+        *reinterpret_cast<float4*>(xr + j * 4) = v;
+    }
+    const int E = E4 * 4;
+    if (tid == 0) {
+        xr[E + 0] = qx - ax.c[ix];
+        xr[E + 1] = qy - ax.c[iy];
+        xr[E + 2] = qz - ax.c[iz];
+        for (int e = E + 3; e < KP; ++e) xr[e] = 0.f;
+        mask[r] = valid ? 1.f : 0.f;
+        vox[r] = (iy * m + ix) * m + iz;
+    }
+}
+
+// Tail of the paired backward (dpd_pairs_combine): the two per-pair upstream scalars applied once, to the encoder route and to the query
+// route (the q - centre columns of dX; A_b is queried by the BA half, rows P Wb + b Wa + n, B_b by the AB half, rows b Wb + n).  One
+// thread per output element over [P Wa 3 | P Wb 3]; rows at or beyond a cloud's count are written as +0.0.
+__global__ __launch_bounds__(256) void pairs_combine_kernel(const float* __restrict__ dptsA, const float* __restrict__ dptsB,
+                                                             const float* __restrict__ dX, const float* __restrict__ G_ab,
+                                                             const float* __restrict__ G_ba, int P, int Wa, int Wb,
+                                                             const int32_t* __restrict__ cA, const int32_t* __restrict__ cB, int KP, int E,
+                                                             float* __restrict__ gA, float* __restrict__ gB) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long nA = (long)P * Wa * 3, nB = (long)P * Wb * 3;
+    if (i >= nA + nB) return;
+    const bool isB = i >= nA;
+    const long e = isB ? i - nA : i;
+    float* out = isB ? gB : gA;
+    if (!out) return;
+    const int W = isB ? Wb : Wa;
+    const long r = e / 3;
+    const int c = (int)(e - r * 3), b = (int)(r / W), n = (int)(r - (long)b * W);
+    const int32_t* cnt = isB ? cB : cA;
+    float v = 0.f;
+    if (n < (cnt ? min(max(cnt[b], 1), W) : W)) {
+        const float gs = (isB ? G_ba : G_ab)[b], gq = (isB ? G_ab : G_ba)[b];       // surface route, query route
+        const long qrow = isB ? r : (long)P * Wb + r;
+        v = gs * (isB ? dptsB : dptsA)[e] + gq * dX[(size_t)qrow * KP + E + c];
+    }
+    out[e] = v;
+}
+
 // pts = [pcA + noise ; pcB] (encoder input), q = [pcB ; pcA] (query clouds): models/dpdist_and_aue.py:45,56-61,69
 __global__ __launch_bounds__(256) void stack_clouds_kernel(const float* __restrict__ pcA, const float* __restrict__ pcB,
                                                             const float* __restrict__ noise, int n, float* __restrict__ pts,
@@ -765,6 +839,35 @@ extern "C" int dpd_asloss_combine(const float* dpts, const float* dX, const floa
     if (KP < k * k * k * kF + 3) return DPD_E_DIM;
     const int n = 2 * B * N * 3;
     DPD_LAUNCH(asloss_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dpts, dX, scale, B * N, KP, k * k * k * kF, gA, gB);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_patch_rows_fwd_counts(const float* q, const int32_t* qcounts, const float* fv, int C, int N, int m, int k, int KP,
+                                         float* X, float* mask, int32_t* vox, void* stream) {
+    using namespace dpd;
+    if (!q || !qcounts || !fv || !X || !mask || !vox) return DPD_E_NULL;
+    if (C <= 0 || N <= 0 || (long)C * N > (1L << 30)) return DPD_E_DIM;
+    if (m < 1 || m > 10 || k < 1 || k > 7 || !(k & 1)) return DPD_E_UNSUPPORTED;
+    if (KP < k * k * k * kF + 3 || (KP & 3)) return DPD_E_DIM;
+    const int Q = C * N;
+    StageProf prof(stream, DPD_STAGE_GATHER, (double)C * m * m * m * kF * 4.0 + Q * 12.0 + Q * 8.0 + (double)Q * KP * 4.0);
+    DPD_LAUNCH(patch_rows_fwd_counts_kernel, dim3((Q + 1) / 2), dim3(256), 0, (hipStream_t)stream, q, qcounts, fv, X, mask, vox, N, m, k, KP,
+               make_axis(m), Q);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_pairs_combine(const float* dptsA, const float* dptsB, const float* dX, const float* G_ab, const float* G_ba, int P, int Wa,
+                                 int Wb, const int32_t* countsA, const int32_t* countsB, int k, int KP, float* gA, float* gB, void* stream) {
+    using namespace dpd;
+    if (!dX || !G_ab || !G_ba || (!gA && !gB) || (gA && !dptsA) || (gB && !dptsB)) return DPD_E_NULL;
+    if (P <= 0 || Wa <= 0 || Wb <= 0 || (long)P * ((long)Wa + Wb) > (1L << 30)) return DPD_E_DIM;
+    if (k < 1 || k > 7 || !(k & 1)) return DPD_E_UNSUPPORTED;
+    if (KP < k * k * k * kF + 3) return DPD_E_DIM;
+    const long n = (long)P * ((long)Wa + Wb) * 3;
+    DPD_LAUNCH(pairs_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dptsA, dptsB, dX, G_ab, G_ba, P, Wa,
+               Wb, countsA, countsB, KP, k * k * k * kF, gA, gB);
     DPD_CHECK_LAUNCH();
     return 0;
 }

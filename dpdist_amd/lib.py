@@ -94,6 +94,10 @@ SIGNATURES = {
     "dpd_cross_index_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "dpd_decoder_fwd_cross_counts": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int] * 5 + [POINTER(DecoderParams)] + [c_void_p] * 6),
     "dpd_cross_bwd_counts": (c_int, [c_void_p] * 11 + [c_int] * 8 + [POINTER(DecoderParams)] + [c_void_p] * 10),
+    # paired distances of clouds of different sizes (dpdist_amd/pairs.py)
+    "dpd_patch_rows_fwd_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dpd_decoder_out_pairs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(DecoderParams)] + [c_void_p] * 6),
+    "dpd_pairs_combine": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

@@ -487,8 +487,15 @@ class DPDistLoss(nn.Module):
         P = self.model.params_
         return (P.flat.data_ptr(), P.flat._version, P.compute_dtype, P.__dict__.get("_derived_gen", 0))
 
-    def forward(self, source, template):
+    def forward(self, source, template, counts_source=None, counts_template=None):
+        """source, template [B,N,3] of one shape, no counts: the as-loss node above.  Clouds of different sizes -- two widths
+        (source [B,Ws,3], template [B,Wt,3]) and / or per-cloud counts (cloud b of a set is its first counts[b] points, as in
+        dpdist_amd.pairs.dpdist_pairs) -- give the mean over the pairs of DPDistPairs, each pair at its own sizes; exact fp32 only
+        (ValueError otherwise)."""
         mod = self.model
+        if counts_source is not None or counts_template is not None or source.shape != template.shape:
+            from .pairs import DPDistPairs
+            return DPDistPairs(mod)(source, template, countsA=counts_source, countsB=counts_template).mean()
         m = int(math.ceil(mod.Embedding_Size ** (1 / 3) - 1e-9))
         return _AsLossFn.apply(source.contiguous(), template.contiguous(), mod.params_.flat, mod.params_, m, mod.k,
                                float(mod.sigma))

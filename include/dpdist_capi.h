@@ -358,6 +358,47 @@ int dpd_cross_bwd_counts(const float* Gd, const float* maskr, const int32_t* qco
                          int Ca_chunk, int Cb, int N, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dpred,
                          float* dy, float* ga, float* gb, float* dq, float* gs, float* dXs, float* dfv, float* gQ, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PAIRED distances of clouds of different sizes (DPD_F32): pair b of two sets A [P,Wa,3] and B [P,Wb,3], each with optional per-cloud
+ * counts (int32, DEVICE memory, as in the RAGGED block; NULL here = the set is full), gives the two halves the reference computes for
+ * one pair at that pair's own sizes (models/dpdist_and_aue.py:56-69, utils/dpdist_util.py:494-511, 690-698, 976-977):
+ *   D_AB[b] = (1 / nB[b]) sum_{n < nB[b]} pred(surface A_b[:nA[b]] ; query B_b[n])[0]
+ *   D_BA[b] = (1 / nA[b]) sum_{n < nA[b]} pred(surface B_b[:nB[b]] ; query A_b[n])[0]
+ * -- the diagonal of the all-pairs matrix above, at P instead of P^2 decoder evaluations.  A real query outside the cube adds 0 and
+ * still counts in the denominator.  Row layout of a chunk of P pairs, Q = P (Wb + Wa) rows:
+ *   AB half   row b Wb + n          query B_b[n], surface A_b       (rows [0, P Wb))
+ *   BA half   row P Wb + b Wa + n   query A_b[n], surface B_b       (rows [P Wb, Q))
+ * so a rectangular call (Wa != Wb, no counts) wastes no row; raggedness inside a set costs masked rows.  The rules of the RAGGED block
+ * hold: the host never reads a device word, the kernels clamp every count into [1, width], padding is never read, every refusal
+ * happens before anything is launched and leaves the outputs untouched.  The rest of the chain is existing entries, called as they are:
+ * dpd_mfv3d_fwd[_tiled | _counts] per set, dpd_decoder_fwd with y = pred = NULL, dpd_decoder_bwd_data with phases = 6 and the g3 below,
+ * dpd_patch_rows_bwd per half (a padded row carries dX = 0 and voxel 0: it adds nothing), dpd_mfv3d_bwd[_tiled | _counts] per set.
+ *
+ * dpd_patch_rows_fwd_counts: dpd_patch_rows_fwd (fp32 rows, no planes) with a per-cloud query count: query n >= qcounts[c] is not read,
+ *   its row of X is written as KP times +0.0, its mask as 0 and its voxel as 0; a real query gets the bits of dpd_patch_rows_fwd.
+ *   Called once per half with the OTHER set's Fisher vectors.  qcounts = NULL is DPD_E_NULL; every other refusal is dpd_patch_rows_fwd's.
+ * dpd_decoder_out_pairs: the output layer over the Q rows of that layout: h3 [Q,H], mask [Q] -> y, pred [Q,3], the bits of
+ *   dpd_decoder_fwd's output layer on those rows, and Dd [2,P] = (D_AB ; D_BA): the sum of pred[:,0] over each pair's real queries in
+ *   2^-32 fixed point (an integer sum: exact, the same bits on every run, independent of the other pairs of the launch) divided by the
+ *   pair's count.  pred must be finite.  With dy [Q,3] and g3 [Q,H] (both or neither) also the output-layer backward of
+ *   sum_b (D_AB[b] + D_BA[b]): dy = ((1 / count) mask / 3 [0 < y0 < 6], 0, 0) with the count of the row's own segment, g3 = dy0
+ *   W4[:,0] [h3 > 0]; the rows of padded queries are +0.0 in both.  Two launches (rows; segment sums).  P, Wa, Wb >= 1 and Q <= 2^30,
+ *   else DPD_E_DIM (a segment's fixed-point sum then stays below 2^64); h3 and g3 16-byte aligned, else DPD_E_UNSUPPORTED.
+ * dpd_pairs_combine: the tail of the backward in one launch.  Everything between the output layer and the inputs is linear in the two
+ *   per-pair upstream scalars G_ab, G_ba [P] (device vectors: d loss / d D_AB, d loss / d D_BA, the gradient of D = (D_AB + D_BA) / 2
+ *   folded in by the caller), so they are applied once, here: with dptsA [P,Wa,3], dptsB [P,Wb,3] the encoder routes (dpd_mfv3d_bwd*
+ *   of the AB half's dfv with A, of the BA half's with B) and dq = the q - centre columns of dX [Q,KP],
+ *     gA[b,n] = G_ab[b] dptsA[b,n] + G_ba[b] dq[P Wb + b Wa + n]        (A_b is the query of the BA half)
+ *     gB[b,n] = G_ba[b] dptsB[b,n] + G_ab[b] dq[b Wb + n]
+ *   and rows n >= the cloud's count are written as +0.0.  gA = NULL or gB = NULL (not both): that set needs no gradient and its dpts
+ *   may be NULL.  KP >= 20 k^3 + 3, k odd, 1 <= k <= 7.                                                                              */
+int dpd_patch_rows_fwd_counts(const float* q, const int32_t* qcounts, const float* fv, int C, int N, int m, int k, int KP, float* X,
+                              float* mask, int32_t* vox, void* stream);
+int dpd_decoder_out_pairs(const float* h3, const float* mask, int P, int Wa, int Wb, const int32_t* countsA, const int32_t* countsB, int H,
+                          const dpd_decoder_params* p, float* y, float* pred, float* Dd, float* dy, float* g3, void* stream);
+int dpd_pairs_combine(const float* dptsA, const float* dptsB, const float* dX, const float* G_ab, const float* G_ba, int P, int Wa, int Wb,
+                      const int32_t* countsA, const int32_t* countsB, int k, int KP, float* gA, float* gB, void* stream);
+
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in
  *               dpd_decoder_fwd / dpd_decoder_bwd_data (ws may be NULL);
