@@ -516,6 +516,9 @@ int gemm_f32(const GemmF32Call& c) {
     if (c.colsum && split_k > 1) return DPD_E_UNSUPPORTED;
     if (c.M_dev && (!f32_tile_rs(tile) || split_k > 1 || g.tail_split || c.A2 || c.colsum || c.cs2)) return DPD_E_UNSUPPORTED;
     g.M_dev = c.M_dev;
+    if (c.K_dev && (!f32_tile_rs(tile) || !c.transA || split_k > 1 || g.tail_split || c.M_dev || c.colsum || (c.cs2 && c.cs2->part_out) || (K & 31)))
+        return DPD_E_UNSUPPORTED;
+    g.K_dev = c.K_dev;
     g.M = M; g.N = N; g.K = K; g.lda = c.lda; g.ldb = c.ldb;
     g.split_k = split_k;
     if (split_k > 1) {
@@ -552,6 +555,8 @@ extern "C" int dpd_prof_enable(int on) {
     }
     return 0;
 }
+
+extern "C" int dpd_prof_enabled(void) { return dpd::g_prof.on ? dpd::g_prof.mode : 0; }      // (like prof_begin: the common case takes no lock)
 
 // Synchronises with the recorded events; returns the number of launches with tag `tag` (and, form >= 0, product form `form`) seen since
 // dpd_prof_enable and fills their summed milliseconds and flops / bytes

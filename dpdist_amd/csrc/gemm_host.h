@@ -33,7 +33,8 @@ struct GemmF32Call {
     const float* B2 = nullptr;
     float* C2 = nullptr;
     const ColsumTwoStep* cs2 = nullptr;   // two-step bias gradient (register-streamed kernels)
-    const int* M_dev = nullptr;           // GemmArgs::M_dev (TN, tiles 32 / 33, no split): M is then the capacity
+    const int* M_dev = nullptr;           // GemmArgs::M_dev (TN or NN, tiles 32 / 33, no split): M is then the capacity
+    const int* K_dev = nullptr;           // GemmArgs::K_dev (TN, tiles 32 / 33, no split, single or grouped): K is then the capacity
 };
 int gemm_f32(const GemmF32Call& c);
 

@@ -57,10 +57,14 @@ __device__ __forceinline__ void rs_load_step(__amdgpu_buffer_rsrc_t r, unsigned 
 // D = pipeline depth in K-tiles (operand register sets): the loads of K-tile t+D-1 are issued, step by step, between the
 // MFMAs of K-tile t, so every operand has D-1 whole tile times ((TM*TN*16) MFMAs x 64 cycles each) to arrive.
 // DM: the live row count comes from the device word g.M_dev (GemmArgs::M_dev); g.M is the capacity the grid was launched for.
-template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D, bool DM = false>
+// DK: the live contraction length comes from the device word g.K_dev (GemmArgs::K_dev); g.K is the capacity the operands hold.  A
+//     length of 0 runs no K-tile at all: the accumulators leave as the zeros they were set to, and the epilogues run as always.
+template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D, bool DM = false, bool DK = false>
 __global__ __launch_bounds__(64 * WR * WC) void gemm_rs_kernel(GemmArgs g) {
     constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
     if (DM) g.M = min(g.M, __builtin_amdgcn_readfirstlane(*g.M_dev));
+    const int Kcap = g.K;      // what the operands hold: the buffer ranges below stay those of the capacity
+    if (DK) g.K = max(0, min(g.K, __builtin_amdgcn_readfirstlane(*g.K_dev))) & ~31;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -95,8 +99,8 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_rs_kernel(GemmArgs g) {
     const float* gB = grp ? g.B2 : g.B;
     const unsigned lda = g.lda, ldb = g.ldb;
 
-    const __amdgpu_buffer_rsrc_t ra = rs_rsrc(gA, AK ? ((size_t)(g.M - 1) * lda + g.K) * 4 : ((size_t)(g.K - 1) * lda + g.M) * 4);
-    const __amdgpu_buffer_rsrc_t rb = rs_rsrc(gB, BKC ? ((size_t)(g.N - 1) * ldb + g.K) * 4 : ((size_t)(g.K - 1) * ldb + g.N) * 4);
+    const __amdgpu_buffer_rsrc_t ra = rs_rsrc(gA, AK ? ((size_t)(g.M - 1) * lda + Kcap) * 4 : ((size_t)(Kcap - 1) * lda + g.M) * 4);
+    const __amdgpu_buffer_rsrc_t rb = rs_rsrc(gB, BKC ? ((size_t)(g.N - 1) * ldb + Kcap) * 4 : ((size_t)(Kcap - 1) * ldb + g.N) * 4);
     unsigned va[TM], vb[TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(64 * WR * WC) void gemm_rs_kernel(GemmArgs g) {
     RsFrag fa[D][TM], fb[D][TN];
     // all loads of K-tile kt (clamped to the last tile: a redundant reload instead of a branch) into register set d
     auto load_step = [&](int kt, int d, int b, int s) {
-        const int ktc = min(kt, nt - 1);
+        const int ktc = DK ? max(min(kt, nt - 1), 0) : min(kt, nt - 1);      // (DK: no live K-tile at all -> tile 0 of the capacity, loaded and never used)
         const unsigned k0 = kbeg + 32u * ktc;
 #pragma unroll
         for (int i = 0; i < TM; ++i) rs_load_step<AK>(ra, va[i], k0, lda, b, s, fa[d][i]);
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(float* __restrict__ C,
     }
 }
 
-template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D, bool DM = false>
+template <bool AK, bool BKC, int TM, int TN, int WR, int WC, int D, bool DM = false, bool DK = false>
 static int launch_rs(const GemmArgs& g_in, hipStream_t s) {
     constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
     GemmArgs g = g_in;
@@ -275,7 +279,7 @@ static int launch_rs(const GemmArgs& g_in, hipStream_t s) {
             }
         }
     }
-    DPD_LAUNCH((gemm_rs_kernel<AK, BKC, TM, TN, WR, WC, D, DM>), dim3(nblk), dim3(64 * WR * WC), 0, s, g);
+    DPD_LAUNCH((gemm_rs_kernel<AK, BKC, TM, TN, WR, WC, D, DM, DK>), dim3(nblk), dim3(64 * WR * WC), 0, s, g);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
     if (g.tail_split > 1) {
         const long total4 = (long)(g.M - row0) * g.N / 4;
@@ -290,11 +294,19 @@ static int launch_rs(const GemmArgs& g_in, hipStream_t s) {
 // tile codes 30..33: register-streamed kernels (wave tile, waves per workgroup, pipeline depth)
 template <bool AK, bool BKC>
 static int launch_rs_tile(int tile, const GemmArgs& g, hipStream_t s) {
-    if (g.M_dev) {      // live row count on the device: the TN form of the two 32-row wave tiles (a k-ordered chain per element: same bits)
-        if constexpr (!AK && !BKC) {
-            if (g.split_k != 1 || g.tail_split || g.A2) return DPD_E_UNSUPPORTED;
+    if (g.M_dev) {      // live row count on the device: the TN and NN forms of the two 32-row wave tiles (a k-ordered chain per element: same bits)
+        if constexpr (!BKC) {
+            if (g.split_k != 1 || g.tail_split || g.A2 || g.K_dev) return DPD_E_UNSUPPORTED;
             if (tile == 32) return launch_rs<AK, BKC, 1, 2, 2, 2, 2, true>(g, s);
             if (tile == 33) return launch_rs<AK, BKC, 1, 1, 2, 2, 2, true>(g, s);
+        }
+        return DPD_E_UNSUPPORTED;
+    }
+    if (g.K_dev) {      // live contraction length on the device: the TN form (single or grouped) of the same two tiles
+        if constexpr (!AK && !BKC) {
+            if (g.split_k != 1 || g.tail_split || g.K < 32) return DPD_E_UNSUPPORTED;
+            if (tile == 32) return launch_rs<AK, BKC, 1, 2, 2, 2, 2, false, true>(g, s);
+            if (tile == 33) return launch_rs<AK, BKC, 1, 1, 2, 2, 2, false, true>(g, s);
         }
         return DPD_E_UNSUPPORTED;
     }

@@ -47,9 +47,14 @@ struct GemmArgs {
     float* tail_slab;
     int k_chunk;      // K range per split (multiple of BK)
     long slab_stride; // floats between split-K slabs (0 when split_k == 1)
-    // optional (register-streamed TN kernels, A stored [K][M]): the LIVE row count as a device word, <= M.  The grid is launched for M (the capacity);
-    // tiles, the XCD map and every clamp use the live count, workgroups beyond the live tiles leave at once.  NULL: M is the count
+    // optional (register-streamed kernels, TN with A stored [K][M] or NN with A stored [M][K]): the LIVE row count as a device word, <= M.
+    // The grid is launched for M (the capacity); tiles, the XCD map and every clamp use the live count, workgroups beyond the live tiles
+    // leave at once.  NULL: M is the count
     const int* M_dev;
+    // optional (register-streamed TN kernels): the LIVE contraction length as a device word; K is then the capacity (what the operands
+    // hold: >= 32).  The word is clamped to [0, K] and rounded down to whole 32-deep K-tiles where it is read; 0 stores a zero tile, and
+    // the second step of the bias gradient (colsum_b) runs whatever the length.  NULL: K is the length
+    const int* K_dev;
 };
 
 // host-side bundle of the two-step bias-gradient pointers (see GemmArgs::colsum_part)

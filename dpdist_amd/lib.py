@@ -55,6 +55,12 @@ class CrossChunk(Structure):   # include/dpdist_capi.h: dpd_cross_chunk (carved 
                 [(n, c_void_p) for n in BUFFERS])
 
 
+class LiveRows(Structure):     # include/dpdist_capi.h: dpd_live_rows (carved by dpd_live_rows_carve; the caller sets X .. rows_per_cloud)
+    _fields_ = ([(n, c_int) for n in ("Qb", "KP", "H")] +
+                [(n, c_void_p) for n in ("cnt", "idx", "pos", "rowflag", "g3c", "h1c", "h2c", "Xc", "X")] + [("ldx", c_int), ("ssq", c_void_p),
+                                                                                                       ("clouds", c_int), ("rows_per_cloud", c_int)])
+
+
 # name -> (restype, argtypes); mirrors include/dpdist_capi.h one to one
 SIGNATURES = {
     "dpd_version": (c_char_p, []),
@@ -116,6 +122,15 @@ SIGNATURES = {
     "dpd_decoder_bwd_weights": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                         c_void_p, c_void_p, c_size_t, POINTER(Planes), c_void_p, c_void_p]),
     "dpd_decoder_bwd_weights_pair": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_size_t, POINTER(Planes), c_void_p, c_void_p, c_void_p]),
+    "dpd_live_rows_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dpd_live_rows_carve": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, POINTER(LiveRows)]),
+    "dpd_decoder_bwd_data_live": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          POINTER(DecoderParams), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          POINTER(SmallGrads), c_void_p, c_size_t, POINTER(Planes), c_int, POINTER(LiveRows), c_void_p]),
+    "dpd_decoder_bwd_weights_live": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_size_t, POINTER(Planes), c_void_p, POINTER(LiveRows), c_void_p]),
+    "dpd_decoder_bwd_weights_pair_live": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_size_t, POINTER(Planes), c_void_p, c_void_p,
+                                                                                 POINTER(LiveRows), c_void_p]),
     "dpd_decoder_bwd_weights_trio": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(Planes), c_void_p]),
     "dpd_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t, ctypes.c_uint32]),
     "dpd_chamfer_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
@@ -168,6 +183,7 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "dpd_set_gemm_plan": (c_int, [c_int, c_int, c_int]),
     "dpd_prof_enable": (c_int, [c_int]),
+    "dpd_prof_enabled": (c_int, []),
     "dpd_prof_collect_form": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     "dpd_prof_collect": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     "dpd_prof_collect_stage": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),

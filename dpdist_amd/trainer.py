@@ -46,6 +46,10 @@ def backward_schedule(dp, order, trio, three, defer_small, last_bucket):
     three: options["dp_buckets"] == 3; last_bucket: index of the last gradient bucket):
         ("data", phases)       dpd_decoder_bwd_data; 1 = output layer, 2 = g2, 4 = g1, 16 = db3 / dW4 / db4 and the loss stay block partials
         ("dw", layer)          one weight gradient;   ("dw23",)  dW2 + dW3 (identical shapes: one grouped launch where the rows allow it)
+        (exact fp32 with options["live_rows"]: the same steps on the `_live` entries -- phase 1 also runs the compaction launch, phases
+         2 / 4 their dH product over the live rows, and every "data" step that holds phase 2 or 4 ends with the partial-sum launch of
+         db2 / db1 for its layers: one such launch in the single-GPU order, one per layer where an order splits the chain; the "dw"
+         steps contract over the live rows)
         ("dw123", fallback)    dW1 + dW2 + dW3 as ONE grouped launch; where the library does not take it, `fallback` replaces the REST of the list
         ("x_free",)            X / mask are free from here on (dW1 was their last reader): the prefetch pipeline hooks in
         ("reduce", b[, upto])  all-reduce of gradient bucket b (.. upto) behind what has been enqueued"""
@@ -89,6 +93,7 @@ class DPDistTrainer:
         "dw_trio": None,       # plane types: dW1 + dW2 + dW3 as one grouped launch (None: on for one plane, off for three)
         "dp_buckets": 2,       # data-parallel "early" order: 2 = layers 2-4 as one collective, 3 = one per layer
         "unique_l1": None,     # exact fp32: layer 1 once per distinct (cloud, voxel) window, same bits (None: on where the shapes allow it)
+        "live_rows": None,     # exact fp32: dH / dW GEMMs over the rows whose dy is not zero, same values (None: on where the shapes allow it)
     }
 
     def __init__(self, params: DPDistParams, batch_size, num_point=64, Embedding_Size=512, sigma3dmfv=0.125, base_lr=1e-4,
@@ -139,12 +144,18 @@ class DPDistTrainer:
         # plain gather and layer 1 (orthogonal to every other option: the activations have the same bits either way)
         self.unique_l1 = bool((opt["unique_l1"] is None or opt["unique_l1"]) and self.dt == 0 and N % 8 == 0 and N <= 1024 and Q % 32 == 0
                               and self.k >= 3 and KP == L.load().dpd_padded_width(self.k) and KP >= 64 and H % 64 == 0 and self.m <= 10)
+        # `live` in decoder.hip (the `_live` twins of the three backward entries): exact fp32, whole 32-row groups, dy out of the fused
+        # output-layer backward and the two-step bias gradients.  Every order of `backward_schedule` takes it as it is: the entries run the
+        # compaction with phase 1 and the partial sums of db2 / db1 with the dH product of their layer
+        self.live_rows = bool((opt["live_rows"] is None or opt["live_rows"]) and self.dt == 0 and BN % 32 == 0 and BN <= 65536
+                              and self.fuse_loss and self._det_db)
         # -- allocations: this ORDER decides the addresses (the plane memory follows the workspace) --
         self._alloc_buffers()
         self._alloc_planes(keep_f32_h=opt["keep_f32_h"])
         self._init_data_parallel(group, distributed, adam_on_side)
         self._init_adam_fuse()
         self._alloc_unique()
+        self._alloc_live()
         # one plane (bf16): dW1 + dW2 + dW3 as one grouped launch; three planes (f32x3): measured SLOWER grouped (0.557 vs 0.523 ms at B = 32:
         # its dW1 alone runs the phase-staggered 128x128 kernel, the grouped launch needs the ring kernel), so opt-in there (options["dw_trio"])
         self._trio = self._planes is not None and bool(self._planes.np == 1 if opt["dw_trio"] is None else opt["dw_trio"])
@@ -194,6 +205,23 @@ class DPDistTrainer:
         self.ucnt = torch.zeros(4, device=dev, dtype=torch.int32)                 # {U_AB, M_u, U_ABp, 0}: read by kernels only
         self._uscratch = torch.empty(L.load().dpd_patch_rows_unique_scratch_bytes(self.C, self.N), device=dev, dtype=torch.uint8)
 
+    def _alloc_live(self):
+        """Index and compact operand copies of the live-row backward (`live_rows`), allocated last like `_alloc_unique`.  `live_count`
+        is the device word pair {L, Lp} the kernels read; the step never reads it on the host."""
+        self._live = self.live_count = self._ev_live = None
+        if not self.live_rows:
+            return
+        lib, P = L.load(), self.P
+        nbytes = lib.dpd_live_rows_bytes(self.BN, P.KP, P.H)
+        self._live_mem = torch.zeros(nbytes, device=P.flat.device, dtype=torch.uint8)
+        lv = L.LiveRows()
+        L.check(lib.dpd_live_rows_carve(L.ptr(self._live_mem), nbytes, self.BN, P.KP, P.H, lv), "dpd_live_rows_carve")
+        lv.X, lv.ldx = self.X.data_ptr(), P.KP
+        if self.front2:      # non-finite clouds from the encoder's sums; the four-launch front end leaves none: the rows of X are looked at
+            lv.ssq, lv.clouds, lv.rows_per_cloud = self._ssq.data_ptr(), self.C, self.N
+        self._live = lv
+        self.live_count = self._live_mem[:16].view(torch.int32)[:2]
+
     def _alloc_planes(self, keep_f32_h):
         """The operand planes of the bf16-matrix-core compute types, then the fp32 activations the planes do not stand in for."""
         f, lib = self._f32, L.load()
@@ -208,7 +236,8 @@ class DPDistTrainer:
         # planes, so the fp32 copies are not written at all (2 x 33.5 MB per forward at B = 64); options["keep_f32_h"] keeps them
         if self._planes is None or keep_f32_h:
             self.h1, self.h2 = f(Q, H), f(Q, H)
-            self.g1, self.g2 = f(BN, H), f(BN, H)
+            # live rows: g1 / g2 hold the COMPACT rows (the first Lp); zeroed once so that every element is defined
+            self.g1, self.g2 = (torch.zeros(BN, H, device=self.P.flat.device) for _ in range(2)) if self.live_rows else (f(BN, H), f(BN, H))
         # g3: the fused output-layer backward writes it as planes when it can (`fused4`, block partials fit: `fused` in decoder.hip).
         # BN // 8 is not rounded up like _nparts: the test is only reached with planes, i.e. BN % 32 == 0, where the two are equal
         if self.g1 is not None or not (self._fused4 and (BN // 8) * self._rec <= BN * H):
@@ -298,6 +327,7 @@ class DPDistTrainer:
         """stacking + encoder + window gather of one batch on the CURRENT stream; `gate`: event to wait for before the
         gather overwrites X / mask / vox (their last reader of the previous step)."""
         self.front_launches += 1
+        self._ssq_fresh = self.front2
         if self.front2:      # two launches: (stack + encoder), (norm + gather)
             shp = (self.B, self.N, 3)
             L.check(L.load().dpd_mfv3d_fwd_stacked(L.ptr(L.req(pcA, name="pcA", shape=shp)), L.ptr(L.req(pcB, name="pcB", shape=shp)),
@@ -318,6 +348,7 @@ class DPDistTrainer:
                                           L.ptr(self.pts), L.ptr(self.q), L.cur_stream()), "dpd_stack_clouds")
 
     def _encode(self):
+        self._ssq_fresh = False      # fv leaves this encoder normalised: `_ssq` does not belong to it
         L.check(L.load().dpd_mfv3d_fwd(L.ptr(self.pts), self.C, self.N, self.m, self.sigma, L.ptr(self.fv), L.cur_stream()),
                 "dpd_mfv3d_fwd")
 
@@ -387,25 +418,34 @@ class DPDistTrainer:
             L.check(lib.dpd_l1_loss(L.ptr(self.pred), L.ptr(labels), BN, 1, 1.0, L.ptr(self.loss), L.ptr(self.dpred), s), "dpd_l1_loss")
             small = L.make_small_grads(sdb1, sdb2, gv[5], gv[6], gv[7], self._partials, db_partials=dbp)
         h3 = None if h3_in_plane else self.h3
+        # live rows (None: the dense form): the three entries below then work on the compact copies the data chain leaves behind its output layer
+        # While the library's profiler is on the dense form runs: its brackets attribute 2 M N K to a launch from the shapes the host
+        # knows, which a live launch does not have -- achieved rates (bench.py's roofline) are those of the dense kernels
+        live = self._live if not (self._live is not None and lib.dpd_prof_enabled()) else None
+        if live is not None:      # non-finite clouds: from the sums of the two-launch front end when that produced this batch
+            live.ssq = self._ssq.data_ptr() if getattr(self, "_ssq_fresh", False) else None
 
         def data(phases):
-            L.check(lib.dpd_decoder_bwd_data(L.ptr(self.dpred), L.ptr(self.mask), L.ptr(self.y), L.ptr(self.h1), L.ptr(self.h2),
-                                             L.ptr(h3), BN, P.KP, P.H, self._cparams, self.dt, L.ptr(self.dy), L.ptr(self.g3),
-                                             L.ptr(self.g2), L.ptr(self.g1), None, small, L.ptr(self.ws), wsb, self._planes,
-                                             phases, L.cur_stream()), "dpd_decoder_bwd_data")   # stream at CALL time (graph branches)
+            L.check(lib.dpd_decoder_bwd_data_live(L.ptr(self.dpred), L.ptr(self.mask), L.ptr(self.y), L.ptr(self.h1), L.ptr(self.h2),
+                                                  L.ptr(h3), BN, P.KP, P.H, self._cparams, self.dt, L.ptr(self.dy), L.ptr(self.g3),
+                                                  L.ptr(self.g2), L.ptr(self.g1), None, small, L.ptr(self.ws), wsb, self._planes,
+                                                  phases, live, L.cur_stream()), "dpd_decoder_bwd_data")   # stream at CALL time (graph branches)
+            if live is not None and (phases & 1) and self._ev_live is not None:
+                self._ev_live.record(torch.cuda.current_stream())      # the compaction has read `_ssq`: the next front end may overwrite it
 
         def dw(layer):
             act, g, dW = self._dw_operands[layer]
             db = gv[2 * layer - 1] if (det_db and layer in (1, 2)) else None
-            L.check(lib.dpd_decoder_bwd_weights(layer, L.ptr(act), act.stride(0) if act is not None else dW.shape[0], L.ptr(g), BN, dW.shape[0], dW.shape[1], self.dt,
-                                                L.ptr(dW), L.ptr(db), L.ptr(self.ws), wsb, self._planes, L.ptr(dbp) if db is not None else None, L.cur_stream()),
+            L.check(lib.dpd_decoder_bwd_weights_live(layer, L.ptr(act), act.stride(0) if act is not None else dW.shape[0], L.ptr(g), BN, dW.shape[0], dW.shape[1], self.dt,
+                                                     L.ptr(dW), L.ptr(db), L.ptr(self.ws), wsb, self._planes, L.ptr(dbp) if db is not None else None, live,
+                                                     L.cur_stream()),
                     "dpd_decoder_bwd_weights(%d)" % layer)
 
         def dw23():
             if BN % 32 == 0:      # layers 2 and 3 have identical shapes: one grouped launch
-                L.check(lib.dpd_decoder_bwd_weights_pair(L.ptr(self.h1), L.ptr(self.g2), L.ptr(gv[2]), L.ptr(self.h2), L.ptr(self.g3),
-                                                         L.ptr(gv[4]), P.H, BN, P.H, P.H, self.dt, L.ptr(self.ws), wsb, self._planes,
-                                                         L.ptr(gv[3]) if det_db else None, L.ptr(dbp), L.cur_stream()),
+                L.check(lib.dpd_decoder_bwd_weights_pair_live(L.ptr(self.h1), L.ptr(self.g2), L.ptr(gv[2]), L.ptr(self.h2), L.ptr(self.g3),
+                                                              L.ptr(gv[4]), P.H, BN, P.H, P.H, self.dt, L.ptr(self.ws), wsb, self._planes,
+                                                              L.ptr(gv[3]) if det_db else None, L.ptr(dbp), live, L.cur_stream()),
                         "dpd_decoder_bwd_weights_pair")
             else:
                 dw(2)
@@ -532,6 +572,8 @@ class DPDistTrainer:
                 # device-local ordering only: events without the system-scope fence (a torch.cuda.Event record in mid-stream costs
                 # the compute stream ~6 us, these 0.3 us: tools/event_cost.py)
                 self._ev_front, self._ev_xfree, self._ev_fwd = (LightEvent(system_fence=False) for _ in range(3))
+                if self._live is not None:
+                    self._ev_live = LightEvent(system_fence=False)
             main = torch.cuda.current_stream()
             self._ev_fwd.record(main)                  # inputs complete + this step's gather/decoder ordered before the side work
 
@@ -539,6 +581,8 @@ class DPDistTrainer:
                 self._ev_xfree.record(main)            # recorded right after dW1, the last reader of X / mask
                 with torch.cuda.stream(self._side):
                     self._ev_fwd.wait(self._side)
+                    if self._ev_live is not None:      # (recorded by this step's data chain, which was enqueued before dW1)
+                        self._ev_live.wait(self._side)
                     self._front(*prefetch, gate=self._ev_xfree)
                     self._ev_front.record(self._side)
                 self._pref_key = self._key(*prefetch)

@@ -493,6 +493,55 @@ int dpd_decoder_bwd_weights_pair(const float* actA, const float* gA, float* dWA,
  * dpd_decoder_bwd_data stored in dpd_small_grads::db_partials (see there).  db_partials == NULL with db != NULL in
  * dpd_decoder_bwd_weights keeps the older two-kernel column sum.                                                         */
 
+/* Live rows (DPD_F32 only): the backward GEMMs over the rows that carry gradient.
+ * A row r with dy[r] == (0, 0, 0) -- the relu6 clamp or the mask of the output layer zeroed it -- has zero rows in g3, g2, g1 and
+ * adds exact zeros to dW1..dW3, db1, db2.  With a descriptor the `_live` twins of the three entries above leave those rows out:
+ *   dpd_decoder_bwd_data_live     behind the output layer (phase 1) ONE launch builds the index of the live rows -- L of them,
+ *       Lp = L rounded up to 32, both device words: the host never reads a count -- and compact copies g3c / h1c / h2c / Xc of
+ *       their rows (positions L .. Lp: zero rows); the dH products (phases 2 / 4) run over the Lp rows only and write g2 / g1 as
+ *       COMPACT rows (g3 and dy stay dense; rows of g2 / g1 from Lp on keep what they held); one more launch rebuilds the 32-row
+ *       partial sums of sg->db_partials from them (in the dense association).  Needs p->W2T / p->W3T, fp32 operands, no dX, no
+ *       phase 8, and db1 / db2 either through sg->db_partials or not at all.
+ *   dpd_decoder_bwd_weights_live  layers 1-3: dW = (compact activation)^T (compact g) with the contraction length Lp read from the
+ *       device word; `act` is not read (the descriptor's copy is), `g` = the compact g1 / g2 (layer 3: not read, g3c is);
+ *       db only with db_partials (layers 1, 2).  Lp = 0 writes zero gradients.
+ *   dpd_decoder_bwd_weights_pair_live  (layer 2, layer 3) likewise; actA / actB / gB are not read.
+ * live == NULL: exactly the entry without the suffix.
+ * VALUES: every gradient compares == to the dense entries' (the sign of a zero may differ): a dW element is one fused-multiply-add
+ * chain over the rows in the kernel's visit order and the compact positions keep the live rows in that order; rows whose layer-1
+ * input is not finite (a cloud the encoder turned to NaN) count as live, so that the dense NaN * 0 = NaN stays.  With non-finite
+ * WEIGHTS the two forms may differ (0 * inf).
+ * The caller owns the memory: dpd_live_rows_carve cuts one buffer of dpd_live_rows_bytes (256-byte aligned) into the members and
+ * sets Qb / KP / H; the caller then sets X / ldx (the layer-1 input rows [Qb,KP], row stride ldx) and EITHER ssq / clouds /
+ * rows_per_cloud (the sums dpd_mfv3d_fwd_stacked left, [clouds][DPD_MFV_SLICES][20]: row r gathers from cloud r / rows_per_cloud and
+ * its query point belongs to cloud r / rows_per_cloud + clouds / 2; Qb = clouds / 2 * rows_per_cloud; a cloud with a non-finite sum
+ * makes the rows of both live) OR ssq = NULL: one extra launch then looks for non-finite values in the rows of X themselves.
+ * Qb % 32 == 0, Qb <= 65536, H % 4 == 0, KP % 4 == 0.                                                                          */
+typedef struct dpd_live_rows {
+    int Qb, KP, H;
+    int32_t* cnt;          /* {L, Lp, 0, 0}: device words, every reader clamps them to Qb */
+    int32_t* idx;          /* [Qb] original row of each compact position (pad positions: a valid row) */
+    int32_t* pos;          /* [Qb] compact position of each row, -1 = not live */
+    int32_t* rowflag;      /* [Qb] scratch of the ssq == NULL form */
+    float* g3c; float* h1c; float* h2c;   /* [Qb,H] */
+    float* Xc;             /* [Qb,KP] */
+    const float* X; int ldx;
+    const float* ssq; int clouds; int rows_per_cloud;
+} dpd_live_rows;
+size_t dpd_live_rows_bytes(int Qb, int KP, int H);
+int dpd_live_rows_carve(void* mem, size_t bytes, int Qb, int KP, int H, dpd_live_rows* out);
+int dpd_decoder_bwd_data_live(const float* dpred, const float* mask, const float* y, const float* h1, const float* h2,
+                              const float* h3, int Qb, int KP, int H, const dpd_decoder_params* p, int dtype,
+                              float* dy, float* g3, float* g2, float* g1, float* dX, const dpd_small_grads* sg,
+                              void* ws, size_t ws_bytes, const dpd_planes* pl, int phases, const dpd_live_rows* live, void* stream);
+int dpd_decoder_bwd_weights_live(int layer, const float* act, int lda, const float* g, int Qb, int Kin, int Nout,
+                                 int dtype, float* dW, float* db, void* ws, size_t ws_bytes, const dpd_planes* pl,
+                                 const float* db_partials, const dpd_live_rows* live, void* stream);
+int dpd_decoder_bwd_weights_pair_live(const float* actA, const float* gA, float* dWA, const float* actB, const float* gB,
+                                      float* dWB, int lda, int Qb, int Kin, int Nout, int dtype, void* ws, size_t ws_bytes,
+                                      const dpd_planes* pl, float* dbA, const float* db_partials, const dpd_live_rows* live,
+                                      void* stream);
+
 /* Scratch needed by the decoder entry points for the given sizes and compute type (split-K slabs, column-sum
  * partials and, for dtype != DPD_F32, the bf16 operand planes of one GEMM at a time).                   */
 size_t dpd_workspace_bytes(int Q, int KP, int H, int dtype);
@@ -834,7 +883,8 @@ int dpd_gemm_planes(int np, int a_fmt, int b_fmt, int M, int N, int K, const voi
 
 /* Tuning knob (process-wide, never needed for correctness): GEMM tile / split-K per
  * call site.  op: 0 fwd layer 1, 1 fwd layers 2-3, 2 bwd dH, 3 bwd dX, 4 bwd dW1, 5 bwd dW2/3, 6 / 7 bwd dH / dX with a
- * transposed weight copy, 8 layer 1 of dpd_decoder_fwd_unique (tile 32 or 33 only); 16 + op: one-plane (bf16) tile of gemm_x3.hip for that call site (0 = automatic; 1-5 ring kernels, 13 =
+ * transposed weight copy, 8 layer 1 of dpd_decoder_fwd_unique (tile 32 or 33 only), 9 / 10 / 11 the live-row dH / dW1 / dW2+dW3
+ * of the `_live` entries (tile 32 or 33 only: same bits, default 33); 16 + op: one-plane (bf16) tile of gemm_x3.hip for that call site (0 = automatic; 1-5 ring kernels, 13 =
  * 192x128 at BK 64, 21 / 23 / 24 phase-staggered), 32: its grouped dW2/dW3 launch, 33: the grouped dW1/dW2/dW3 launch of
  * dpd_decoder_bwd_weights_trio.  tile as in dpd_gemm_f32 (0 = auto); split_k applies to ops 4, 5 and, for the plane weight gradients
  * (ops 20, 21, 32, 33): n > 1 = n K slices per tile reduced inside the launch (last-arriving slice, slice order: deterministic),
@@ -854,6 +904,10 @@ int dpd_decoder_bwd_weights_trio(int Qb, int KP, int H, int dtype, float* dW1, f
  * by a hipEvent pair on its own stream.  dpd_prof_collect waits for them and returns the launch count and the
  * summed durations [ms] / flops (2*M*N*K as launched) since dpd_prof_enable(1).                              */
 int dpd_prof_enable(int on);
+/* the mode the profiler is in (0 = off).  A live-row launch (dpd_live_rows) has no shape the host knows, so its bracket would carry the
+ * DENSE 2*M*N*K against a shorter duration and the quotient would no longer be a rate: a caller that wants achieved rates checks this and
+ * runs the dense entries while the profiler is on (DPDistTrainer.backward does).                                           */
+int dpd_prof_enabled(void);
 int dpd_prof_collect(double* total_ms, double* total_flops);
 /* the same for ONE product form: 0 = NN / NT (forward layers and data gradients -- in DPD_F32 one kernel, the step's dominant one),
  * 1 = TN (weight gradients)                                                                                               */
