@@ -35,8 +35,9 @@ static int g_x3_trio_tile = 0, g_x3_trio_split = 1;   // plane dW1+dW2+dW3 in on
 static int g_l1u_tile = 33;   // layer 1 over distinct windows (dpd_decoder_fwd_unique): 32 or 33 (dpd_set_gemm_plan op 8)
 // live-row backward (dpd_live_rows): dH over the live rows, dW1, dW2 + dW3 over the live contraction length: 32 or 33 (dpd_set_gemm_plan
 // ops 9, 10, 11).  The short dH wants the 32x32 wave tile: a wave's K loop is as long as the dense one's, only the tiles get fewer
-enum { LIVE_DH = 0, LIVE_DW1 = 1, LIVE_DW23 = 2 };
-static int g_live_tile[3] = {33, 33, 33};
+// (op 12: the dW part of a pair launch, dpd_decoder_bwd_pair_live; its dH part takes op 9's)
+enum { LIVE_DH = 0, LIVE_DW1 = 1, LIVE_DW23 = 2, LIVE_PAIR_DW = 3 };
+static int g_live_tile[4] = {33, 33, 33, 33};
 constexpr size_t kRedCntBytes = 8192;                 // arrival words of the in-launch reduction: the last 8 KiB of the base workspace
 
 // Compute type of the three wide layers (the `dtype` argument of the decoder entry points):
@@ -1336,7 +1337,7 @@ extern "C" int dpd_set_gemm_plan(int op, int tile, int split_k) {
         dpd::g_l1u_tile = tile;
         return 0;
     }
-    if (op >= 9 && op <= 11) {      // live-row backward: dH, dW1, dW2 + dW3 (same bits on either tile)
+    if (op >= 9 && op <= 12) {      // live-row backward: dH, dW1, dW2 + dW3, the dW part of a pair launch (same bits on either tile)
         if (tile != 32 && tile != 33) return DPD_E_DIM;
         dpd::g_live_tile[op - 9] = tile;
         return 0;
@@ -2082,6 +2083,69 @@ extern "C" int dpd_decoder_bwd_weights_pair_live(const float* actA, const float*
     f.transA = 1; f.M = Kin; f.N = Nout; f.K = Qb;
     f.A = actA; f.lda = lda; f.B = gA; f.ldb = Nout; f.C = dWA; f.ldc = Nout;
     f.tile = tile; f.s = (hipStream_t)stream; f.A2 = actB; f.B2 = gB; f.C2 = dWB; f.cs2 = dbA ? &cs : nullptr;
+    return gemm_f32(f);
+}
+
+// One live dH product beside the weight gradient that does not wait for it (gemm_rs_pair_kernel).  The live dH launch alone is 160
+// workgroups for 256 CUs at the training shapes, each wave one dependent chain of H / 2 MFMAs: 40 % of the SIMDs idle and the rest
+// hold one wave whose load latency nothing hides.  The dW product of the layer ABOVE reads only what exists already (dW3 = h2c^T g3c
+// beside g3c -> g2; dW2 = h1c^T g2 beside g2 -> g1) and fills those SIMDs.  Every element comes from the same wave body over the same
+// operands in the same k order as in the separate launches: same bits.
+extern "C" int dpd_decoder_bwd_pair_live(int layer, const float* g_in, float* g_out, float* dW, int Qb, int H, const dpd_decoder_params* p,
+                                         const dpd_live_rows* live, void* stream) {
+    using namespace dpd;
+    if (!p || !live || !g_out || !dW || (layer == 2 && !g_in)) return DPD_E_NULL;
+    if ((layer != 2 && layer != 3) || Qb <= 0 || H <= 0) return DPD_E_DIM;
+    if (!p->W2T || !p->W3T) return DPD_E_UNSUPPORTED;
+    if (int rc = check_live(live, Qb, 0, H)) return rc;
+    const float* gin = layer == 3 ? live->g3c : g_in;
+    const float* act = layer == 3 ? live->h2c : live->h1c;      // the dH part's gate and the dW part's A operand
+    GemmF32Call a, b;
+    a.M = Qb; a.N = H; a.K = H;
+    a.A = gin; a.lda = H; a.B = layer == 3 ? p->W3T : p->W2T; a.ldb = H; a.C = g_out; a.ldc = H;
+    a.gate = act; a.epilogue = EPI_GATE; a.tile = g_live_tile[LIVE_DH]; a.s = (hipStream_t)stream; a.M_dev = live->cnt + 1;
+    b.transA = 1; b.M = H; b.N = H; b.K = Qb;
+    b.A = act; b.lda = H; b.B = gin; b.ldb = H; b.C = dW; b.ldc = H;
+    b.tile = g_live_tile[LIVE_PAIR_DW]; b.s = a.s; b.K_dev = live->cnt + 1;
+    a.pair = &b;
+    return gemm_f32(a);
+}
+
+extern "C" int dpd_decoder_bwd_chain_live(const float* dpred, const float* mask, const float* y, const float* h1, const float* h2,
+                                          const float* h3, int Qb, int KP, int H, const dpd_decoder_params* p, float* dy, float* g3,
+                                          float* g2, float* g1, const dpd_small_grads* sg, void* ws, size_t ws_bytes, int defer_small,
+                                          float* dW1, float* dW2, float* dW3, float* db1, float* db2, const dpd_live_rows* live,
+                                          void* stream) {
+    using namespace dpd;
+    if (!live || !dW1 || !dW2 || !dW3 || !g2 || !g1) return DPD_E_NULL;
+    if (sg && (sg->db1 || sg->db2)) return DPD_E_UNSUPPORTED;      // (the output-layer launch would zero them behind nobody's back)
+    float* dbp = sg ? sg->db_partials : nullptr;
+    if ((db1 || db2) && !dbp) return DPD_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    // 1. output layer, small gradients, compaction (every check of the shapes and of the descriptor happens in there)
+    if (int rc = dpd_decoder_bwd_data_live(dpred, mask, y, h1, h2, h3, Qb, KP, H, p, 0, dy, g3, g2, g1, nullptr, sg, ws, ws_bytes, nullptr,
+                                           1 | (defer_small ? 16 : 0), live, stream))
+        return rc;
+    // 2. / 3. the two pair launches
+    if (int rc = dpd_decoder_bwd_pair_live(3, nullptr, g2, dW3, Qb, H, p, live, stream)) return rc;
+    if (int rc = dpd_decoder_bwd_pair_live(2, g2, g1, dW2, Qb, H, p, live, stream)) return rc;
+    // 4. the partial sums of db2 (first half of the scratch) and db1 in the dense association
+    const int nb = Qb / 32;
+    if (dbp) {
+        LivePartArgs a{{db2 ? g2 : nullptr, db1 ? g1 : nullptr}, {dbp, dbp + (size_t)nb * H}, live->pos, live->cnt, Qb, H};
+        DPD_LAUNCH(live_db_partials_kernel, dim3(nb, (H + 255) / 256, 2), dim3(256), 0, s, a);
+        DPD_CHECK_LAUNCH();
+    }
+    // 5. dW1 = Xc^T g1 over the live contraction length; its first-row-block waves add up db1 and, behind it, db2 (in the five-launch form
+    // dW2's waves do that: the same sum over the same partials in the same block order)
+    ColsumTwoStep cs{};
+    cs.part_in = db1 ? dbp + (size_t)nb * H : nullptr; cs.out = db1;
+    cs.part_in2 = db2 ? dbp : nullptr; cs.out2 = db2;
+    cs.nparts = nb;
+    GemmF32Call f;
+    f.transA = 1; f.M = KP; f.N = H; f.K = Qb;
+    f.A = live->Xc; f.lda = KP; f.B = g1; f.ldb = H; f.C = dW1; f.ldc = H;
+    f.tile = g_live_tile[LIVE_DW1]; f.s = s; f.cs2 = (db1 || db2) ? &cs : nullptr; f.K_dev = live->cnt + 1;
     return gemm_f32(f);
 }
 

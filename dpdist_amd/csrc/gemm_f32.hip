@@ -481,7 +481,8 @@ static int launch_tile(int tile, const GemmArgs& g, hipStream_t s) {
     }
 }
 
-int gemm_f32(const GemmF32Call& c) {
+// every check of one call and its kernel arguments; tile / split_k: what the launch then uses
+static int f32_args(const GemmF32Call& c, GemmArgs& g_out, int& tile_out, int& split_out) {
     const int M = c.M, N = c.N, K = c.K;
     if (!c.A || !c.B || !c.C) return DPD_E_NULL;
     // split_k == 0: "tail split" (gemm_rs.h): whole-K tiles, only the partial last round of tiles is cut along K (needs ws for
@@ -510,6 +511,7 @@ int gemm_f32(const GemmF32Call& c) {
         g.colsum_part = c.cs2->part_out;
         g.colsum_part_in = c.cs2->part_in; g.colsum_part_in2 = c.cs2->part_in2;
         g.colsum_b = c.cs2->out; g.colsum_b2 = c.cs2->out2; g.colsum_nparts = c.cs2->nparts;
+        if (c.cs2->out2 && !c.A2 && !c.K_dev) return DPD_E_UNSUPPORTED;     // a second sum without a second problem: the K_dev form only
     }
     if (c.A2 && (!c.B2 || !c.C2 || split_k > 1 || c.epilogue != EPI_NONE || c.colsum)) return DPD_E_UNSUPPORTED;
     if (c.A2 && !whole_tiles) return DPD_E_UNSUPPORTED;   // grouped launches exist for the DMA / register-streamed kernels only
@@ -528,6 +530,33 @@ int gemm_f32(const GemmF32Call& c) {
     } else {
         g.k_chunk = (K + 31) / 32 * 32; g.C = c.C; g.ldc = c.ldc; g.slab_stride = 0; g.epi = c.epilogue;
     }
+    g_out = g; tile_out = tile; split_out = split_k;
+    return 0;
+}
+
+// c and *c.pair in one launch (GemmF32Call::pair): both parts are checked as calls of their own first, then for the pair form
+static int gemm_f32_pair(const GemmF32Call& c) {
+    const GemmF32Call& d = *c.pair;
+    if (d.pair) return DPD_E_UNSUPPORTED;
+    GemmArgs ga, gb;
+    int ta, tb, sa, sb;
+    if (int rc = f32_args(c, ga, ta, sa)) return rc;
+    if (int rc = f32_args(d, gb, tb, sb)) return rc;
+    const auto tile_ok = [](int t) { return t == 32 || t == 33; };
+    if (!c.split_k || !d.split_k || sa != 1 || sb != 1 || ga.tail_split || gb.tail_split || !tile_ok(ta) || !tile_ok(tb)) return DPD_E_UNSUPPORTED;
+    if (c.transA || c.transB || !c.M_dev || c.K_dev || c.epilogue != EPI_GATE || c.A2 || c.colsum || c.cs2) return DPD_E_UNSUPPORTED;
+    if (!d.transA || d.transB || !d.K_dev || d.M_dev || d.epilogue != EPI_NONE || d.A2 || d.colsum || (d.cs2 && d.cs2->out2) || d.K < 32 || d.s != c.s) return DPD_E_UNSUPPORTED;
+    // one bracket, the flops of both parts (at the capacities: see dpd_prof_enabled); it counts with the NN / NT launches
+    ProfScope prof_scope{prof_begin(c.s), c.s, 2.0 * c.M * c.N * c.K + 2.0 * d.M * d.N * d.K, 0};
+    return launch_rs_pair(ta, tb, ga, gb, c.s);
+}
+
+int gemm_f32(const GemmF32Call& c) {
+    if (c.pair) return gemm_f32_pair(c);
+    const int M = c.M, N = c.N, K = c.K;
+    GemmArgs g;
+    int tile, split_k;
+    if (int rc = f32_args(c, g, tile, split_k)) return rc;
     // profiler bracket: the GEMM kernel AND, with split-K, its reduce kernel (both belong to this GEMM)
     ProfScope prof_scope{prof_begin(c.s), c.s, 2.0 * M * N * K, c.transA ? 1 : 0};
     int rc;
@@ -602,4 +631,23 @@ extern "C" int dpd_gemm_f32(int transA, int transB, int M, int N, int K, const f
     c.bias = bias; c.gate = gate; c.epilogue = epilogue; c.split_k = split_k; c.tile = tile;
     c.ws = ws; c.ws_bytes = ws_bytes; c.s = (hipStream_t)stream;
     return dpd::gemm_f32(c);
+}
+
+extern "C" int dpd_gemm_f32_pair(const dpd_gemm_pair_part* a, const dpd_gemm_pair_part* b, void* stream) {
+    if (!a || !b) return DPD_E_NULL;
+    dpd::GemmF32Call c[2];
+    dpd::ColsumTwoStep cs{};
+    const dpd_gemm_pair_part* p[2] = {a, b};
+    for (int i = 0; i < 2; ++i) {
+        c[i].transA = p[i]->transA; c[i].transB = p[i]->transB; c[i].M = p[i]->M; c[i].N = p[i]->N; c[i].K = p[i]->K;
+        c[i].A = p[i]->A; c[i].lda = p[i]->lda; c[i].B = p[i]->B; c[i].ldb = p[i]->ldb; c[i].C = p[i]->C; c[i].ldc = p[i]->ldc;
+        c[i].gate = p[i]->gate; c[i].epilogue = p[i]->epilogue; c[i].split_k = p[i]->split_k; c[i].tile = p[i]->tile;
+        c[i].M_dev = p[i]->M_dev; c[i].K_dev = p[i]->K_dev; c[i].s = (hipStream_t)stream;
+    }
+    if (b->bias_out) {      // second step of a bias gradient in the TN part's first-row-block waves
+        cs.part_in = b->bias_parts; cs.out = b->bias_out; cs.nparts = b->bias_nparts;
+        c[1].cs2 = &cs;
+    }
+    c[0].pair = &c[1];
+    return dpd::gemm_f32(c[0]);
 }

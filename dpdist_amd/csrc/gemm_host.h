@@ -35,6 +35,10 @@ struct GemmF32Call {
     const ColsumTwoStep* cs2 = nullptr;   // two-step bias gradient (register-streamed kernels)
     const int* M_dev = nullptr;           // GemmArgs::M_dev (TN or NN, tiles 32 / 33, no split): M is then the capacity
     const int* K_dev = nullptr;           // GemmArgs::K_dev (TN, tiles 32 / 33, no split, single or grouped): K is then the capacity
+    // A second, independent problem in the SAME launch (gemm_rs_pair_kernel): this call is then the NN product with M_dev and the gate
+    // epilogue (a live-row dH), *pair a TN product with K_dev, no epilogue, at most the second step of a bias gradient (a live-row dW):
+    // tiles 32 / 33 each, split_k == 1, not grouped, K >= 32 for the TN part, the same stream; anything else: DPD_E_UNSUPPORTED
+    const GemmF32Call* pair = nullptr;
 };
 int gemm_f32(const GemmF32Call& c);
 

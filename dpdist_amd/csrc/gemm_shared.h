@@ -26,7 +26,8 @@ struct GemmArgs {
     float* colsum;    // optional [N]: += column sums of the stored values (atomics; caller zeroes it)
     // deterministic bias gradients without atomics or an extra launch: a GEMM whose rows are data rows stores, per 32-row block,
     // the column sums of what it writes (colsum_part [ceil(M/32)][N]); a LATER GEMM's first-row-block waves add those partials
-    // in a fixed order into colsum_b [N] (reading colsum_part_in, nparts blocks; *_2: the grouped second problem)
+    // in a fixed order into colsum_b [N] (reading colsum_part_in, nparts blocks; *_2: the grouped second problem or, in a launch that is
+    // not grouped (K_dev form only), a second sum of the same N columns that the same waves finish)
     float* colsum_part;
     const float* colsum_part_in;
     const float* colsum_part_in2;

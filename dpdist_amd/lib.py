@@ -61,6 +61,13 @@ class LiveRows(Structure):     # include/dpdist_capi.h: dpd_live_rows (carved by
                                                                                                        ("clouds", c_int), ("rows_per_cloud", c_int)])
 
 
+class GemmPairPart(Structure):     # include/dpdist_capi.h: dpd_gemm_pair_part (one of the two problems of dpd_gemm_f32_pair)
+    _fields_ = ([(n, c_int) for n in ("transA", "transB", "M", "N", "K")] +
+                [("A", c_void_p), ("lda", c_int), ("B", c_void_p), ("ldb", c_int), ("C", c_void_p), ("ldc", c_int), ("gate", c_void_p)] +
+                [(n, c_int) for n in ("epilogue", "split_k", "tile")] +
+                [("M_dev", c_void_p), ("K_dev", c_void_p), ("bias_parts", c_void_p), ("bias_out", c_void_p), ("bias_nparts", c_int)])
+
+
 # name -> (restype, argtypes); mirrors include/dpdist_capi.h one to one
 SIGNATURES = {
     "dpd_version": (c_char_p, []),
@@ -131,6 +138,9 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_size_t, POINTER(Planes), c_void_p, POINTER(LiveRows), c_void_p]),
     "dpd_decoder_bwd_weights_pair_live": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_size_t, POINTER(Planes), c_void_p, c_void_p,
                                                                                  POINTER(LiveRows), c_void_p]),
+    "dpd_decoder_bwd_pair_live": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(DecoderParams), POINTER(LiveRows), c_void_p]),
+    "dpd_decoder_bwd_chain_live": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, POINTER(DecoderParams)] + [c_void_p] * 4 +
+                                           [POINTER(SmallGrads), c_void_p, c_size_t, c_int] + [c_void_p] * 5 + [POINTER(LiveRows), c_void_p]),
     "dpd_decoder_bwd_weights_trio": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(Planes), c_void_p]),
     "dpd_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t, ctypes.c_uint32]),
     "dpd_chamfer_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
@@ -181,6 +191,7 @@ SIGNATURES = {
     "dpd_adam_tf_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float, c_float, c_float, c_void_p]),
     "dpd_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                              c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "dpd_gemm_f32_pair": (c_int, [POINTER(GemmPairPart), POINTER(GemmPairPart), c_void_p]),
     "dpd_set_gemm_plan": (c_int, [c_int, c_int, c_int]),
     "dpd_prof_enable": (c_int, [c_int]),
     "dpd_prof_enabled": (c_int, []),

@@ -94,6 +94,7 @@ class DPDistTrainer:
         "dp_buckets": 2,       # data-parallel "early" order: 2 = layers 2-4 as one collective, 3 = one per layer
         "unique_l1": None,     # exact fp32: layer 1 once per distinct (cloud, voxel) window, same bits (None: on where the shapes allow it)
         "live_rows": None,     # exact fp32: dH / dW GEMMs over the rows whose dy is not zero, same values (None: on where the shapes allow it)
+        "live_pair": None,     # ... single GPU: each live dH GEMM and a ready dW GEMM in one launch, same bits (None: on where live_rows is)
     }
 
     def __init__(self, params: DPDistParams, batch_size, num_point=64, Embedding_Size=512, sigma3dmfv=0.125, base_lr=1e-4,
@@ -149,6 +150,10 @@ class DPDistTrainer:
         # compaction with phase 1 and the partial sums of db2 / db1 with the dH product of their layer
         self.live_rows = bool((opt["live_rows"] is None or opt["live_rows"]) and self.dt == 0 and BN % 32 == 0 and BN <= 65536
                               and self.fuse_loss and self._det_db)
+        # `dpd_decoder_bwd_chain_live`: the plain single-GPU order of the live-row backward with each dH product and the weight gradient that
+        # is ready beside it in ONE launch (14 launches per step instead of 15).  The data-parallel orders need dW3 / dW2 early for their
+        # buckets and keep the separate entries; off = the five-launch form (A/B runs, tests)
+        self.live_pair = bool((opt["live_pair"] is None or opt["live_pair"]) and self.live_rows)
         # -- allocations: this ORDER decides the addresses (the plane memory follows the workspace) --
         self._alloc_buffers()
         self._alloc_planes(keep_f32_h=opt["keep_f32_h"])
@@ -460,6 +465,16 @@ class DPDistTrainer:
             L.check(rc, "dpd_decoder_bwd_weights_trio")
             return True
 
+        if live is not None and self.live_pair and not self.reducer and x_free is None:
+            # the plain order of `backward_schedule` -- ("data", 7 [| 16]), ("dw", 1), ("dw23",) -- as ONE library call that pairs the
+            # launches: output layer + compaction, {g2 | dW3}, {g1 | dW2}, the partial sums, dW1 (which finishes db1 and db2).  dW1, the
+            # last reader of X / mask, is the LAST launch here: a step with the prefetch pipeline (x_free given) wants it early, so that the
+            # next front end runs beside dW2 + dW3 and the optimizer, and keeps the schedule below
+            L.check(lib.dpd_decoder_bwd_chain_live(L.ptr(self.dpred), L.ptr(self.mask), L.ptr(self.y), L.ptr(self.h1), L.ptr(self.h2), L.ptr(h3),
+                                                   BN, P.KP, P.H, self._cparams, L.ptr(self.dy), L.ptr(self.g3), L.ptr(self.g2), L.ptr(self.g1),
+                                                   small, L.ptr(self.ws), wsb, 1 if defer_small else 0, L.ptr(gv[0]), L.ptr(gv[2]), L.ptr(gv[4]),
+                                                   L.ptr(gv[1]), L.ptr(gv[3]), live, L.cur_stream()), "dpd_decoder_bwd_chain_live")
+            return
         todo = iter(backward_schedule(bool(self.reducer), self.dp_schedule, self._trio, self._dp_buckets == 3, bool(defer_small), len(P.bucket_bounds) - 2))
         while (step := next(todo, None)) is not None:
             op = step[0]

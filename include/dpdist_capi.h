@@ -541,6 +541,25 @@ int dpd_decoder_bwd_weights_pair_live(const float* actA, const float* gA, float*
                                       float* dWB, int lda, int Qb, int Kin, int Nout, int dtype, void* ws, size_t ws_bytes,
                                       const dpd_planes* pl, float* dbA, const float* db_partials, const dpd_live_rows* live,
                                       void* stream);
+/* A live dH product and the weight gradient that does not need its result, in ONE launch (dpd_gemm_f32_pair), behind the compaction:
+ *   layer 3:  g_out (compact g2) = (g3c W3T) * [h2c > 0]   beside   dW (dW3) = h2c^T g3c;   g_in is not read
+ *   layer 2:  g_out (compact g1) = (g_in W2T) * [h1c > 0]  beside   dW (dW2) = h1c^T g_in;  g_in = the compact g2
+ * Same bits as phase 2 / 4 of dpd_decoder_bwd_data_live and dpd_decoder_bwd_weights_live(layer) without a bias gradient.  Tiles:
+ * dpd_set_gemm_plan ops 9 (dH part) and 12 (dW part).                                                                             */
+int dpd_decoder_bwd_pair_live(int layer, const float* g_in, float* g_out, float* dW, int Qb, int H, const dpd_decoder_params* p,
+                              const dpd_live_rows* live, void* stream);
+/* The whole exact-fp32 backward of a single-GPU step on the live rows, in the order that keeps every SIMD busy:
+ *   1. output layer (+ loss, + small-gradient reduction) and the compaction: phase 1 of dpd_decoder_bwd_data_live, unchanged
+ *   2. { dH -> g2 | dW3 }   3. { dH -> g1 | dW2 }     one launch each (dpd_decoder_bwd_pair_live)
+ *   4. the 32-row partial sums of db2 / db1, one launch (sg->db_partials given)
+ *   5. dW1; its first-row-block waves finish db1 AND db2 (the partials of db2 exist only behind step 4; same block-order sums)
+ * One launch less than data (phases 7) + weights(1) + weights_pair, and every gradient -- g2, g1 (compact rows), dW1..dW3, db1, db2 and
+ * what phase 1 writes -- has the bits of that sequence.  Arguments as in dpd_decoder_bwd_data_live (dtype DPD_F32, no dX, no planes);
+ * `defer_small` != 0 = its phase 16.  sg->db1 / sg->db2 must be NULL (phase 1 would zero them); db1 / db2 here need sg->db_partials. */
+int dpd_decoder_bwd_chain_live(const float* dpred, const float* mask, const float* y, const float* h1, const float* h2,
+                               const float* h3, int Qb, int KP, int H, const dpd_decoder_params* p, float* dy, float* g3, float* g2,
+                               float* g1, const dpd_small_grads* sg, void* ws, size_t ws_bytes, int defer_small, float* dW1,
+                               float* dW2, float* dW3, float* db1, float* db2, const dpd_live_rows* live, void* stream);
 
 /* Scratch needed by the decoder entry points for the given sizes and compute type (split-K slabs, column-sum
  * partials and, for dtype != DPD_F32, the bf16 operand planes of one GEMM at a time).                   */
@@ -856,6 +875,30 @@ int dpd_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, in
                  float* Cout, int ldc, const float* bias, const float* gate, int epilogue, int split_k, int tile,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* Two independent exact-fp32 products in ONE launch of the register-streamed kernels (csrc/gemm_rs.h: gemm_rs_pair_kernel): the
+ * workgroups of part a come first, those of part b behind them; no workgroup waits for another.  The fields mean what the arguments
+ * of dpd_gemm_f32 mean.  The pair form takes exactly:
+ *   a  NN (transA = transB = 0), M_dev set (the live row count, a device word <= M; M is the capacity the grid is launched for; rows
+ *      from the count on are not written), epilogue 3 with `gate` (row stride ldc);
+ *   b  TN (transA = 1: A stored [K,M]), K_dev set (the live contraction length, a device word clamped to [0, K] and rounded down to
+ *      32; 0 stores zeros), epilogue 0, K >= 32 and K % 32 == 0; bias_out (may be NULL): [N] = the sum over bias_nparts blocks of
+ *      bias_parts [bias_nparts][N], in block order, by the part's first-row-block waves;
+ *   both: tile 32 or 33 (same bits), split_k = 1.
+ * Every element has the bits the part's own dpd_gemm_f32-style launch gives.  Refusals, before anything is launched: DPD_E_NULL for a
+ * NULL part or operand, DPD_E_UNSUPPORTED for any other form (split-K, the tail split, another tile, K < 32 in part b, ...).          */
+typedef struct dpd_gemm_pair_part {
+    int transA, transB, M, N, K;
+    const float* A; int lda;
+    const float* B; int ldb;
+    float* C; int ldc;
+    const float* gate;
+    int epilogue, split_k, tile;
+    const int32_t* M_dev;
+    const int32_t* K_dev;
+    const float* bias_parts; float* bias_out; int bias_nparts;
+} dpd_gemm_pair_part;
+int dpd_gemm_f32_pair(const dpd_gemm_pair_part* a, const dpd_gemm_pair_part* b, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * bf16-plane building blocks (gemm_x3.hip).  A plane tensor holds np (1 or 3) bf16 planes of an fp32 matrix in
  * 16-byte chunks of 8 contraction elements:
@@ -884,7 +927,7 @@ int dpd_gemm_planes(int np, int a_fmt, int b_fmt, int M, int N, int K, const voi
 /* Tuning knob (process-wide, never needed for correctness): GEMM tile / split-K per
  * call site.  op: 0 fwd layer 1, 1 fwd layers 2-3, 2 bwd dH, 3 bwd dX, 4 bwd dW1, 5 bwd dW2/3, 6 / 7 bwd dH / dX with a
  * transposed weight copy, 8 layer 1 of dpd_decoder_fwd_unique (tile 32 or 33 only), 9 / 10 / 11 the live-row dH / dW1 / dW2+dW3
- * of the `_live` entries (tile 32 or 33 only: same bits, default 33); 16 + op: one-plane (bf16) tile of gemm_x3.hip for that call site (0 = automatic; 1-5 ring kernels, 13 =
+ * of the `_live` entries and 12 the dW part of dpd_decoder_bwd_pair_live (tile 32 or 33 only: same bits, default 33; 13-15 are free); 16 + op: one-plane (bf16) tile of gemm_x3.hip for that call site (0 = automatic; 1-5 ring kernels, 13 =
  * 192x128 at BK 64, 21 / 23 / 24 phase-staggered), 32: its grouped dW2/dW3 launch, 33: the grouped dW1/dW2/dW3 launch of
  * dpd_decoder_bwd_weights_trio.  tile as in dpd_gemm_f32 (0 = auto); split_k applies to ops 4, 5 and, for the plane weight gradients
  * (ops 20, 21, 32, 33): n > 1 = n K slices per tile reduced inside the launch (last-arriving slice, slice order: deterministic),

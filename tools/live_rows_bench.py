@@ -6,7 +6,9 @@ alternating, on two inputs --
                when there is nothing to leave out.
 Each line: input, form, ms per step (host clock around `steps` steps that end in a synchronise) and the live count {L, Lp} read back
 AFTER the timed window (the step itself never reads it).
-    python tools/live_rows_bench.py [--batch 32] [--steps 200] [--warmup 220] [--reps 3]"""
+--pair alternates the option `live_pair` instead (live rows on in both forms): the five-launch live backward against the one whose dH
+products share a launch with a weight gradient; on all_live the dH part of a pair has all its workgroups.
+    python tools/live_rows_bench.py [--batch 32] [--steps 200] [--warmup 220] [--reps 3] [--pair]"""
 import argparse
 import os
 import sys
@@ -21,7 +23,7 @@ from dpdist_amd.model import DPDistParams                 # noqa: E402
 from dpdist_amd.trainer import DPDistTrainer              # noqa: E402
 
 
-def run(dev, B, N, kind, on, steps, warmup, batch):
+def run(dev, B, N, kind, on, steps, warmup, batch, pair=False):
     P = DPDistParams(k=5, mlp=(1024, 1024, 1024), device=dev, compute_dtype="f32")
     P.reset_parameters_tf(generator=torch.Generator().manual_seed(1234))
     lr = 1e-4
@@ -29,8 +31,8 @@ def run(dev, B, N, kind, on, steps, warmup, batch):
         P.view("b4").add_(3.0)
         lr = 1e-7
     tr = DPDistTrainer(P, B, num_point=N, Embedding_Size=512, sigma3dmfv=0.125, base_lr=lr, distributed=False,
-                       options={"live_rows": None if on else False})
-    assert tr.live_rows == on
+                       options={"live_pair": on} if pair else {"live_rows": None if on else False})
+    assert (tr.live_pair if pair else tr.live_rows) == on
     for _ in range(warmup):
         tr.step(*batch)
     torch.cuda.synchronize()
@@ -39,7 +41,7 @@ def run(dev, B, N, kind, on, steps, warmup, batch):
         tr.step(*batch)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / steps * 1e3
-    count = tr.live_count.cpu().tolist() if on else None
+    count = tr.live_count.cpu().tolist() if (on or pair) else None
     return ms, count, float(tr.loss.cpu()[0])
 
 
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=220)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--pair", action="store_true", help="alternate live_pair (live rows on) instead of live_rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("live_rows_bench needs a GPU")
@@ -58,9 +61,9 @@ def main():
     for kind in ("bench", "all_live"):
         for rep in range(a.reps):
             for on in (False, True):
-                ms, count, loss = run(dev, B, N, kind, on, a.steps, a.warmup, batch)
-                print("%-9s live_rows=%-5s rep %d  %.4f ms/step  live {L, Lp} = %s of %d  loss_samples %.6f"
-                      % (kind, on, rep, ms, count, B * N, loss), flush=True)
+                ms, count, loss = run(dev, B, N, kind, on, a.steps, a.warmup, batch, a.pair)
+                print("%-9s %s=%-5s rep %d  %.4f ms/step  live {L, Lp} = %s of %d  loss_samples %.6f"
+                      % (kind, "live_pair" if a.pair else "live_rows", on, rep, ms, count, B * N, loss), flush=True)
 
 
 if __name__ == "__main__":
