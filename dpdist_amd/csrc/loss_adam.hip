@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(float* __restrict__ p, 
     }
     b -= f.tile_end[2];
     if (b < f.ntail) {
-        // = small_grads_reduce (decoder.hip) followed by Adam on the 16 elements of this block
+        // = small_grads_reduce (decoder_out.hip) followed by Adam on the 16 elements of this block
         float (*red)[17] = reinterpret_cast<float (*)[17]>(&tile[0][0]);
         float* s_loss = &tile[8][0];
         const int li = tid & 15, sl = tid >> 4, H = f.H;

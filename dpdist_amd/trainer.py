@@ -118,7 +118,7 @@ class DPDistTrainer:
         # -- shape rules, each stated once; the library applies the same ones and answers a mismatch with an error, not a fallback --
         # clouds; decoder rows of the forward (both directions); rows that carry gradient (the AB half)
         self.C, self.Q, self.BN = C, Q, BN = 2 * B, 2 * B * N, B * N
-        # `fused4` in decoder.hip (dpd_decoder_bwd_data): the output-layer backward that can also take the loss, the layer's forward and g3 as planes
+        # `fused4` in decoder_out.hip (out_layer_bwd, the output-layer step of dpd_decoder_bwd_data): the output-layer backward that can also take the loss, the layer's forward and g3 as planes
         self._fused4 = H % 256 == 0 and H <= 1024
         # `kOBRows` = 8 rows per block of that kernel, one record of 4 H + kOBRec floats per block (its older form's 4 H + 4 fits too)
         self._nparts, self._rec = (BN + 7) // 8, 4 * H + 8
@@ -127,7 +127,7 @@ class DPDistTrainer:
         # `adam_tf_fused` reduces the block partials into [b3 | W4 | b4] only where those END the flat buffer (up to 3 elements of
         # alignment padding behind them) and the records are `fused4`'s
         self._tail_ok = 0 <= params.numel - (params._segments["b3"][0] + 4 * H + 3) <= 3 and self._fused4
-        # `free_db` in decoder.hip (dpd_decoder_bwd_weights): exact fp32, whole 32-row groups -- db1 / db2 as by-products of the dW GEMMs
+        # `free_db` in decoder_bwd.hip (dpd_decoder_bwd_weights): exact fp32, whole 32-row groups -- db1 / db2 as by-products of the dW GEMMs
         # (column sums of the operand they stream: deterministic); the plane compute types keep the fused-epilogue atomics of the data chain
         self._det_db = self.dt == 0 and BN % 32 == 0 and bool(opt["det_db"])
         # -- stage forms --
@@ -145,7 +145,7 @@ class DPDistTrainer:
         # plain gather and layer 1 (orthogonal to every other option: the activations have the same bits either way)
         self.unique_l1 = bool((opt["unique_l1"] is None or opt["unique_l1"]) and self.dt == 0 and N % 8 == 0 and N <= 1024 and Q % 32 == 0
                               and self.k >= 3 and KP == L.load().dpd_padded_width(self.k) and KP >= 64 and H % 64 == 0 and self.m <= 10)
-        # `live` in decoder.hip (the `_live` twins of the three backward entries): exact fp32, whole 32-row groups, dy out of the fused
+        # `live` in decoder_bwd.hip (the `_live` twins of the three backward entries; their live form is decoder_live.hip): exact fp32, whole 32-row groups, dy out of the fused
         # output-layer backward and the two-step bias gradients.  Every order of `backward_schedule` takes it as it is: the entries run the
         # compaction with phase 1 and the partial sums of db2 / db1 with the dH product of their layer
         self.live_rows = bool((opt["live_rows"] is None or opt["live_rows"]) and self.dt == 0 and BN % 32 == 0 and BN <= 65536
@@ -243,7 +243,7 @@ class DPDistTrainer:
             self.h1, self.h2 = f(Q, H), f(Q, H)
             # live rows: g1 / g2 hold the COMPACT rows (the first Lp); zeroed once so that every element is defined
             self.g1, self.g2 = (torch.zeros(BN, H, device=self.P.flat.device) for _ in range(2)) if self.live_rows else (f(BN, H), f(BN, H))
-        # g3: the fused output-layer backward writes it as planes when it can (`fused4`, block partials fit: `fused` in decoder.hip).
+        # g3: the fused output-layer backward writes it as planes when it can (`fused4`, block partials fit: `fused` in decoder_out.hip).
         # BN // 8 is not rounded up like _nparts: the test is only reached with planes, i.e. BN % 32 == 0, where the two are equal
         if self.g1 is not None or not (self._fused4 and (BN // 8) * self._rec <= BN * H):
             self.g3 = f(BN, H)
