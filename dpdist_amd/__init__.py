@@ -22,4 +22,7 @@ def __getattr__(name):
     if name in ("dpdist_pairs", "DPDistPairs"):
         from . import pairs
         return getattr(pairs, name)
+    if name in ("chamfer_matrix", "hausdorff_matrix", "ChamferMatrix"):
+        from . import baselines
+        return getattr(baselines, name)
     raise AttributeError(name)

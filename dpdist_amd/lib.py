@@ -145,6 +145,9 @@ SIGNATURES = {
     "dpd_crc32c": (ctypes.c_uint32, [c_void_p, c_size_t, ctypes.c_uint32]),
     "dpd_chamfer_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
     "dpd_chamfer_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    # all-pairs Chamfer / Hausdorff (dpdist_amd/baselines.py): S, countsS, Cs, Ns, Q, countsQ, Cq, Nq, ...
+    "dpd_chamfer_matrix_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4),
+    "dpd_chamfer_matrix_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     "dpd_nn_dist": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dpd_emd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dpd_emd_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 6 + [c_size_t, c_void_p]),

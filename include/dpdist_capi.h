@@ -650,6 +650,32 @@ int dpd_chamfer_bwd(const float* a, const float* b, int B, int N, int M, const i
                     float gscale, float* da, float* db, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * All-pairs Chamfer and Hausdorff: the baseline distance matrices of two SETS of clouds (dpdist_amd/baselines.py), one DIRECTED matrix
+ * per call; the caller runs each direction with the sets swapped, as for the all-pairs DPDist.  S [Cs,Ns,3]: the "surface" clouds,
+ * Q [Cq,Nq,3]: the "query" clouds; countsS / countsQ: per-cloud counts (int32, DEVICE memory, the rules of the RAGGED block: never read
+ * by the host, clamped into [1, width] by the kernels, the padding is never read); NULL = the set is full.  With ns_i, nq_j the counts,
+ *   d2(q, s)  = (dx*dx + dy*dy) + dz*dz, d? = q? - s?, fp32 and not fused (chamfer_pair_sq of csrc/chamfer_scan.h)
+ *   mn(i,j,n) = min_{p < ns_i} d2(Q[j,n], S[i,p]),  arg(i,j,n) = the lowest p that attains it
+ *   mean_sq[i,j] = (1 / nq_j) sum_{n < nq_j} mn          mean_rt[i,j] = (1 / nq_j) sum_{n < nq_j} sqrtf(mn)
+ *   max_sq[i,j]  = max_{n < nq_j} mn                      (each [Cs,Cq] and optional; at least one, else DPD_E_NULL)
+ * dpd_chamfer_matrix_bwd: W [Cs,Cq] = the upstream of the directed mean of `form` (0: mean_sq, 1: mean_rt; else DPD_E_DIM),
+ *   dQ[j,n] =   sum_i W[i,j] / nq_j * t(Q[j,n], S[i, arg(i,j,n)])                                   (i ascending)
+ *   dS[i,p] = - sum_j W[i,j] / nq_j * sum_{n : arg(i,j,n) = p} t(Q[j,n], S[i,p])                    (j, then n ascending)
+ *   t(q, s) = 2 (q - s) for form 0; (q - s) / |q - s| for form 1, with the hardware reciprocal square root of d2 and exactly 0 where
+ *   the minimum is 0 (the deviation of dpd_chamfer_sqrt_bwd).  The argmins are recomputed, nothing of size [Cs,Cq,N] is stored.  dS
+ *   [Cs,Ns,3] and dQ [Cq,Nq,3] are overwritten, either may be NULL (both: DPD_E_NULL); rows at or beyond a cloud's count are +0.0.
+ * Every sum has one fixed order that depends on the pair's two counts only, and there are no atomics: two calls give the same bits, and
+ * a pair's forward values are bit for bit those of the entry on that pair alone (Cs = Cq = 1, widths cut to the counts) -- the padded
+ * widths, the padding and the other clouds change no bit.  No workspace, no allocation, stream-ordered.
+ * Refusals, before anything is launched and with the outputs untouched: DPD_E_NULL for a missing S, Q, W or output; DPD_E_DIM for
+ * Cs < 1, Cq < 1 or Cs * Cq >= 2^31; DPD_E_UNSUPPORTED unless 1 <= Ns, Nq <= 4096 (the surface cloud lives in LDS).  The number of
+ * clouds is not bound by a grid dimension.                                                                                            */
+int dpd_chamfer_matrix_fwd(const float* S, const int32_t* countsS, int Cs, int Ns, const float* Q, const int32_t* countsQ, int Cq, int Nq,
+                           float* mean_sq, float* mean_rt, float* max_sq, void* stream);
+int dpd_chamfer_matrix_bwd(const float* S, const int32_t* countsS, int Cs, int Ns, const float* Q, const int32_t* countsQ, int Cq, int Nq,
+                           int form, const float* W, float* dS, float* dQ, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Nearest-point distance labels of the training set; replaces scipy's cdist(point_set, candidates).min(0) of the reference's
  * label generator (dataset_sample_with_gt.py:90-91,121-122).  For each of S shapes
  *   dist[s][i] = min_j |q_si - p_sj|   (Euclidean, NOT squared),   arg[s][i] = the lowest such j (arg may be NULL).

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""DPDist and its baselines side by side on one retrieval task, on one GPU: C synthetic chairs (synth.make_chair), each sampled twice
+independently into sets A and B; every distance gives a [C, C] matrix between the two sets, and sample i of A should find sample i of B.
+
+    python tools/compare_demo.py [--clouds 64] [--num_point 64] [--dp_steps 3000] [--noise] [--add_occlusions F]
+
+DPDist is trained briefly on 64-point chair clouds as tools/registration_demo.py does (its own trainer, TF-Xavier seed 1234) and frozen;
+the matrices are dpdist_matrix, chamfer_matrix (both forms) and hausdorff_matrix.  --noise / --add_occlusions perturb set B through
+regtest.add_noise / regtest.occlude (the registration test's perturbations).  The Earth Mover's distance is not here: its matching is
+iterative per pair and has no all-pairs entry.
+
+Prints one JSON line: per distance the share of rows whose smallest entry is the diagonal (top-1 retrieval) and the mean rank of the
+diagonal (1 = always first).  There are no thresholds: the numbers are what they are.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+
+def retrieval(D):
+    """D [C, C] on the host -> (top-1 share, mean rank of the diagonal); a tie counts against the diagonal"""
+    diag = np.diag(D)[:, None]
+    rank = (D <= diag).sum(1)                              # 1 = the diagonal alone is the smallest of its row
+    return float((rank == 1).mean()), float(rank.mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clouds", type=int, default=64, help="chairs (= clouds per set)")
+    ap.add_argument("--num_point", type=int, default=64, help="points per cloud")
+    ap.add_argument("--dp_steps", type=int, default=3000)
+    ap.add_argument("--dp_pool", type=int, default=384, help="distinct DPDist training batches (32 chairs each)")
+    ap.add_argument("--dp_lr", type=float, default=1e-4)
+    ap.add_argument("--noise", action="store_true", help="perturb set B (regtest.add_noise)")
+    ap.add_argument("--add_occlusions", type=float, default=0.0, help="fraction of every cloud of B cut out around a random point")
+    ap.add_argument("--seed", type=int, default=7)
+    a = ap.parse_args()
+    import torch
+    from dpdist_amd import chamfer_matrix, dpdist_matrix, hausdorff_matrix, regtest, synth
+    from dpdist_amd.model import DPDistModel
+    from dpdist_amd.trainer import DPDistTrainer
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    cu = lambda x: torch.tensor(x, device=dev)   # noqa: E731
+
+    torch.manual_seed(1234)                                # the initialisation tools/registration_demo.py trains from
+    model = DPDistModel(device=dev)
+    tr = DPDistTrainer(model.params_, 32, base_lr=a.dp_lr, distributed=False)
+    pool = [tuple(cu(x) for x in synth.s2_modelnet_shaped(32, 64, 5000 + i, shapes="chair")) for i in range(min(a.dp_pool, max(1, a.dp_steps)))]
+    t0 = time.time()
+    run = float("nan")
+    for s in range(a.dp_steps):
+        loss = tr.step(*pool[s % len(pool)])
+        if (s + 1) % 500 == 0 or s + 1 == a.dp_steps:
+            run = loss[0].item()
+            print("DPDist step %d  loss_samples %.4f" % (s + 1, run), file=sys.stderr, flush=True)
+    torch.cuda.synchronize()
+    out = {"clouds": a.clouds, "num_point": a.num_point, "noise": a.noise, "add_occlusions": a.add_occlusions,
+           "dpdist": {"steps": a.dp_steps, "train_l1": run, "train_s": time.time() - t0}}
+
+    rng = np.random.default_rng(a.seed)
+    chairs = [synth.make_chair(rng) for _ in range(a.clouds)]
+    A = cu(np.stack([c.sample(rng, a.num_point) for c in chairs]).astype(np.float32))
+    B = cu(np.stack([c.sample(rng, a.num_point) for c in chairs]).astype(np.float32))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(a.seed)
+    if a.add_occlusions > 0:
+        B = regtest.occlude(B, a.add_occlusions, generator=gen)
+    if a.noise:
+        B = regtest.add_noise(B, generator=gen)
+    B = B.contiguous()
+
+    mats = {"dpdist": dpdist_matrix(model, A, B), "chamfer_squared": chamfer_matrix(A, B, "squared"), "chamfer_sqrt": chamfer_matrix(A, B, "sqrt"),
+            "hausdorff": hausdorff_matrix(A, B)}
+    out["retrieval"] = {}
+    for name, D in mats.items():
+        top1, rank = retrieval(D.detach().cpu().numpy().astype(np.float64))
+        out["retrieval"][name] = {"top1": top1, "mean_rank": rank}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
