@@ -25,4 +25,7 @@ def __getattr__(name):
     if name in ("chamfer_matrix", "hausdorff_matrix", "ChamferMatrix"):
         from . import baselines
         return getattr(baselines, name)
+    if name in ("emd_matrix", "EMDMatrix"):
+        from . import emd
+        return getattr(emd, name)
     raise AttributeError(name)

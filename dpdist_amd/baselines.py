@@ -35,17 +35,17 @@ def _form(form):
     return FORMS[form]
 
 
-def _prepare(cloudsA, cloudsB, countsA, countsB):
+def _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS):
     """every argument check, before anything is launched -> (A, B, cA, cB): contiguous fp32 sets and int32 device counts (None: a full
-    set; B and cB are None for a set against itself)"""
+    set; B and cB are None for a set against itself); cap: the most points per cloud the caller's entries take"""
     _check_shape(cloudsA, "cloudsA")
     if cloudsB is not None:
         _check_shape(cloudsB, "cloudsB")
     elif countsB is not None:
         raise ValueError("countsB given without cloudsB (a set against itself takes countsA)")
     for t, name in ((cloudsA, "cloudsA"), (cloudsB, "cloudsB")):
-        if t is not None and t.shape[1] > MAX_POINTS:
-            raise ValueError("%s holds %d points per cloud, the cap is %d" % (name, t.shape[1], MAX_POINTS))
+        if t is not None and t.shape[1] > cap:
+            raise ValueError("%s holds %d points per cloud, the cap is %d" % (name, t.shape[1], cap))
     if cloudsA.shape[0] * (cloudsA if cloudsB is None else cloudsB).shape[0] >= 1 << 31:
         raise ValueError("the matrix must hold fewer than 2^31 pairs")
     cA = _host_counts(countsA, cloudsA.shape[0], cloudsA.shape[1], "countsA")

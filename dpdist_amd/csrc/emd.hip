@@ -21,14 +21,10 @@
 // The four partial sums of a point are combined through LDS as (p0 + p1) + (p2 + p3).  Every sum has one order, there are no atomics, and
 // every output element has one writer per launch: two runs give identical bits.
 // exp goes through v_exp_f32 (base 2) with log2(e) folded into the level on the host; 1 / sqrt through v_rsq_f32.
-#include "common.h"
+// The scan of a wave and the finish of an owner are written once, in emd_int.h: the all-pairs kernel of emd_matrix.hip calls them too.
+#include "emd_int.h"
 
 namespace dpd {
-
-constexpr int kEmdThreads = 256;
-constexpr int kEmdWaves = kEmdThreads / kWave;   // 4
-constexpr int kEmdMax = DPD_EMD_MAX_POINTS;      // 2048: the staged cloud is 32 KiB of LDS
-constexpr int kEmdLevels = 10;
 
 struct EmdWs {            // carved from the caller's workspace, floats
     float* remainL;       // [B,n]
@@ -37,9 +33,6 @@ struct EmdWs {            // carved from the caller's workspace, floats
     float* remainR;       // [B,m]
     float* ratioR;        // [B,m]
 };
-
-__device__ __forceinline__ float emd_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float emd_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
 
 // stage `cnt` points of cloud p [cnt,3] with their vector entry v (or the constant c when v is NULL) as float4 {x,y,z,v}
 __device__ __forceinline__ void emd_stage(float4* s, const float* __restrict__ p, const float* __restrict__ v, float c, int cnt) {
@@ -74,51 +67,17 @@ __global__ __launch_bounds__(kEmdThreads) void emd_row_kernel(const float* __res
 
     const int per = (m + kEmdWaves - 1) / kEmdWaves;
     const int l0 = wave * per, l1 = min(m, l0 + per);
-    float sw = 0.f, sc = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, sr = 0.f;
-#pragma unroll 4
-    for (int l = l0; l < l1; ++l) {
-        const float4 q = s2[l];
-        const float dx = x - q.x, dy = y - q.y, dz = z - q.z;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        if (W) {
-            const float w = emd_exp2(lw * d2) * rl * sR[l];
-            const float inv = emd_rsqrt(fmaxf(d2, 1e-20f));
-            sw += w;
-            sc += w * (d2 * inv);                        // w sqrt(d^2); 0 at d^2 = 0
-            const float t = w * inv;
-            gx += t * dx, gy += t * dy, gz += t * dz;
-            if (mrow && k0 < n) {                        // lanes = consecutive k: coalesced
-                float* e = mrow + (size_t)l * n;
-                *e = first ? w : *e + w;
-            }
-        }
-        if (R) sr += emd_exp2(lr * d2) * q.w;
-    }
-    red[wave][0][lane] = sw, red[wave][1][lane] = sc, red[wave][2][lane] = gx, red[wave][3][lane] = gy, red[wave][4][lane] = gz,
-    red[wave][5][lane] = sr;
+    float acc[6];
+    emd_row_scan<W, R>(s2, sR, l0, l1, x, y, z, rl, lw, lr, k0 < n ? mrow : nullptr, n, first, acc);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) red[wave][c][lane] = acc[c];
     __syncthreads();
     if (wave != 0 || k0 >= n) return;
     float t[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
     const size_t ik = (size_t)b * n + k;
-    float rem = (first && !W) ? initL : ws.remainL[ik];
-    if (W) {
-        rem = fmaxf(0.f, rem - t[0]);
-        ws.remainL[ik] = rem;
-        ws.costk[ik] = first ? t[1] : ws.costk[ik] + t[1];
-        if (grad1) {
-            float* g = grad1 + ik * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = first ? t[2 + c] : g[c] + t[2 + c];
-                g[c] = v * gs;
-            }
-        }
-    } else {
-        ws.remainL[ik] = rem;
-    }
-    if (R) ws.ratioL[ik] = rem / (1e-9f + t[5]);
+    emd_row_finish<W, R>(t, first, initL, ws.remainL[ik], ws.costk[ik], ws.ratioL[ik], grad1 ? grad1 + ik * 3 : nullptr, gs);
 }
 
 // Column pass: step 2 of the level with base-2 exponent scale lv, and grad2's share of that level.
@@ -138,38 +97,17 @@ __global__ __launch_bounds__(kEmdThreads) void emd_col_kernel(const float* __res
 
     const int per = (n + kEmdWaves - 1) / kEmdWaves;
     const int k0 = wave * per, k1 = min(n, k0 + per);
-    float s = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll 4
-    for (int k = k0; k < k1; ++k) {
-        const float4 q = s1[k];
-        const float dx = q.x - x, dy = q.y - y, dz = q.z - z;          // x1 - x2, the sign grad1 uses
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        const float a = emd_exp2(lv * d2) * q.w;
-        s += a;
-        if (G) {
-            const float t = a * emd_rsqrt(fmaxf(d2, 1e-20f));
-            gx += t * dx, gy += t * dy, gz += t * dz;
-        }
-    }
-    red[wave][0][lane] = s;
-    if (G) red[wave][1][lane] = gx, red[wave][2][lane] = gy, red[wave][3][lane] = gz;
+    float acc[4];
+    emd_col_scan<G>(s1, k0, k1, x, y, z, lv, acc);
+    red[wave][0][lane] = acc[0];
+    if (G) red[wave][1][lane] = acc[1], red[wave][2][lane] = acc[2], red[wave][3][lane] = acc[3];
     __syncthreads();
     if (wave != 0 || l0 >= m) return;
     const size_t il = (size_t)b * m + l;
-    const float rem = first ? (float)max(n, m) / (float)m : ws.remainR[il];
-    const float sum = rem * ((red[0][0][lane] + red[1][0][lane]) + (red[2][0][lane] + red[3][0][lane]));
-    const float rr = fminf(rem / (sum + 1e-9f), 1.0f) * rem;
-    ws.ratioR[il] = rr;
-    ws.remainR[il] = fmaxf(0.f, rem - sum);
-    if (G) {
-        float* g = grad2 + il * 3;
+    float t[4] = {};
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float t = (red[0][1 + c][lane] + red[1][1 + c][lane]) + (red[2][1 + c][lane] + red[3][1 + c][lane]);
-            const float v = first ? -(rr * t) : g[c] - rr * t;
-            g[c] = v * gs;
-        }
-    }
+    for (int c = 0; c < (G ? 4 : 1); ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
+    emd_col_finish<G>(t, first, (float)max(n, m) / (float)m, ws.remainR[il], ws.ratioR[il], G ? grad2 + il * 3 : nullptr, gs);
 }
 
 // cost[b] = sum_k costk[b][k] and loss = mean_b cost[b] / n, one workgroup, fixed order
@@ -259,12 +197,8 @@ extern "C" int dpd_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, i
     hipStream_t s = (hipStream_t)stream;
     const dim3 grow(B, (n + kWave - 1) / kWave), gcol(B, (m + kWave - 1) / kWave), blk(kEmdThreads);
     const float gs = gscale / ((float)B * (float)n);
-    float lv[kEmdLevels];                                 // level * log2(e): exp(level d^2) = exp2(lv d^2)
-    for (int i = 0; i < kEmdLevels; ++i) {
-        const int j = 7 - i;
-        const double level = j == -2 ? 0.0 : -(j >= 0 ? (double)(1 << (2 * j)) : 0.25);
-        lv[i] = (float)(level * 1.4426950408889634074);
-    }
+    const EmdLevels levels = emd_levels();
+    const float* lv = levels.v;
     DPD_LAUNCH((emd_row_kernel<false, true>), grow, blk, 0, s, xyz1, xyz2, n, m, 0.f, lv[0], 1, w, grad1, match, 1.f);
     DPD_CHECK_LAUNCH();
     for (int i = 0; i < kEmdLevels; ++i) {

@@ -6,10 +6,17 @@ Restates (relative to /root/reference):
     models/ipcr_model.py:296-314       its use as the loss of the iterative PCRNet
 The reference's CUDA op (pc_distance/tf_approxmatch) is not in its tree; the contract is the one in include/dpdist_capi.h (dpd_emd_fwd).
 The match carries no gradient, like the op's.
+
+All pairs of two sets of clouds: emd_matrix / EMDMatrix (csrc/emd_matrix.hip: dpd_emd_matrix_fwd / _bwd, one workgroup per pair), in the
+conventions of dpdist_matrix and chamfer_matrix.  D[i, j] = earth_mover(A_i, B_j), bit for bit; nothing of size [Ca, Cb, N] exists in the
+forward, and the backward's per-pair gradients pass through a workspace bounded by MAX_WS_BYTES.  There is no fallback to expanded pairs.
 """
 import torch
 
 from . import lib as L
+
+MAX_POINTS = 2048                # DPD_EMD_MAX_POINTS: both clouds of a pair live in LDS
+MAX_WS_BYTES = 1 << 30           # bound on the workspace of EMDMatrix's backward: above it the backward goes in chunks of rows of A
 
 
 def _dims(pcd1, pcd2):
@@ -90,3 +97,101 @@ class _MatchCostFn(torch.autograd.Function):
 def match_cost(pcd1, pcd2, match):
     """The op's match_cost: cost [B] = sum_{k,l} match[l][k] |pcd1_k - pcd2_l| with gradients to both clouds, none to the match."""
     return _MatchCostFn.apply(pcd1.contiguous(), pcd2.contiguous(), match.contiguous())
+
+
+def _matrix_prepare(cloudsA, cloudsB, countsA, countsB):
+    from .baselines import _prepare
+    return _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS)
+
+
+def _matrix_check(rc, what):
+    from .baselines import _check
+    _check(rc, what)
+
+
+def _matrix_forward(A, B, cA, cB):
+    """D [Ca,Cb] of prepared sets (B None: A against itself, all Ca^2 pairs -- the match is not symmetric)"""
+    lib = L.load()
+    Q, cQ = (A, cA) if B is None else (B, cB)
+    D = torch.empty(A.shape[0], Q.shape[0], device=A.device, dtype=torch.float32)
+    with torch.cuda.device(A.device):
+        _matrix_check(lib.dpd_emd_matrix_fwd(L.ptr(A), L.ptr(cA), A.shape[0], A.shape[1], L.ptr(Q), L.ptr(cQ), Q.shape[0], Q.shape[1], None,
+                                             L.ptr(D), L.cur_stream()), "dpd_emd_matrix_fwd")
+    return D
+
+
+def _matrix_backward(A, B, cA, cB, W, needA, needB):
+    """(dA | None, dB | None) under the upstream W [Ca,Cb] of D.  Rows of A go in ascending chunks whose workspace stays within
+    MAX_WS_BYTES (one row at least); dB is a left fold over the rows, continued from chunk to chunk, so chunking changes no bit."""
+    lib = L.load()
+    (Ca, Na), (Cb, Nb) = A.shape[:2], B.shape[:2]
+    per_row = Cb * (Na + Nb) * 3 * 4
+    rows = max(1, min(Ca, MAX_WS_BYTES // per_row))
+    dA = torch.empty_like(A) if needA else None
+    dB = torch.empty_like(B) if needB else None
+    with torch.cuda.device(A.device):
+        ws = torch.empty(rows * per_row, device=A.device, dtype=torch.uint8)
+        s = L.cur_stream()
+        for chunk, i0 in enumerate(range(0, Ca, rows)):
+            r = min(rows, Ca - i0)
+            _matrix_check(lib.dpd_emd_matrix_bwd(L.ptr(A[i0:]), L.ptr(None if cA is None else cA[i0:]), r, Na, L.ptr(B), L.ptr(cB), Cb, Nb,
+                                                 L.ptr(W[i0:]), L.ptr(None if dA is None else dA[i0:]), L.ptr(dB), int(chunk > 0), L.ptr(ws),
+                                                 ws.numel(), s), "dpd_emd_matrix_bwd")
+    return dA, dB
+
+
+@torch.no_grad()
+def emd_matrix(cloudsA, cloudsB=None, *, countsA=None, countsB=None):
+    """cloudsA [Ca,N,3], cloudsB [Cb,M,3] (None: cloudsA against itself) -> D [Ca,Cb], D[i,j] = earth_mover(A_i, B_j): the cost of the
+    approximate matching of the pair over the number of points of A_i, bit for bit the paired entry's value.  The two sets may have
+    different widths.  countsA / countsB (keywords): ragged sets as in dpdist_matrix -- a sequence or CPU integer tensor is checked (one
+    count per cloud, each in [1, width]) and copied once, an int32 device tensor is used as it is and clamped by the kernels; padding is
+    never read.  ValueError for CPU tensors, a dtype other than float32, sets on two devices, bad counts, countsB without cloudsB and
+    more than 2048 points per cloud -- before anything is launched.  Forward only: EMDMatrix is differentiable."""
+    return _matrix_forward(*_matrix_prepare(cloudsA, cloudsB, countsA, countsB))
+
+
+class _EMDMatrixFn(torch.autograd.Function):
+    """D of two cloud sets as one autograd node; B is None for a set against itself"""
+
+    @staticmethod
+    def forward(ctx, A, B, cA, cB):
+        ctx.self_matrix = B is None
+        ctx.counts = (cA, cB)
+        ctx.set_materialize_grads(False)
+        a = A.detach().contiguous()
+        b = None if B is None else B.detach().contiguous()
+        ctx.save_for_backward(*((a,) if b is None else (a, b)))        # the two sets only: the match is recomputed
+        return _matrix_forward(a, b, cA, cB)
+
+    @staticmethod
+    def backward(ctx, gD):
+        cA, cB = ctx.counts
+        A = ctx.saved_tensors[0]
+        needA = ctx.needs_input_grad[0]
+        needB = (not ctx.self_matrix) and ctx.needs_input_grad[1]
+        if gD is None or not (needA or needB):
+            return (None,) * 4
+        W = gD.to(torch.float32).contiguous()
+        with torch.no_grad():
+            if ctx.self_matrix:                                        # both routes of the one call land in A
+                g1, g2 = _matrix_backward(A, A, cA, cA, W, True, True)
+                return g1 + g2, None, None, None
+            dA, dB = _matrix_backward(A, ctx.saved_tensors[1], cA, cB, W, needA, needB)
+        return dA, dB, None, None
+
+
+class EMDMatrix(torch.nn.Module):
+    """emd_matrix as a differentiable module: gradients to cloudsA and cloudsB under any upstream gradient of D [Ca,Cb].  One autograd node
+    over the library, on the current stream, without a host synchronisation; the forward values are bit for bit those of emd_matrix.  The
+    match carries no gradient (as in earth_mover); the node saves the two sets only and the backward recomputes the match of every
+    pair.  cloudsB = None: both routes of the one call land in cloudsA's gradient.  The gradient at a padded point is exactly +0.0; a set
+    that needs no gradient gets None and its route is skipped.  Arguments and errors as emd_matrix."""
+
+    def forward(self, cloudsA, cloudsB=None, *, countsA=None, countsB=None):
+        want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (cloudsA, cloudsB))
+        A, B, cA, cB = _matrix_prepare(cloudsA, cloudsB, countsA, countsB)
+        if not want_grad:
+            with torch.no_grad():
+                return _matrix_forward(A, B, cA, cB)
+        return _EMDMatrixFn.apply(cloudsA, cloudsB, cA, cB)

@@ -152,6 +152,10 @@ SIGNATURES = {
     "dpd_emd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dpd_emd_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "dpd_emd_match_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "dpd_emd_matrix_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dpd_emd_matrix_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    "dpd_emd_matrix_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3 +
+                           [c_int, c_void_p, c_size_t, c_void_p]),
     "dpd_pose_apply_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dpd_pose_apply_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "dpd_pose_refine_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -720,6 +720,33 @@ int dpd_emd_match_cost(const float* xyz1, const float* xyz2, int B, int n, int m
                        float* loss, float* grad1, float* grad2, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * All-pairs Earth Mover's distance: the EMD of every pair of two SETS of clouds (dpdist_amd/emd.py: emd_matrix, EMDMatrix;
+ * csrc/emd_matrix.hip), one launch with one workgroup per pair.  A [Ca,Na,3], B [Cb,Nb,3]; countsA / countsB: per-cloud counts (int32,
+ * DEVICE memory, the rules of the RAGGED block: never read by the host, clamped into [1, width] by the kernels, the padding is never
+ * read); NULL = the set is full.  For pair (i,j), n = countsA[i] and m = countsB[j]:
+ *   cost[i,j] = dpd_emd_fwd's cost[0] for xyz1 = A_i[:n], xyz2 = B_j[:m], B = 1 (the definition above, unchanged), bit for bit
+ *   dist[i,j] = cost[i,j] / n, which is earth_mover of that pair               (each [Ca,Cb]; either may be NULL, both: DPD_E_NULL)
+ * The match is not symmetric: a set against itself is called with B == A and computes all Ca^2 pairs, there is no transpose shortcut.
+ * dpd_emd_matrix_bwd: the match is a constant and is recomputed (the forward keeps nothing).  With g1(i,j) [n,3] and g2(i,j) [m,3] the
+ * definition's d cost / d xyz1 and d cost / d xyz2 of the pair and W [Ca,Cb] the upstream of dist,
+ *   dA[i,k] = sum_j (W[i,j] / n_i) g1(i,j)[k]        j ascending, from +0.0
+ *   dB[j,l] = sum_i (W[i,j] / n_i) g2(i,j)[l]        i ascending, a left fold from +0.0, or from dB's value when accumulate_dB != 0
+ * so a caller may split A into consecutive row blocks (A, countsA, W and dA advanced, accumulate_dB set from the second block on) without
+ * changing a bit.  dA [Ca,Na,3] and dB [Cb,Nb,3]: either may be NULL (both: DPD_E_NULL), a skipped side is not computed; rows at or
+ * beyond a cloud's count are written +0.0.  ws: dpd_emd_matrix_workspace_bytes = Ca * Cb * (Na + Nb) * 3 floats of device scratch for
+ * the per-pair gradients (the backward only; 0 for a refused shape); a second kernel folds them in the orders above.
+ * Every sum has one fixed order that depends on the pair's two counts only, and there are no atomics: two calls give the same bits, and
+ * the padded widths, the padding and the other clouds change no bit.  No allocation, stream-ordered.
+ * Refusals, before anything is launched and with the outputs untouched: DPD_E_NULL for a missing A, B, W or all outputs; DPD_E_DIM for
+ * Ca < 1, Cb < 1 or Ca * Cb >= 2^31; DPD_E_UNSUPPORTED unless 1 <= Na, Nb <= DPD_EMD_MAX_POINTS (both clouds of a pair live in LDS);
+ * DPD_E_WORKSPACE for a missing or too small workspace.  The number of pairs is not bound by a grid dimension.                        */
+size_t dpd_emd_matrix_workspace_bytes(int Ca, int Na, int Cb, int Nb);
+int dpd_emd_matrix_fwd(const float* A, const int32_t* countsA, int Ca, int Na, const float* B, const int32_t* countsB, int Cb, int Nb,
+                       float* cost, float* dist, void* stream);
+int dpd_emd_matrix_bwd(const float* A, const int32_t* countsA, int Ca, int Na, const float* B, const int32_t* countsB, int Cb, int Nb,
+                       const float* W, float* dA, float* dB, int accumulate_dB, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pose algebra of the iterative registration that consumes DPDist as its loss (row f2; csrc/pose.hip): ONE launch for the chain of
  * ~115 element-wise ops the reference runs per refinement loop.  pred [B,7] = the pose network's raw output (t, angle, axis).
  *   pose   [B,7]   (optional) quat_normalize(pred): (tanh(t) 0.1, cos(a/2), axis sin(a/2)), |a| <= lim_rot_deg

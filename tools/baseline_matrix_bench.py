@@ -18,7 +18,16 @@ The two routes alternate, `--rounds` calls after two warm-up calls, each timed w
 timed both routes are held to the bars of tests/test_baseline_matrix_gpu.py against a float64 evaluation (on the device, through the
 argmins the paired entry stored): D within twice the mean bar (max(n_ab, n_ba) + 3) u ref of each other, each gradient element within
 (T + c) u S of float64 with c = 4 for the matrix and 8 for the expanded route (it rounds its weights differently); the tool refuses to
-time otherwise.  No threshold is set on the times."""
+time otherwise.  No threshold is set on the times.
+
+    python tools/baseline_matrix_bench.py --emd [--out profiles/emd_matrix_bench.txt]
+
+times the all-pairs Earth Mover's distance instead (dpdist_amd.emd_matrix / EMDMatrix: one workgroup per pair, one launch) against the
+route there was before it: the Ca * Cb pairs expanded into [Ca * Cb, n, 3] copies and sent through the paired entry dpd_emd_fwd (22
+dependent launches over all pairs), the per-pair upstream applied and the pairs summed in torch.  Full sets (the paired entry has no
+counts), at 32 x 32 clouds of 64 points, 16 x 16 of 256, 8 x 8 of 1024 and 4 x 4 of 2048.  The time of the copies is part of the
+expanded route and is shown on its own as well.  Before a shape is timed D of the two routes has to be the same bits and every gradient
+element within 4 (C + 4) u S of the other route's (C terms of absolute sum S, each rounded a few times differently)."""
 import argparse
 import json
 import os
@@ -180,14 +189,140 @@ def check_grad(name, got, ref, c):
     return float((err / bar.clamp_min(1e-300)).max())
 
 
+EMD_SHAPES = ((32, 64), (16, 256), (8, 1024), (4, 2048))
+
+
+class ExpandedEMD:
+    """the route of the parent commit: every pair as a batch entry of dpd_emd_fwd"""
+
+    def __init__(self, A, B):
+        self.lib, self.A, self.B = L.load(), A, B
+        self.C, self.N = A.shape[0], A.shape[1]
+        self.P = self.C * self.C
+        dev = A.device
+        self.ws = torch.empty(self.lib.dpd_emd_workspace_bytes(self.P, self.N, self.N), device=dev, dtype=torch.uint8)
+        self.cost, self.loss = torch.empty(self.P, device=dev), torch.empty(1, device=dev)
+        self.copy_ms = []
+
+    def copies(self):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        a = self.A.repeat_interleave(self.C, 0)
+        b = self.B.repeat(self.C, 1, 1)
+        e1.record()
+        self.copy_ms.append((e0, e1))
+        return a, b
+
+    def run(self, a, b, g1, g2):
+        # gscale = P N: the gradients of cost[p] itself, not of the batch mean
+        L.check(self.lib.dpd_emd_fwd(L.ptr(a), L.ptr(b), self.P, self.N, self.N, float(self.P * self.N), L.ptr(self.cost), L.ptr(self.loss),
+                                     L.ptr(g1), L.ptr(g2), None, L.ptr(self.ws), self.ws.numel(), L.cur_stream()), "dpd_emd_fwd")
+        return (self.cost / self.N).view(self.C, self.C)
+
+    def forward(self):
+        a, b = self.copies()
+        return self.run(a, b, None, None)
+
+    def forward_backward(self, G, stats=False):
+        a, b = self.copies()
+        g1, g2 = torch.empty_like(a), torch.empty_like(b)
+        D = self.run(a, b, g1, g2)
+        w = (G / self.N)[:, :, None, None]
+        t1, t2 = g1.view(self.C, self.C, self.N, 3) * w, g2.view(self.C, self.C, self.N, 3) * w
+        if stats:
+            return D, t1.sum(1), t2.sum(0), t1.abs().sum(1), t2.abs().sum(0)
+        return D, t1.sum(1), t2.sum(0)
+
+    def take_copy_ms(self):
+        ms = [e0.elapsed_time(e1) for e0, e1 in self.copy_ms]
+        self.copy_ms = []
+        return ms
+
+
+def emd_main(a):
+    from dpdist_amd import EMDMatrix, emd_matrix
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(12)
+    res = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "shapes": {}}
+    lines = ["# tools/baseline_matrix_bench.py --emd --rounds %d" % a.rounds,
+             "# device: %s; Earth Mover's distance of every pair, full sets; ms per call (in-stream device event pairs), median [min .. max] of %d"
+             % (res["device"], a.rounds),
+             "# alternating calls after 2 warm-up calls.  matrix: emd_matrix / EMDMatrix (one launch, one workgroup per pair; forward+backward:",
+             "# loss = (G * D).sum(), random G).  expanded: the pairs copied into [Ca * Cb, n, 3] batches and sent through dpd_emd_fwd; its time",
+             "# includes the copies, whose share is shown as `copies`.", ""]
+    mod = EMDMatrix()
+    for C, N in EMD_SHAPES:
+        A = torch.tensor(rng.uniform(-0.8, 0.8, (C, N, 3)).astype(np.float32), device=dev)
+        B = torch.tensor(rng.uniform(-0.8, 0.8, (C, N, 3)).astype(np.float32), device=dev)
+        G = torch.tensor(rng.standard_normal((C, C)).astype(np.float32), device=dev)
+        ex = ExpandedEMD(A, B)
+
+        def matrix_fb():
+            x, y = A.detach().requires_grad_(True), B.detach().requires_grad_(True)
+            D = mod(x, y)
+            (G * D).sum().backward()
+            return D.detach(), x.grad, y.grad
+
+        f = {"matrix": (lambda: emd_matrix(A, B), matrix_fb), "expanded": (ex.forward, lambda: ex.forward_backward(G))}
+        # agreement, before anything is timed
+        Dm, gAm, gBm = matrix_fb()
+        De, gAe, gBe, SA, SB = ex.forward_backward(G, stats=True)
+        torch.cuda.synchronize()
+        for label, D in (("matrix", Dm), ("matrix forward", f["matrix"][0]()), ("expanded forward", f["expanded"][0]())):
+            if not torch.equal(D, De):
+                raise SystemExit("%d x %d x %d: D of %s and of the expanded route differ in bits" % (C, C, N, label))
+        worst = 0.0
+        for label, got, ref, S in (("dA", gAm, gAe, SA), ("dB", gBm, gBe, SB)):
+            bar = 4 * (C + 4) * U * S
+            err = (got.double() - ref.double()).abs()
+            if not bool((err <= bar).all()):
+                raise SystemExit("%d x %d x %d: %s of the two routes differ by more than 4 (C + 4) u S" % (C, C, N, label))
+            worst = max(worst, float((err / bar.clamp_min(1e-300)).max()))
+        ex.take_copy_ms()
+        name = "%dx%dx%d" % (C, C, N)
+        lines.append("%s: Ca = Cb = %d, n = m = %d; D the same bits on both routes, gradients within %.3f of 4 (C + 4) u S of each other" % (name, C, N, worst))
+        shape = res["shapes"][name] = {"grad_difference_over_bar": worst}
+        for k, what in ((0, "forward"), (1, "forward+backward")):
+            for _ in range(2):
+                f["matrix"][k](), f["expanded"][k]()
+            torch.cuda.synchronize()
+            ex.take_copy_ms()
+            t = {"matrix": [], "expanded": []}
+            for _ in range(a.rounds):
+                for route in ("matrix", "expanded"):
+                    t[route].append(timed(f[route][k]))
+            copies = float(np.median(ex.take_copy_ms()))
+            med = {route: float(np.median(v)) for route, v in t.items()}
+            ratio = med["expanded"] / med["matrix"]
+            win = "matrix" if ratio > 1 else "expanded"
+            shape[what] = {"matrix_ms": round(med["matrix"], 4), "expanded_ms": round(med["expanded"], 4), "expanded_copies_ms": round(copies, 4),
+                           "expanded_over_matrix": round(ratio, 2), "winner": win}
+            lines.append("    %-17s matrix %9.3f [%9.3f .. %9.3f]   expanded %9.3f [%9.3f .. %9.3f] (copies %7.3f)   expanded / matrix %6.2f   -> %s wins"
+                         % (what, med["matrix"], min(t["matrix"]), max(t["matrix"]), med["expanded"], min(t["expanded"]), max(t["expanded"]), copies,
+                            ratio, win))
+        lines.append("")
+    text = "\n".join(lines)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(text)
+    print(text)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--emd", action="store_true", help="time the all-pairs Earth Mover's distance instead (see the module docstring)")
     ap.add_argument("--clouds", type=int, default=64)
     ap.add_argument("--points", type=int, default=1024)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--rows", type=int, default=8, help="rows of the matrix per call of the paired entry (expanded route)")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "baseline_matrix_bench.txt"))
+    ap.add_argument("--out", default=None, help="the record; default profiles/baseline_matrix_bench.txt, with --emd profiles/emd_matrix_bench.txt")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "emd_matrix_bench.txt" if a.emd else "baseline_matrix_bench.txt")
+    if a.emd:
+        return emd_main(a)
     dev = torch.device("cuda:0")
     C, N = a.clouds, a.points
     rng = np.random.default_rng(12)

@@ -5,9 +5,9 @@ independently into sets A and B; every distance gives a [C, C] matrix between th
     python tools/compare_demo.py [--clouds 64] [--num_point 64] [--dp_steps 3000] [--noise] [--add_occlusions F]
 
 DPDist is trained briefly on 64-point chair clouds as tools/registration_demo.py does (its own trainer, TF-Xavier seed 1234) and frozen;
-the matrices are dpdist_matrix, chamfer_matrix (both forms) and hausdorff_matrix.  --noise / --add_occlusions perturb set B through
-regtest.add_noise / regtest.occlude (the registration test's perturbations).  The Earth Mover's distance is not here: its matching is
-iterative per pair and has no all-pairs entry.
+the matrices are dpdist_matrix, chamfer_matrix (both forms), hausdorff_matrix and emd_matrix (the three distances of the reference's
+registration comparison and the Hausdorff distance).  --noise / --add_occlusions perturb set B through regtest.add_noise /
+regtest.occlude (the registration test's perturbations).
 
 Prints one JSON line: per distance the share of rows whose smallest entry is the diagonal (top-1 retrieval) and the mean rank of the
 diagonal (1 = always first).  There are no thresholds: the numbers are what they are.
@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     a = ap.parse_args()
     import torch
-    from dpdist_amd import chamfer_matrix, dpdist_matrix, hausdorff_matrix, regtest, synth
+    from dpdist_amd import chamfer_matrix, dpdist_matrix, emd_matrix, hausdorff_matrix, regtest, synth
     from dpdist_amd.model import DPDistModel
     from dpdist_amd.trainer import DPDistTrainer
     dev = torch.device("cuda", 0)
@@ -76,7 +76,7 @@ def main():
     B = B.contiguous()
 
     mats = {"dpdist": dpdist_matrix(model, A, B), "chamfer_squared": chamfer_matrix(A, B, "squared"), "chamfer_sqrt": chamfer_matrix(A, B, "sqrt"),
-            "hausdorff": hausdorff_matrix(A, B)}
+            "hausdorff": hausdorff_matrix(A, B), "emd": emd_matrix(A, B)}
     out["retrieval"] = {}
     for name, D in mats.items():
         top1, rank = retrieval(D.detach().cpu().numpy().astype(np.float64))
