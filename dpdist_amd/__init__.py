@@ -22,10 +22,10 @@ def __getattr__(name):
     if name in ("dpdist_pairs", "DPDistPairs"):
         from . import pairs
         return getattr(pairs, name)
-    if name in ("chamfer_matrix", "hausdorff_matrix", "ChamferMatrix"):
+    if name in ("chamfer_matrix", "hausdorff_matrix", "ChamferMatrix", "chamfer_pairs", "hausdorff_pairs", "ChamferPairs"):
         from . import baselines
         return getattr(baselines, name)
-    if name in ("emd_matrix", "EMDMatrix"):
+    if name in ("emd_matrix", "EMDMatrix", "emd_pairs", "EMDPairs"):
         from . import emd
         return getattr(emd, name)
     raise AttributeError(name)

@@ -1,5 +1,6 @@
-"""All-pairs baselines: the Chamfer and Hausdorff distance matrices between two sets of clouds (include/dpdist_capi.h:
-dpd_chamfer_matrix_fwd, dpd_chamfer_matrix_bwd), in the conventions of dpdist_matrix (dpdist_amd/pairwise.py).
+"""The baselines between two sets of clouds: the Chamfer and Hausdorff distance matrices of all pairs (include/dpdist_capi.h:
+dpd_chamfer_matrix_fwd, dpd_chamfer_matrix_bwd), in the conventions of dpdist_matrix (dpdist_amd/pairwise.py), and the same distances
+of the pairs (A_b, B_b) alone (dpd_chamfer_pairs_fwd, dpd_chamfer_pairs_bwd), in the conventions of dpdist_pairs.
 
     D_AB[i, j] = mean over the real points q of B_j of  min_p |q - A_i[p]|^2      (form "squared";  "sqrt": of the root of that minimum)
     D_BA[i, j] = mean over the real points q of A_i of  min_p |q - B_j[p]|^2
@@ -13,6 +14,9 @@ is the Hausdorff distance.  A is the surface of D_AB, as in dpdist_matrix.  Noth
 surface cloud in LDS and walks query clouds past it.  Exact fp32, on the current stream, without a host synchronisation, no workspace.
 Ragged sets (countsA / countsB) are those of dpdist_matrix: padding influences no bit and gets the gradient +0.0; here it is never read.
 There is no fallback to expanded pairs.
+
+chamfer_pairs / hausdorff_pairs / ChamferPairs: D[b] = D of the pair (A_b, B_b) with the definitions above, bit for bit the 1 x 1 matrix
+of that pair, from kernels shaped for few, large pairs (a pair is spread over workgroups; the argmins [P, W] are kept for the backward).
 """
 import torch
 
@@ -35,18 +39,23 @@ def _form(form):
     return FORMS[form]
 
 
-def _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS):
+def _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS, pairs=False):
     """every argument check, before anything is launched -> (A, B, cA, cB): contiguous fp32 sets and int32 device counts (None: a full
-    set; B and cB are None for a set against itself); cap: the most points per cloud the caller's entries take"""
+    set; B and cB are None for a set against itself); cap: the most points per cloud the caller's entries take; pairs: the sets are
+    scored cloud by cloud (both are needed and must hold the same number of clouds) instead of all against all"""
     _check_shape(cloudsA, "cloudsA")
-    if cloudsB is not None:
+    if pairs:
+        _check_shape(cloudsB, "cloudsB")
+        if cloudsA.shape[0] != cloudsB.shape[0]:
+            raise ValueError("cloudsA and cloudsB must hold the same number of clouds, got %d and %d" % (cloudsA.shape[0], cloudsB.shape[0]))
+    elif cloudsB is not None:
         _check_shape(cloudsB, "cloudsB")
     elif countsB is not None:
         raise ValueError("countsB given without cloudsB (a set against itself takes countsA)")
     for t, name in ((cloudsA, "cloudsA"), (cloudsB, "cloudsB")):
         if t is not None and t.shape[1] > cap:
             raise ValueError("%s holds %d points per cloud, the cap is %d" % (name, t.shape[1], cap))
-    if cloudsA.shape[0] * (cloudsA if cloudsB is None else cloudsB).shape[0] >= 1 << 31:
+    if not pairs and cloudsA.shape[0] * (cloudsA if cloudsB is None else cloudsB).shape[0] >= 1 << 31:
         raise ValueError("the matrix must hold fewer than 2^31 pairs")
     cA = _host_counts(countsA, cloudsA.shape[0], cloudsA.shape[1], "countsA")
     cB = None if cloudsB is None else _host_counts(countsB, cloudsB.shape[0], cloudsB.shape[1], "countsB")
@@ -197,4 +206,113 @@ class ChamferMatrix(torch.nn.Module):
                 D, d_ab, d_ba = _chamfer_forward(A, B, cA, cB, self._form)
         else:
             D, d_ab, d_ba = _ChamferMatrixFn.apply(cloudsA, cloudsB, self._form, cA, cB)
+        return (D, d_ab, d_ba) if return_directed else D
+
+
+def _pairs_forward(A, B, cA, cB, want):
+    """one dpd_chamfer_pairs_fwd call -> ({name: [2, P]} for the names in `want`, (arg_ab [P,Wb], arg_ba [P,Wa]))"""
+    lib = L.load()
+    P, Wa, Wb = A.shape[0], A.shape[1], B.shape[1]
+    dev = A.device
+    out = {n: torch.empty(2, P, device=dev, dtype=torch.float32) for n in want}
+    min_ab, min_ba = torch.empty(P, Wb, device=dev, dtype=torch.float32), torch.empty(P, Wa, device=dev, dtype=torch.float32)
+    arg_ab, arg_ba = torch.empty(P, Wb, device=dev, dtype=torch.int32), torch.empty(P, Wa, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _check(lib.dpd_chamfer_pairs_fwd(L.ptr(A), L.ptr(cA), Wa, L.ptr(B), L.ptr(cB), Wb, P, L.ptr(min_ab), L.ptr(arg_ab), L.ptr(min_ba),
+                                         L.ptr(arg_ba), L.ptr(out.get("mean_sq")), L.ptr(out.get("mean_rt")), L.ptr(out.get("max_sq")),
+                                         L.cur_stream()), "dpd_chamfer_pairs_fwd")
+    return out, (arg_ab, arg_ba)
+
+
+def _chamfer_pairs_forward(A, B, cA, cB, form):
+    out, args = _pairs_forward(A, B, cA, cB, (("mean_sq", "mean_rt")[form],))
+    d = out[("mean_sq", "mean_rt")[form]]
+    return ((d[0] + d[1]) / 2, d[0], d[1]), args
+
+
+@torch.no_grad()
+def chamfer_pairs(cloudsA, cloudsB, form="squared", return_directed=False, *, countsA=None, countsB=None):
+    """cloudsA [P,N,3], cloudsB [P,M,3] -> the Chamfer distance D [P] of the pairs (A_b, B_b), or (D, D_AB, D_BA) with return_directed:
+    D[b] is chamfer_matrix(A[b:b+1], B[b:b+1])[0, 0] with the same counts, bit for bit (form "squared": aue.chamfer_dist of the pair,
+    "sqrt": regtest.chamfer_sqrt).  D_AB[b] averages over the real points of B_b their nearest distance to A_b.  The two sets may have
+    different widths.  countsA / countsB (keywords): ragged sets as in dpdist_pairs -- a sequence or CPU integer tensor is checked (one
+    count per cloud, each in [1, width]) and copied once, an int32 device tensor is used as it is and clamped by the kernels; padding is
+    never read.  ValueError for sets of different lengths, CPU tensors, a dtype other than float32, sets on two devices, bad counts and
+    more than 4096 points per cloud -- before anything is launched.  Forward only: ChamferPairs is differentiable."""
+    f = _form(form)
+    A, B, cA, cB = _prepare(cloudsA, cloudsB, countsA, countsB, pairs=True)
+    (D, d_ab, d_ba), _ = _chamfer_pairs_forward(A, B, cA, cB, f)
+    return (D, d_ab, d_ba) if return_directed else D
+
+
+@torch.no_grad()
+def hausdorff_pairs(cloudsA, cloudsB, return_directed=False, *, countsA=None, countsB=None):
+    """The Hausdorff distance H [P] = sqrt(max(max_AB, max_BA)) of the pairs (A_b, B_b), or (H, H_AB, H_BA) with return_directed: bit for
+    bit hausdorff_matrix of each pair alone.  Arguments, ragged sets and errors as chamfer_pairs.  FORWARD ONLY, as hausdorff_matrix."""
+    A, B, cA, cB = _prepare(cloudsA, cloudsB, countsA, countsB, pairs=True)
+    m = _pairs_forward(A, B, cA, cB, ("max_sq",))[0]["max_sq"]
+    H = torch.sqrt(torch.maximum(m[0], m[1]))
+    return (H, torch.sqrt(m[0]), torch.sqrt(m[1])) if return_directed else H
+
+
+class _ChamferPairsFn(torch.autograd.Function):
+    """(D, D_AB, D_BA) [P] of the pairs of two cloud sets as one autograd node"""
+
+    @staticmethod
+    def forward(ctx, A, B, form, cA, cB):
+        ctx.form = form
+        ctx.counts = (cA, cB)
+        ctx.set_materialize_grads(False)
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        out, (arg_ab, arg_ba) = _chamfer_pairs_forward(a, b, cA, cB, form)
+        ctx.save_for_backward(a, b, arg_ab, arg_ba)                    # the argmins are [P, W]: kept, not recomputed
+        return out
+
+    @staticmethod
+    def backward(ctx, gD, gAB, gBA):
+        cA, cB = ctx.counts
+        A, B, arg_ab, arg_ba = ctx.saved_tensors
+        needA, needB = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (gD is None and gAB is None and gBA is None) or not (needA or needB):
+            return (None,) * 5
+
+        def upstream(*terms):
+            terms = [t for t in terms if t is not None]
+            return sum(terms[1:], terms[0]).to(torch.float32).contiguous() if terms else None
+
+        # D = (D_AB + D_BA) / 2: G_ab = G / 2 + G_ab, G_ba = G / 2 + G_ba, as ChamferMatrix forms them
+        half = None if gD is None else gD / 2
+        g_ab, g_ba = upstream(half, gAB), upstream(half, gBA)
+        lib = L.load()
+        dA = torch.empty_like(A) if needA else None
+        dB = torch.empty_like(B) if needB else None
+        with torch.cuda.device(A.device), torch.no_grad():
+            _check(lib.dpd_chamfer_pairs_bwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], ctx.form,
+                                             L.ptr(arg_ab), L.ptr(arg_ba), L.ptr(g_ab), L.ptr(g_ba), L.ptr(dA), L.ptr(dB), L.cur_stream()),
+                   "dpd_chamfer_pairs_bwd")
+        return dA, dB, None, None, None
+
+
+class ChamferPairs(torch.nn.Module):
+    """chamfer_pairs as a differentiable module: gradients to cloudsA and cloudsB under any upstream gradient of D [P] and, with
+    return_directed, of D_AB and D_BA.  One autograd node over the library, on the current stream, without a host synchronisation; the
+    forward values are bit for bit those of chamfer_pairs and the gradients those of ChamferMatrix on each pair alone.  The node saves
+    the two sets and the argmins [P, W] of the forward (ties go to the lowest index).  Each set's gradient is its surface route from one
+    direction plus its query route from the other, written by one kernel.  form "sqrt": a pair of coincident points contributes exactly
+    zero, as in ChamferMatrix.  The gradient at a padded point is exactly +0.0; a set that needs no gradient gets None and its route is
+    skipped.  Arguments and errors as chamfer_pairs."""
+
+    def __init__(self, form="squared"):
+        super().__init__()
+        self.form = form
+        self._form = _form(form)
+
+    def forward(self, cloudsA, cloudsB, return_directed=False, *, countsA=None, countsB=None):
+        want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (cloudsA, cloudsB))
+        A, B, cA, cB = _prepare(cloudsA, cloudsB, countsA, countsB, pairs=True)
+        if not want_grad:
+            with torch.no_grad():
+                D, d_ab, d_ba = _chamfer_pairs_forward(A, B, cA, cB, self._form)[0]
+        else:
+            D, d_ab, d_ba = _ChamferPairsFn.apply(cloudsA, cloudsB, self._form, cA, cB)
         return (D, d_ab, d_ba) if return_directed else D

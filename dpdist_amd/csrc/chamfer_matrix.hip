@@ -14,60 +14,11 @@
 
 namespace dpd {
 
-constexpr int kCmMaxPoints = 4096;     // the paired entries' cap: the surface cloud lives in LDS
 constexpr int kCmQueries = 4;          // query points a thread keeps in registers per pass (forward, query route)
 constexpr int kCmPass = 256 * kCmQueries;
 constexpr int kCmSurfThreads = 1024;   // surface route: one workgroup per surface cloud
-constexpr int kCmMaxGrid = 1 << 20;    // workgroups per launch; the kernels stride over their units beyond it
 constexpr int kCmFwdUnits = 2048;      // forward: (surface cloud, query group) units aimed at, 8 per CU
 constexpr int kCmDqBlocks = 512;       // query route: workgroups aimed at before a thread takes more queries, 2 per CU
-
-__device__ __forceinline__ int cm_count(const int32_t* __restrict__ counts, int c, int width) {
-    if (!counts) return width;
-    const int n = counts[c];
-    return n < 1 ? 1 : (n > width ? width : n);
-}
-
-__device__ __forceinline__ void cm_stage(float* __restrict__ s_y, const float* __restrict__ y, int ny) {
-    for (int e = threadIdx.x; e < ny * 3; e += blockDim.x) s_y[e] = y[e];
-}
-
-// best[r] = min_p |q_r - s_p|^2 over the ny staged points, arg[r] = the lowest such p (ARG).  A minimum does not depend on the visiting
-// order; the argmin takes the first strict improvement of an ascending walk.
-template <int R, bool ARG>
-__device__ __forceinline__ void cm_scan(const float* __restrict__ s_y, int ny, const float (&q)[R][3], float (&best)[R], int (&arg)[R]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) { best[r] = INFINITY; arg[r] = 0; }
-    int p = 0;
-    for (; p + 4 <= ny; p += 4) {
-        const float4* v = reinterpret_cast<const float4*>(s_y + p * 3);
-        const float4 a = v[0], b = v[1], c = v[2];
-        const float y[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float d = chamfer_pair_sq(q[r][0], q[r][1], q[r][2], y + k * 3);
-                if (ARG) {
-                    if (d < best[r]) { best[r] = d; arg[r] = p + k; }
-                } else {
-                    best[r] = fminf(best[r], d);
-                }
-            }
-        }
-    }
-    for (; p < ny; ++p) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float d = chamfer_pair_sq(q[r][0], q[r][1], q[r][2], s_y + p * 3);
-            if (ARG) {
-                if (d < best[r]) { best[r] = d; arg[r] = p; }
-            } else {
-                best[r] = fminf(best[r], d);
-            }
-        }
-    }
-}
 
 // the queries n = first + r * 256 of this thread (r < RMAX) against the staged cloud; `live` (wave-uniform) is how many of the wave's r
 // carry a real query, so a wave of a small cloud scans for one or two points per thread, not four.  Lanes without a real query scan the
@@ -115,17 +66,6 @@ __device__ __forceinline__ int cm_live(int base, int nq, int rmax) {
     if (wave_first >= nq) return 0;
     const int live = (nq - wave_first + 255) / 256;
     return live > rmax ? rmax : live;
-}
-
-// max over the 64 lanes of NON-NEGATIVE values (a lane without a DPP source reads 0), returned in every lane
-__device__ __forceinline__ float cm_wave_max(float v) {
-    v = fmaxf(v, dpp_move<0xB1>(v));
-    v = fmaxf(v, dpp_move<0x4E>(v));
-    v = fmaxf(v, dpp_move<0x141>(v));
-    v = fmaxf(v, dpp_move<0x140>(v));
-    v = fmaxf(v, dpp_move<0x142, 0xA>(v));
-    v = fmaxf(v, dpp_move<0x143, 0xC>(v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
 // Forward.  Unit u = (surface cloud i, group g of `per` consecutive query clouds); a workgroup stages S_i once per unit.
@@ -182,22 +122,6 @@ __global__ __launch_bounds__(256) void chamfer_matrix_fwd_kernel(const float* __
             __syncthreads();
         }
     }
-}
-
-// one term of a gradient: w * t(x, y) added to g.  Squared form: t = 2 (x - y); square-rooted form: t = (x - y) / |x - y| with the
-// hardware reciprocal square root of d2 = |x - y|^2, and exactly nothing where d2 is 0 (the deviation of dpd_chamfer_sqrt_bwd).
-template <int FORM>
-__device__ __forceinline__ void cm_term(float w, float d2, float xx, float xy, float xz, const float* __restrict__ y, float (&g)[3]) {
-    float s;
-    if (FORM == 0) {
-        s = 2.f;
-    } else {
-        if (!(d2 > 0.f)) return;
-        s = rsqrtf(d2);   // v_rsq_f32, with the input scaled where d2 is subnormal
-    }
-    g[0] += w * (s * (xx - y[0]));
-    g[1] += w * (s * (xy - y[1]));
-    g[2] += w * (s * (xz - y[2]));
 }
 
 // Query route: dQ[j,n] = sum_i W[i,j] / nq_j * t(q_n, s_arg(i,j,n)), i ascending.  Workgroup (j, chunk of 256 R queries) walks every

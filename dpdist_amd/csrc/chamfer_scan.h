@@ -38,4 +38,84 @@ __device__ __forceinline__ void chamfer_min_scan(const float* __restrict__ a, co
     (dir ? arg_b : arg_a)[(size_t)c * nx + i] = bj;
 }
 
+// What the counted kernels share: chamfer_matrix.hip (one workgroup owns a surface cloud and walks query clouds past it) and
+// chamfer_pairs.hip (a workgroup takes 256 queries of one pair) clamp, stage, scan and differentiate with these bodies, so a pair gets the
+// same bits from either.
+constexpr int kCmMaxPoints = 4096;     // the cap of every Chamfer entry: the surface cloud lives in LDS
+constexpr int kCmMaxGrid = 1 << 20;    // workgroups per launch; the kernels stride over their units beyond it
+
+__device__ __forceinline__ int cm_count(const int32_t* __restrict__ counts, int c, int width) {
+    if (!counts) return width;
+    const int n = counts[c];
+    return n < 1 ? 1 : (n > width ? width : n);
+}
+
+__device__ __forceinline__ void cm_stage(float* __restrict__ s_y, const float* __restrict__ y, int ny) {
+    for (int e = threadIdx.x; e < ny * 3; e += blockDim.x) s_y[e] = y[e];
+}
+
+// best[r] = min_p |q_r - s_p|^2 over the ny staged points, arg[r] = the lowest such p (ARG).  A minimum does not depend on the visiting
+// order; the argmin takes the first strict improvement of an ascending walk.
+template <int R, bool ARG>
+__device__ __forceinline__ void cm_scan(const float* __restrict__ s_y, int ny, const float (&q)[R][3], float (&best)[R], int (&arg)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) { best[r] = INFINITY; arg[r] = 0; }
+    int p = 0;
+    for (; p + 4 <= ny; p += 4) {
+        const float4* v = reinterpret_cast<const float4*>(s_y + p * 3);
+        const float4 a = v[0], b = v[1], c = v[2];
+        const float y[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float d = chamfer_pair_sq(q[r][0], q[r][1], q[r][2], y + k * 3);
+                if (ARG) {
+                    if (d < best[r]) { best[r] = d; arg[r] = p + k; }
+                } else {
+                    best[r] = fminf(best[r], d);
+                }
+            }
+        }
+    }
+    for (; p < ny; ++p) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float d = chamfer_pair_sq(q[r][0], q[r][1], q[r][2], s_y + p * 3);
+            if (ARG) {
+                if (d < best[r]) { best[r] = d; arg[r] = p; }
+            } else {
+                best[r] = fminf(best[r], d);
+            }
+        }
+    }
+}
+
+// max over the 64 lanes of NON-NEGATIVE values (a lane without a DPP source reads 0), returned in every lane
+__device__ __forceinline__ float cm_wave_max(float v) {
+    v = fmaxf(v, dpp_move<0xB1>(v));
+    v = fmaxf(v, dpp_move<0x4E>(v));
+    v = fmaxf(v, dpp_move<0x141>(v));
+    v = fmaxf(v, dpp_move<0x140>(v));
+    v = fmaxf(v, dpp_move<0x142, 0xA>(v));
+    v = fmaxf(v, dpp_move<0x143, 0xC>(v));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// one term of a gradient: w * t(x, y) added to g.  Squared form: t = 2 (x - y); square-rooted form: t = (x - y) / |x - y| with the
+// hardware reciprocal square root of d2 = |x - y|^2, and exactly nothing where d2 is 0 (the deviation of dpd_chamfer_sqrt_bwd).
+template <int FORM>
+__device__ __forceinline__ void cm_term(float w, float d2, float xx, float xy, float xz, const float* __restrict__ y, float (&g)[3]) {
+    float s;
+    if (FORM == 0) {
+        s = 2.f;
+    } else {
+        if (!(d2 > 0.f)) return;
+        s = rsqrtf(d2);   // v_rsq_f32, with the input scaled where d2 is subnormal
+    }
+    g[0] += w * (s * (xx - y[0]));
+    g[1] += w * (s * (xy - y[1]));
+    g[2] += w * (s * (xz - y[2]));
+}
+
 }  // namespace dpd

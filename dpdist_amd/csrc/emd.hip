@@ -21,23 +21,11 @@
 // The four partial sums of a point are combined through LDS as (p0 + p1) + (p2 + p3).  Every sum has one order, there are no atomics, and
 // every output element has one writer per launch: two runs give identical bits.
 // exp goes through v_exp_f32 (base 2) with log2(e) folded into the level on the host; 1 / sqrt through v_rsq_f32.
-// The scan of a wave and the finish of an owner are written once, in emd_int.h: the all-pairs kernel of emd_matrix.hip calls them too.
+// The scan of a wave and the finish of an owner are written once, in emd_int.h: the all-pairs kernel of emd_matrix.hip calls them too;
+// so is what a workgroup does for one owner tile of one pair (emd_row_tile, emd_col_tile), which the counted kernels of emd_pairs.hip share.
 #include "emd_int.h"
 
 namespace dpd {
-
-struct EmdWs {            // carved from the caller's workspace, floats
-    float* remainL;       // [B,n]
-    float* ratioL;        // [B,n]
-    float* costk;         // [B,n]  sum_l match[l][k] sqrt(d^2)
-    float* remainR;       // [B,m]
-    float* ratioR;        // [B,m]
-};
-
-// stage `cnt` points of cloud p [cnt,3] with their vector entry v (or the constant c when v is NULL) as float4 {x,y,z,v}
-__device__ __forceinline__ void emd_stage(float4* s, const float* __restrict__ p, const float* __restrict__ v, float c, int cnt) {
-    for (int i = threadIdx.x; i < cnt; i += kEmdThreads) s[i] = make_float4(p[i * 3], p[i * 3 + 1], p[i * 3 + 2], v ? v[i] : c);
-}
 
 // Row pass.  W: step 3 of the level whose base-2 exponent scale is lw (match += w, remainL -= sum w, cost and grad1);
 // R: step 1 of the level with scale lr (ratioL).  first: no level has run yet (remainL / remainR are their initial constants, the
@@ -49,35 +37,10 @@ __global__ __launch_bounds__(kEmdThreads) void emd_row_kernel(const float* __res
     __shared__ float4 s2[kEmdMax];                       // {x2, y2, z2, remainR[l]}
     __shared__ float sR[W ? kEmdMax : 1];                // ratioR[l]
     __shared__ float red[kEmdWaves][6][kWave];
-    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const float* p2 = xyz2 + (size_t)b * m * 3;
-    const float initL = (float)max(n, m) / (float)n, initR = (float)max(n, m) / (float)m;
-    // step 1 of the first level reads the initial remainR; later ones read what the column pass left
-    emd_stage(s2, p2, (first && !W) ? nullptr : ws.remainR + (size_t)b * m, initR, m);
-    if (W)
-        for (int i = threadIdx.x; i < m; i += kEmdThreads) sR[i] = ws.ratioR[(size_t)b * m + i];
-    __syncthreads();
-
-    const int k0 = blockIdx.y * kWave + lane;
-    const int k = min(k0, n - 1);                        // a tail lane recomputes the last point and stores nothing
-    const float* p1 = xyz1 + ((size_t)b * n + k) * 3;
-    const float x = p1[0], y = p1[1], z = p1[2];
-    const float rl = W ? ws.ratioL[(size_t)b * n + k] : 0.f;
-    float* mrow = match ? match + (size_t)b * m * n + k : nullptr;
-
-    const int per = (m + kEmdWaves - 1) / kEmdWaves;
-    const int l0 = wave * per, l1 = min(m, l0 + per);
-    float acc[6];
-    emd_row_scan<W, R>(s2, sR, l0, l1, x, y, z, rl, lw, lr, k0 < n ? mrow : nullptr, n, first, acc);
-#pragma unroll
-    for (int c = 0; c < 6; ++c) red[wave][c][lane] = acc[c];
-    __syncthreads();
-    if (wave != 0 || k0 >= n) return;
-    float t[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
-    const size_t ik = (size_t)b * n + k;
-    emd_row_finish<W, R>(t, first, initL, ws.remainL[ik], ws.costk[ik], ws.ratioL[ik], grad1 ? grad1 + ik * 3 : nullptr, gs);
+    const size_t b = blockIdx.x, bn = b * n, bm = b * m;
+    const EmdVec v{ws.remainL + bn, ws.ratioL + bn, ws.costk + bn, ws.remainR + bm, ws.ratioR + bm};
+    emd_row_tile<W, R>(s2, sR, red, xyz1 + bn * 3, xyz2 + bm * 3, n, m, blockIdx.y, lw, lr, first, v, grad1 ? grad1 + bn * 3 : nullptr,
+                       match ? match + bm * n : nullptr, gs);
 }
 
 // Column pass: step 2 of the level with base-2 exponent scale lv, and grad2's share of that level.
@@ -86,28 +49,9 @@ __global__ __launch_bounds__(kEmdThreads) void emd_col_kernel(const float* __res
                                                               float lv, int first, EmdWs ws, float* __restrict__ grad2, float gs) {
     __shared__ float4 s1[kEmdMax];                       // {x1, y1, z1, ratioL[k]}
     __shared__ float red[kEmdWaves][4][kWave];
-    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    emd_stage(s1, xyz1 + (size_t)b * n * 3, ws.ratioL + (size_t)b * n, 0.f, n);
-    __syncthreads();
-
-    const int l0 = blockIdx.y * kWave + lane;
-    const int l = min(l0, m - 1);
-    const float* p2 = xyz2 + ((size_t)b * m + l) * 3;
-    const float x = p2[0], y = p2[1], z = p2[2];
-
-    const int per = (n + kEmdWaves - 1) / kEmdWaves;
-    const int k0 = wave * per, k1 = min(n, k0 + per);
-    float acc[4];
-    emd_col_scan<G>(s1, k0, k1, x, y, z, lv, acc);
-    red[wave][0][lane] = acc[0];
-    if (G) red[wave][1][lane] = acc[1], red[wave][2][lane] = acc[2], red[wave][3][lane] = acc[3];
-    __syncthreads();
-    if (wave != 0 || l0 >= m) return;
-    const size_t il = (size_t)b * m + l;
-    float t[4] = {};
-#pragma unroll
-    for (int c = 0; c < (G ? 4 : 1); ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
-    emd_col_finish<G>(t, first, (float)max(n, m) / (float)m, ws.remainR[il], ws.ratioR[il], G ? grad2 + il * 3 : nullptr, gs);
+    const size_t b = blockIdx.x, bn = b * n, bm = b * m;
+    const EmdVec v{ws.remainL + bn, ws.ratioL + bn, ws.costk + bn, ws.remainR + bm, ws.ratioR + bm};
+    emd_col_tile<G>(s1, red, xyz1 + bn * 3, xyz2 + bm * 3, n, m, blockIdx.y, lv, first, v, G ? grad2 + bm * 3 : nullptr, gs);
 }
 
 // cost[b] = sum_k costk[b][k] and loss = mean_b cost[b] / n, one workgroup, fixed order

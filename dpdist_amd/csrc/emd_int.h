@@ -122,4 +122,97 @@ __device__ __forceinline__ void emd_col_finish(const float (&t)[4], int first, f
     }
 }
 
+// the count of cloud c of a ragged set (include/dpdist_capi.h, RAGGED block): clamped into [1, width]; counts = NULL: the set is full
+__device__ __forceinline__ int em_count(const int32_t* __restrict__ counts, int c, int width) {
+    if (!counts) return width;
+    const int n = counts[c];
+    return n < 1 ? 1 : (n > width ? width : n);
+}
+
+// ---- a pass as a launch: what one 256-thread workgroup does for one owner tile (64 points) of ONE pair.  The paired kernels of emd.hip
+// call these with the pair's slices of a dense batch, the counted kernels of emd_pairs.hip with the pair's own n, m and padded strides.
+
+struct EmdWs {            // the vectors of a batch, carved from the caller's workspace, floats
+    float* remainL;       // [B,n]
+    float* ratioL;        // [B,n]
+    float* costk;         // [B,n]  sum_l match[l][k] sqrt(d^2)
+    float* remainR;       // [B,m]
+    float* ratioR;        // [B,m]
+};
+using EmdVec = EmdWs;     // the same five pointers advanced to one pair
+
+// stage `cnt` points of cloud p [cnt,3] with their vector entry v (or the constant c when v is NULL) as float4 {x,y,z,v}
+__device__ __forceinline__ void emd_stage(float4* s, const float* __restrict__ p, const float* __restrict__ v, float c, int cnt) {
+    for (int i = threadIdx.x; i < cnt; i += kEmdThreads) s[i] = make_float4(p[i * 3], p[i * 3 + 1], p[i * 3 + 2], v ? v[i] : c);
+}
+
+// Row pass of owner tile `tile` of the pair p1 [n,3], p2 [m,3].  s2 [m] float4, sR [m] floats (W only), red: LDS of the workgroup.
+// Lane i of EVERY wave owns point 64 tile + i; wave v scans quarter v of the other cloud.  grad1 / match: the pair's, or NULL.
+template <bool W, bool R>
+__device__ __forceinline__ void emd_row_tile(float4* __restrict__ s2, float* __restrict__ sR, float (*__restrict__ red)[6][kWave],
+                                             const float* __restrict__ p1, const float* __restrict__ p2, int n, int m, int tile, float lw,
+                                             float lr, int first, const EmdVec& v, float* __restrict__ grad1, float* __restrict__ match,
+                                             float gs) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const float initL = (float)max(n, m) / (float)n, initR = (float)max(n, m) / (float)m;
+    // step 1 of the first level reads the initial remainR; later ones read what the column pass left
+    emd_stage(s2, p2, (first && !W) ? nullptr : v.remainR, initR, m);
+    if (W)
+        for (int i = threadIdx.x; i < m; i += kEmdThreads) sR[i] = v.ratioR[i];
+    __syncthreads();
+
+    const int k0 = tile * kWave + lane;
+    const int k = min(k0, n - 1);                        // a tail lane recomputes the last point and stores nothing
+    const float x = p1[k * 3], y = p1[k * 3 + 1], z = p1[k * 3 + 2];
+    const float rl = W ? v.ratioL[k] : 0.f;
+    float* mrow = match ? match + k : nullptr;
+
+    const int per = (m + kEmdWaves - 1) / kEmdWaves;
+    const int l0 = wave * per, l1 = min(m, l0 + per);
+    float acc[6];
+    emd_row_scan<W, R>(s2, sR, l0, l1, x, y, z, rl, lw, lr, k0 < n ? mrow : nullptr, n, first, acc);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) red[wave][c][lane] = acc[c];
+    __syncthreads();
+    if (wave != 0 || k0 >= n) return;
+    float t[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
+    emd_row_finish<W, R>(t, first, initL, v.remainL[k], v.costk[k], v.ratioL[k], grad1 ? grad1 + k * 3 : nullptr, gs);
+}
+
+// Column pass of owner tile `tile` of the pair: step 2 of the level with scale lv, and grad2's share of that level (G; grad2: the pair's).
+template <bool G>
+__device__ __forceinline__ void emd_col_tile(float4* __restrict__ s1, float (*__restrict__ red)[4][kWave], const float* __restrict__ p1,
+                                             const float* __restrict__ p2, int n, int m, int tile, float lv, int first, const EmdVec& v,
+                                             float* __restrict__ grad2, float gs) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    emd_stage(s1, p1, v.ratioL, 0.f, n);
+    __syncthreads();
+
+    const int l0 = tile * kWave + lane;
+    const int l = min(l0, m - 1);
+    const float x = p2[l * 3], y = p2[l * 3 + 1], z = p2[l * 3 + 2];
+
+    const int per = (n + kEmdWaves - 1) / kEmdWaves;
+    const int k0 = wave * per, k1 = min(n, k0 + per);
+    float acc[4];
+    emd_col_scan<G>(s1, k0, k1, x, y, z, lv, acc);
+    red[wave][0][lane] = acc[0];
+    if (G) red[wave][1][lane] = acc[1], red[wave][2][lane] = acc[2], red[wave][3][lane] = acc[3];
+    __syncthreads();
+    if (wave != 0 || l0 >= m) return;
+    float t[4] = {};
+#pragma unroll
+    for (int c = 0; c < (G ? 4 : 1); ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
+    emd_col_finish<G>(t, first, (float)max(n, m) / (float)m, v.remainR[l], v.ratioR[l], G ? grad2 + l * 3 : nullptr, gs);
+}
+
+// ---- the pairs (b, b) of two sets through the one-workgroup-per-pair kernel of emd_matrix.hip (host side; emd_pairs.hip calls them).
+// cost / dist [P] (either may be NULL); g1 [P,Wa,3] / g2 [P,Wb,3]: the unscaled d cost / d xyz of each pair's real rows (either may be NULL).
+int em_diag_fwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, float* cost,
+                float* dist, hipStream_t s);
+int em_diag_grads(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, float* g1, float* g2,
+                  hipStream_t s);
+
 }  // namespace dpd

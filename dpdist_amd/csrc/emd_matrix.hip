@@ -18,6 +18,9 @@
 // read and written by its owner lane alone).  A second kernel folds them: dA[i,k] = sum_j (W[i,j] / n_i) g1(i,j)[k], j ascending, and
 // dB[j,l] = sum_i (W[i,j] / n_i) g2(i,j)[l], i ascending, a left fold from +0.0 (or from dB's value: accumulate_dB).  No atomics, one
 // writer per element, padding never read, rows at or beyond a count written +0.0.
+//
+// The same kernel serves the pairs (b, b) of two sets of equal length (em_diag_fwd / em_diag_grads below: the one-launch form of
+// dpd_emd_pairs_fwd / _bwd, emd_pairs.hip) through its pair map: diag != 0 takes p -> (p, p) instead of p -> (p / Cb, p % Cb).
 #include "emd_int.h"
 
 #ifndef DPD_EMD_WIDE_FROM
@@ -28,12 +31,6 @@ namespace dpd {
 
 constexpr int kEmMaxGrid = 1 << 20;   // workgroups per launch; the kernels stride over their pairs beyond it
 constexpr int kEmRed = kEmdWaves * 6 * kWave;   // floats of partial sums per group
-
-__device__ __forceinline__ int em_count(const int32_t* __restrict__ counts, int c, int width) {
-    if (!counts) return width;
-    const int n = counts[c];
-    return n < 1 ? 1 : (n > width ? width : n);
-}
 
 // Row pass of one pair over its owner tiles; the barrier that ends the last tile ends the pass.
 template <int GROUPS, bool W, bool R, bool COST, bool G1>
@@ -112,12 +109,13 @@ __device__ __forceinline__ void em_col_pass(const float4* __restrict__ s1, float
 }
 
 // COST: the forward (cost / dist); G1 / G2: the backward's per-pair gradients into gw1 [pairs,Na,3] / gw2 [pairs,Nb,3].
+// diag: the pair map p -> (p, p) over Ca = Cb clouds (the one-launch form of dpd_emd_pairs_fwd / _bwd) instead of p -> (p / Cb, p % Cb).
 template <int GROUPS, bool COST, bool G1, bool G2>
 __global__ __launch_bounds__(GROUPS* kEmdThreads) void emd_matrix_kernel(const float* __restrict__ A, const int32_t* __restrict__ countsA, int Ca,
                                                                         int Na, const float* __restrict__ B,
                                                                         const int32_t* __restrict__ countsB, int Cb, int Nb, EmdLevels lv,
                                                                         float* __restrict__ cost, float* __restrict__ dist,
-                                                                        float* __restrict__ gw1, float* __restrict__ gw2) {
+                                                                        float* __restrict__ gw1, float* __restrict__ gw2, int diag) {
     extern __shared__ __align__(16) float4 em_lds[];
     float4* s1 = em_lds;                                   // [Na] {x1, y1, z1, ratioL}
     float4* s2 = s1 + Na;                                  // [Nb] {x2, y2, z2, remainR}
@@ -127,9 +125,9 @@ __global__ __launch_bounds__(GROUPS* kEmdThreads) void emd_matrix_kernel(const f
     float* red = ratioR + Nb;                              // [GROUPS][4][6][64]
     float* red4 = red + GROUPS * kEmRed;                   // [4]
     const int nthr = GROUPS * kEmdThreads;
-    const long long pairs = (long long)Ca * Cb;
+    const long long pairs = diag ? (long long)Ca : (long long)Ca * Cb;
     for (long long p = blockIdx.x; p < pairs; p += gridDim.x) {   // 64-bit: the last stride may pass 2^31
-        const int i = (int)(p / Cb), j = (int)(p % Cb);
+        const int i = diag ? (int)p : (int)(p / Cb), j = diag ? (int)p : (int)(p % Cb);
         const int n = em_count(countsA, i, Na), m = em_count(countsB, j, Nb);
         const float* a = A + (size_t)i * Na * 3;
         const float* b = B + (size_t)j * Nb * 3;
@@ -214,24 +212,36 @@ static int em_check_dims(int Ca, int Na, int Cb, int Nb) {
 
 template <int GROUPS, bool COST, bool G1, bool G2>
 static int em_launch(const float* A, const int32_t* countsA, int Ca, int Na, const float* B, const int32_t* countsB, int Cb, int Nb, float* cost,
-                     float* dist, float* gw1, float* gw2, hipStream_t s) {
+                     float* dist, float* gw1, float* gw2, int diag, hipStream_t s) {
     auto kern = emd_matrix_kernel<GROUPS, COST, G1, G2>;
     const size_t lds = (size_t)(Na + Nb) * sizeof(float4) + ((size_t)2 * Na + Nb + GROUPS * kEmRed + 4) * sizeof(float);
     static LdsOptIn lds_opt;   // one per template instantiation
     if (int rc = ensure_dyn_lds(lds_opt, (const void*)kern, lds)) return rc;
-    const long long pairs = (long long)Ca * Cb;
+    const long long pairs = diag ? (long long)Ca : (long long)Ca * Cb;
     DPD_LAUNCH(kern, dim3(pairs < kEmMaxGrid ? (int)pairs : kEmMaxGrid), dim3(GROUPS * kEmdThreads), lds, s, A, countsA, Ca, Na, B, countsB, Cb,
-               Nb, emd_levels(), cost, dist, gw1, gw2);
+               Nb, emd_levels(), cost, dist, gw1, gw2, diag);
     DPD_CHECK_LAUNCH();
     return 0;
 }
 
 template <bool COST, bool G1, bool G2>
 static int em_pairs(const float* A, const int32_t* countsA, int Ca, int Na, const float* B, const int32_t* countsB, int Cb, int Nb, float* cost,
-                    float* dist, float* gw1, float* gw2, hipStream_t s) {
+                    float* dist, float* gw1, float* gw2, hipStream_t s, int diag = 0) {
     if ((Na > Nb ? Na : Nb) >= DPD_EMD_WIDE_FROM)
-        return em_launch<4, COST, G1, G2>(A, countsA, Ca, Na, B, countsB, Cb, Nb, cost, dist, gw1, gw2, s);
-    return em_launch<1, COST, G1, G2>(A, countsA, Ca, Na, B, countsB, Cb, Nb, cost, dist, gw1, gw2, s);
+        return em_launch<4, COST, G1, G2>(A, countsA, Ca, Na, B, countsB, Cb, Nb, cost, dist, gw1, gw2, diag, s);
+    return em_launch<1, COST, G1, G2>(A, countsA, Ca, Na, B, countsB, Cb, Nb, cost, dist, gw1, gw2, diag, s);
+}
+
+int em_diag_fwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, float* cost,
+                float* dist, hipStream_t s) {
+    return em_pairs<true, false, false>(A, countsA, P, Wa, B, countsB, P, Wb, cost, dist, nullptr, nullptr, s, 1);
+}
+
+int em_diag_grads(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, float* g1, float* g2,
+                  hipStream_t s) {
+    if (g1 && g2) return em_pairs<false, true, true>(A, countsA, P, Wa, B, countsB, P, Wb, nullptr, nullptr, g1, g2, s, 1);
+    if (g1) return em_pairs<false, true, false>(A, countsA, P, Wa, B, countsB, P, Wb, nullptr, nullptr, g1, g2, s, 1);
+    return em_pairs<false, false, true>(A, countsA, P, Wa, B, countsB, P, Wb, nullptr, nullptr, g1, g2, s, 1);
 }
 
 }  // namespace dpd

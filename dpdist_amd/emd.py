@@ -10,6 +10,10 @@ The match carries no gradient, like the op's.
 All pairs of two sets of clouds: emd_matrix / EMDMatrix (csrc/emd_matrix.hip: dpd_emd_matrix_fwd / _bwd, one workgroup per pair), in the
 conventions of dpdist_matrix and chamfer_matrix.  D[i, j] = earth_mover(A_i, B_j), bit for bit; nothing of size [Ca, Cb, N] exists in the
 forward, and the backward's per-pair gradients pass through a workspace bounded by MAX_WS_BYTES.  There is no fallback to expanded pairs.
+
+The pairs (A_b, B_b) alone, ragged: emd_pairs / EMDPairs (csrc/emd_pairs.hip: dpd_emd_pairs_fwd / _bwd), in the conventions of dpdist_pairs.
+D[b] = earth_mover(A_b, B_b), bit for bit; the library runs a pair per workgroup in one launch at small widths and a launch per pass with
+a workgroup per 64-point tile at large ones.
 """
 import torch
 
@@ -195,3 +199,85 @@ class EMDMatrix(torch.nn.Module):
             with torch.no_grad():
                 return _matrix_forward(A, B, cA, cB)
         return _EMDMatrixFn.apply(cloudsA, cloudsB, cA, cB)
+
+
+def _pairs_prepare(cloudsA, cloudsB, countsA, countsB):
+    from .baselines import _prepare
+    return _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS, pairs=True)
+
+
+def _pairs_workspace(lib, A, B):
+    return torch.empty(max(1, lib.dpd_emd_pairs_workspace_bytes(A.shape[0], A.shape[1], B.shape[1])), device=A.device, dtype=torch.uint8)
+
+
+def _pairs_forward(A, B, cA, cB, form=0):
+    """D [P] of prepared sets; form: 0 the library's choice, 1 one launch, 2 per pass (the same bits)"""
+    lib = L.load()
+    D = torch.empty(A.shape[0], device=A.device, dtype=torch.float32)
+    with torch.cuda.device(A.device):
+        ws = _pairs_workspace(lib, A, B)
+        _matrix_check(lib.dpd_emd_pairs_fwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], form, None, L.ptr(D),
+                                            L.ptr(ws), ws.numel(), L.cur_stream()), "dpd_emd_pairs_fwd")
+    return D
+
+
+def _pairs_backward(A, B, cA, cB, W, needA, needB, form=0):
+    """(dA | None, dB | None) under the upstream W [P] of D"""
+    lib = L.load()
+    dA = torch.empty_like(A) if needA else None
+    dB = torch.empty_like(B) if needB else None
+    with torch.cuda.device(A.device):
+        ws = _pairs_workspace(lib, A, B)
+        _matrix_check(lib.dpd_emd_pairs_bwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], form, L.ptr(W),
+                                            L.ptr(dA), L.ptr(dB), L.ptr(ws), ws.numel(), L.cur_stream()), "dpd_emd_pairs_bwd")
+    return dA, dB
+
+
+@torch.no_grad()
+def emd_pairs(cloudsA, cloudsB, *, countsA=None, countsB=None):
+    """cloudsA [P,N,3], cloudsB [P,M,3] -> D [P], D[b] = earth_mover(A_b, B_b): the cost of the approximate matching of the pair over the
+    number of points of A_b, bit for bit the paired entry's value and emd_matrix's on the pair alone.  The two sets may have different
+    widths.  countsA / countsB (keywords): ragged sets as in dpdist_pairs -- a sequence or CPU integer tensor is checked (one count per
+    cloud, each in [1, width]) and copied once, an int32 device tensor is used as it is and clamped by the kernels; padding is never
+    read.  ValueError for sets of different lengths, CPU tensors, a dtype other than float32, sets on two devices, bad counts and more
+    than 2048 points per cloud -- before anything is launched.  Forward only: EMDPairs is differentiable."""
+    return _pairs_forward(*_pairs_prepare(cloudsA, cloudsB, countsA, countsB))
+
+
+class _EMDPairsFn(torch.autograd.Function):
+    """D [P] of the pairs of two cloud sets as one autograd node"""
+
+    @staticmethod
+    def forward(ctx, A, B, cA, cB):
+        ctx.counts = (cA, cB)
+        ctx.set_materialize_grads(False)
+        a, b = A.detach().contiguous(), B.detach().contiguous()
+        ctx.save_for_backward(a, b)                                    # the two sets only: the match is recomputed
+        return _pairs_forward(a, b, cA, cB)
+
+    @staticmethod
+    def backward(ctx, gD):
+        cA, cB = ctx.counts
+        A, B = ctx.saved_tensors
+        needA, needB = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if gD is None or not (needA or needB):
+            return (None,) * 4
+        with torch.no_grad():
+            dA, dB = _pairs_backward(A, B, cA, cB, gD.to(torch.float32).contiguous(), needA, needB)
+        return dA, dB, None, None
+
+
+class EMDPairs(torch.nn.Module):
+    """emd_pairs as a differentiable module: gradients to cloudsA and cloudsB under any upstream gradient of D [P].  One autograd node
+    over the library, on the current stream, without a host synchronisation; the forward values are bit for bit those of emd_pairs and
+    the gradients those of EMDMatrix on each pair alone.  The match carries no gradient (as in earth_mover); the node saves the two sets
+    only and the backward recomputes the match.  The gradient at a padded point is exactly +0.0; a set that needs no gradient gets None
+    and its route is skipped.  Arguments and errors as emd_pairs."""
+
+    def forward(self, cloudsA, cloudsB, *, countsA=None, countsB=None):
+        want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (cloudsA, cloudsB))
+        A, B, cA, cB = _pairs_prepare(cloudsA, cloudsB, countsA, countsB)
+        if not want_grad:
+            with torch.no_grad():
+                return _pairs_forward(A, B, cA, cB)
+        return _EMDPairsFn.apply(cloudsA, cloudsB, cA, cB)

@@ -156,6 +156,12 @@ SIGNATURES = {
     "dpd_emd_matrix_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
     "dpd_emd_matrix_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3 +
                            [c_int, c_void_p, c_size_t, c_void_p]),
+    # the baselines per pair, ragged (baselines.py, emd.py): A, countsA, Wa, B, countsB, Wb, P, ...
+    "dpd_chamfer_pairs_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 8),
+    "dpd_chamfer_pairs_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 7),
+    "dpd_emd_pairs_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dpd_emd_pairs_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "dpd_emd_pairs_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "dpd_pose_apply_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dpd_pose_apply_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "dpd_pose_refine_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -747,6 +747,58 @@ int dpd_emd_matrix_bwd(const float* A, const int32_t* countsA, int Ca, int Na, c
                        const float* W, float* dA, float* dB, int accumulate_dB, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The baselines PER PAIR, for ragged batches: Chamfer / Hausdorff and the Earth Mover's distance of the pairs (A_b, B_b), b < P, of two
+ * sets A [P,Wa,3] and B [P,Wb,3] (dpdist_amd/baselines.py: chamfer_pairs, hausdorff_pairs, ChamferPairs; dpdist_amd/emd.py: emd_pairs,
+ * EMDPairs; csrc/chamfer_pairs.hip, csrc/emd_pairs.hip).  The definitions are those of the two matrix blocks above restricted to the
+ * pairs (b, b); the launch shape is the one for few, large pairs (a pair is spread over workgroups).  countsA / countsB [P]: per-cloud
+ * counts (int32, DEVICE memory, the rules of the RAGGED block: never read by the host, clamped into [1, width] by the kernels, the
+ * padding is never read); NULL = the set is full.  With na = countsA[b], nb = countsB[b]:
+ *
+ * dpd_chamfer_pairs_fwd.  A is the surface of the AB direction:
+ *   min_ab[b,n] = min_{p < na} d2(B[b,n], A[b,p]), arg_ab[b,n] = the lowest p that attains it      [P,Wb], n < nb
+ *   min_ba[b,k] = min_{p < nb} d2(A[b,k], B[b,p]), arg_ba[b,k] likewise                            [P,Wa], k < na
+ *   mean_sq, mean_rt, max_sq: [2,P], row 0 the AB direction (over the nb queries of B_b), row 1 BA -- the matrix block's formulas.
+ *   The four min / arg arrays are REQUIRED (the means are reduced from them and the backward reads the argmins); their entries at or
+ *   beyond a count are NOT written.  The three [2,P] outputs are each optional; with none of them only min / arg are produced.
+ *   Every value is bit for bit dpd_chamfer_matrix_fwd's on that pair alone (Cs = Cq = 1, the same counts): a second launch reduces the
+ *   minima in that kernel's order (lane t sums the queries t, t + 256, ... ascending, wave_sum's tree, ((w0 + w1) + (w2 + w3))).
+ * dpd_chamfer_pairs_bwd.  G_ab, G_ba [P]: the upstreams of the two directed means of `form` (0: mean_sq, 1: mean_rt; else DPD_E_DIM);
+ *   either may be NULL (that direction carries no gradient and its routes are skipped; both: DPD_E_NULL).  arg_ab / arg_ba: the forward's.
+ *   dA[b,k] = (surface route of AB at A[b,k]) + (query route of BA at A[b,k]),  dB[b,n] = (query route of AB) + (surface route of BA),
+ *   each route dpd_chamfer_matrix_bwd's formula at Cs = Cq = 1: w = G[b] / n_query (one fp32 division), terms w * (s * (x - y)) with
+ *   s = 2 or the hardware reciprocal square root of d2 (exactly nothing where d2 is 0), the surface route in ascending query order.  The
+ *   bits are those of the sum of that entry's two calls on the pair alone.  dA [P,Wa,3], dB [P,Wb,3] are overwritten by ONE kernel with
+ *   one writer per element; either may be NULL (both: DPD_E_NULL); rows at or beyond a count are written +0.0.
+ *
+ * dpd_emd_pairs_fwd.  cost[b] = dpd_emd_fwd's cost[0] of xyz1 = A_b[:na], xyz2 = B_b[:nb] at B = 1, bit for bit; dist[b] = cost[b] / na
+ *   (each [P]; either may be NULL, both: DPD_E_NULL).
+ * dpd_emd_pairs_bwd.  W [P]: the upstream of dist.  The match is a constant and is recomputed.  With g1(b), g2(b) the definition's
+ *   d cost / d xyz1, d cost / d xyz2 of the pair:  dA[b,k] = +0.0 + (W[b] / na) g1(b)[k],  dB[b,l] = +0.0 + (W[b] / na) g2(b)[l]
+ *   -- the bits of dpd_emd_matrix_bwd on the pair alone.  Either of dA, dB may be NULL (both: DPD_E_NULL), a skipped side is not
+ *   computed; rows at or beyond a count are written +0.0.
+ *   form: 0 = the library chooses by the padded widths, 1 = one launch (one workgroup per pair, the all-pairs kernel over the pair map
+ *   p -> (p, p)), 2 = per pass (the counted twins of dpd_emd_fwd's kernels: a workgroup per 64-point owner tile of a pair, 22 launches).
+ *   Both forms run the same pass bodies and give the same bits.  ws: dpd_emd_pairs_workspace_bytes(P, Wa, Wb) = P (3 Wa + 2 Wb) floats
+ *   of device scratch (the vectors of form 2; required by every form, since form 0 does not tell; 0 for a refused shape).
+ *
+ * Every sum has one fixed order that depends on the pair's two counts only, and there are no atomics: two calls give the same bits, and
+ * the padded widths, the padding and the other pairs change no bit.  No allocation, stream-ordered; P is not bound by a grid dimension.
+ * Refusals, before anything is launched and with the outputs untouched: DPD_E_NULL for a missing set, min / arg array, upstream or all
+ * outputs; DPD_E_DIM for P < 1 or a bad form; DPD_E_UNSUPPORTED unless 1 <= Wa, Wb <= 4096 (Chamfer) or DPD_EMD_MAX_POINTS (EMD);
+ * DPD_E_WORKSPACE for a missing or too small workspace.                                                                               */
+int dpd_chamfer_pairs_fwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P,
+                          float* min_ab, int32_t* arg_ab, float* min_ba, int32_t* arg_ba, float* mean_sq, float* mean_rt, float* max_sq,
+                          void* stream);
+int dpd_chamfer_pairs_bwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, int form,
+                          const int32_t* arg_ab, const int32_t* arg_ba, const float* G_ab, const float* G_ba, float* dA, float* dB,
+                          void* stream);
+size_t dpd_emd_pairs_workspace_bytes(int P, int Wa, int Wb);
+int dpd_emd_pairs_fwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, int form,
+                      float* cost, float* dist, void* ws, size_t ws_bytes, void* stream);
+int dpd_emd_pairs_bwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, int form,
+                      const float* W, float* dA, float* dB, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pose algebra of the iterative registration that consumes DPDist as its loss (row f2; csrc/pose.hip): ONE launch for the chain of
  * ~115 element-wise ops the reference runs per refinement loop.  pred [B,7] = the pose network's raw output (t, angle, axis).
  *   pose   [B,7]   (optional) quat_normalize(pred): (tanh(t) 0.1, cos(a/2), axis sin(a/2)), |a| <= lim_rot_deg
