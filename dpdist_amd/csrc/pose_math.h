@@ -1,6 +1,7 @@
-// Pose algebra shared by the kernels that compose the registration's transforms (pose.hip: the refinement loop; regtest.hip: the
-// per-iteration trace of the test protocol).  One definition, so that every kernel produces the same fp32 bits for the same raw
-// network output (the build has -ffp-contract=off: an expression is the same roundings wherever it is inlined).
+// Pose algebra shared by the kernels that compose the registration's transforms (pose.hip: the apply kernel, the last loop of a
+// refinement; pose_point.hip: the PoseMove prologue of the shared MLP, every other loop; regtest.hip: the per-iteration trace of the
+// test protocol).  One definition, so that every kernel produces the same fp32 bits for the same raw network output (the build has
+// -ffp-contract=off: an expression is the same roundings wherever it is inlined).
 #pragma once
 #include "common.h"
 
@@ -46,6 +47,39 @@ __device__ __forceinline__ float quat_norm_dev(const float q[4]) { return sqrtf(
 __device__ __forceinline__ float pose_compose_entry(const float R[3][3], const float t[3], const float Tc[4], int i) {
     if (i < 3) return ((R[i][0] * Tc[0] + R[i][1] * Tc[1]) + R[i][2] * Tc[2]) + t[i] * Tc[3];
     return Tc[3];
+}
+
+// Column j of T_in[b] for the composition above; T_in == nullptr: of the identity (the first loop of a refinement)
+__device__ __forceinline__ void pose_load_T_col(const float* __restrict__ T_in, int b, int j, float Tc[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Tc[r] = T_in ? T_in[(size_t)b * 16 + r * 4 + j] : (r == j ? 1.f : 0.f);
+}
+
+// The head's last layer on ONE wave (models/ipcr_model.py:284): pr[j] = W4[j, :] . h3[b, :] + b4[j], j < 7, in every lane; K4 % 4 == 0.
+// Lane l takes the float4s at k = 4 l, 4 l + 256, ...; the lanes' sums meet in wave_sum's fixed tree.  (The row is indexed inside the loop:
+// handed over as a row pointer it cost pose_apply_fwd_kernel six VGPRs and a wave of occupancy.)
+__device__ __forceinline__ void pose_fc4_wave(const float* __restrict__ h3, int b, const float* __restrict__ W4, const float* __restrict__ b4, int K4,
+                                              int lane, float pr[7]) {
+    float bb[7], acc[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) { bb[j] = b4[j]; acc[j] = 0.f; }
+    for (int k = lane * 4; k < K4; k += 256) {
+        const float4 x = *reinterpret_cast<const float4*>(h3 + (size_t)b * K4 + k);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const float4 w = *reinterpret_cast<const float4*>(W4 + (size_t)j * K4 + k);
+            acc[j] = fmaf(x.x, w.x, fmaf(x.y, w.y, fmaf(x.z, w.z, fmaf(x.w, w.w, acc[j]))));
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) pr[j] = wave_sum(acc[j]) + bb[j];
+}
+
+// One point moved: o = R p + t (helper.py:539-570: data R^T + t, row vectors)
+__device__ __forceinline__ void pose_move_point(const float R[3][3], const float t[3], float x, float y, float z, float o[3]) {
+    o[0] = (x * R[0][0] + y * R[0][1] + z * R[0][2]) + t[0];
+    o[1] = (x * R[1][0] + y * R[1][1] + z * R[1][2]) + t[1];
+    o[2] = (x * R[2][0] + y * R[2][1] + z * R[2][2]) + t[2];
 }
 
 }  // namespace dpd

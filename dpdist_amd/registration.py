@@ -47,7 +47,7 @@ def quat_normalize(pred, rot_lim=45.0):
 
 
 NATIVE_TRAIN_MAX_POINTS = 2048      # dpd_pose_point_fwd_train / _bwd (include/dpdist_capi.h); the reference's MAX_NUM_POINT
-# (in, out) of the Linear layers of THE pose network csrc/pose.hip implements (models/ipcr_model.py:198-233,273-284 as PoseNet builds it)
+# (in, out) of the Linear layers of THE pose network csrc/pose*.hip implements (models/ipcr_model.py:198-233,273-284 as PoseNet builds it)
 POINT_WIDTHS = [(3, 64), (64, 64), (64, 64), (64, 128), (128, 1024)]
 HEAD_WIDTHS = [(2048, 1024), (1024, 512), (512, 256), (256, 7)]
 
@@ -67,12 +67,12 @@ def _has_widths(seq, widths):
 
 
 def native_point_supported(net):
-    """Whether `net`'s shared MLP is the one csrc/pose.hip implements (3-64-64-64-128-1024, with biases): all `PoseNet._pooled` needs."""
+    """Whether `net`'s shared MLP is the one csrc/pose_point.hip implements (3-64-64-64-128-1024, with biases): all `PoseNet._pooled` needs."""
     return isinstance(net, PoseNet) and _has_widths(net.point, POINT_WIDTHS)
 
 
 def native_refine_supported(net):
-    """Whether `net` is the architecture csrc/pose.hip implements: that shared MLP and the head 2048-1024-512-256-7, all with biases."""
+    """Whether `net` is the architecture csrc/pose*.hip implement: that shared MLP and the head 2048-1024-512-256-7, all with biases."""
     return native_point_supported(net) and _has_widths(net.head, HEAD_WIDTHS)
 
 
@@ -116,7 +116,7 @@ def _point_backward(w, ptsA, ptsB, nA, nB, N, df, h, ties, grads):
 
 class _PointFeaturesFn(torch.autograd.Function):
     """Shared MLP + max pool of the pose network (models/ipcr_model.py:198-233) with its weight gradients on the library
-    (include/dpdist_capi.h: dpd_pose_point_fwd_train / dpd_pose_point_bwd; csrc/pose.hip): one launch forward, three backward (four above
+    (include/dpdist_capi.h: dpd_pose_point_fwd_train / dpd_pose_point_bwd; csrc/pose_point.hip, pose_point_bwd.hip): one launch forward, three backward (four above
     64 points), instead of ~16 forward and ~45 backward launches of torch / hipBLASLt kernels at batch 16.  The clouds carry no gradient (the
     refined source of a registration step is a constant of the step, iterative_PCRNet_ours.py:442-470).  Same mathematics as `point(...).amax(1)` -- gradient of
     the max pool shared evenly among ties like tf.reduce_max -- in another fp32 summation order."""
@@ -259,7 +259,7 @@ class PoseNet(nn.Module):
         wb = self._library_weights(source, head=True)
         if wb is not None and template.shape == source.shape and template.dtype == source.dtype and not template.requires_grad:
             # the training evaluation on the library (one autograd node): the dropout mask is the one `refine` drew with the refinements'
-            # masks, or drawn here (torch's Philox stream either way); everything else is csrc/pose.hip
+            # masks, or drawn here (torch's Philox stream either way); everything else is csrc/pose*.hip
             mask, self.next_mask = self.next_mask, None
             if mask is None or not self.training or mask.shape != (B, 256) or mask.device != source.device:
                 mask = _dropout_masks(self, 1, B, source.device)
