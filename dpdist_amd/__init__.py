@@ -22,6 +22,9 @@ def __getattr__(name):
     if name in ("dpdist_pairs", "DPDistPairs"):
         from . import pairs
         return getattr(pairs, name)
+    if name in ("dpdist_field", "DPDistField"):
+        from . import field
+        return getattr(field, name)
     if name in ("chamfer_matrix", "hausdorff_matrix", "ChamferMatrix", "chamfer_pairs", "hausdorff_pairs", "ChamferPairs"):
         from . import baselines
         return getattr(baselines, name)

@@ -558,6 +558,18 @@ extern "C" int dpd_decoder_fwd_cross_counts(const float* Xu /* k-major */, int l
     return fwd_cross(Xu, ldu, slot_cap, Xt, uid, cnt, Pu, maskr, qcounts, pairs, Cb, N, KP, H, p, act0, act1, y, pred, Dd, stream);
 }
 
+// Per-point field (patch_rows.hip: dpd_field_gather): the launches of dpd_decoder_fwd_cross over the chunk's rows, without pair means
+extern "C" int dpd_decoder_fwd_field(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt,
+                                     float* Pu, const float* maskr, int rows, int KP, int H, const dpd_decoder_params* p, float* act0, float* act1,
+                                     float* y, float* pred, void* stream) {
+    if (!Xu || !Xt || !uid || !cnt || !Pu || !maskr || !p || !act0 || !act1 || !y || !pred) return DPD_E_NULL;
+    if (act0 == act1) return DPD_E_DIM;
+    int Q = 0;
+    if (int rc = check_cross(p, ldu, slot_cap, nullptr, rows, 0, 1, KP, H, &Q)) return rc;
+    // h1 -> act0, h2 -> act1, h3 -> act0: nothing is kept for a backward pass
+    return fwd_over_slots(Xu, ldu, slot_cap, Xt, uid, cnt + 1, Pu, maskr, Q, KP, H, p, act0, act1, act0, y, pred, (hipStream_t)stream, true);
+}
+
 // dpd_decoder_fwd_cross with the three activations kept for dpd_cross_bwd: the same launches on the same operands, so the same bits
 extern "C" int dpd_decoder_fwd_cross_keep(const float* Xu /* k-major */, int ldu, int slot_cap, const float* Xt, const int32_t* uid,
                                           const int32_t* cnt, float* Pu, const float* maskr, int pairs, int N, int KP, int H,

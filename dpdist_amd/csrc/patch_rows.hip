@@ -9,6 +9,7 @@
 // (d_axis0, d_axis1, d_axis2) like extract_volume_patches) | q - centre (3) | zero pad ].  Everything is float4
 // aligned (20 channels = 5 float4; KP*4 bytes is a multiple of 16).  HBM-bound: algorithmic bytes per query row
 // = KP*4 written (+ 12 read; fv[c] = 40 KB per cloud is L2 resident and shared by the cloud's 64 rows).
+#include <algorithm>
 #include <cstdlib>
 
 #include "cross_chunk.h"
@@ -475,6 +476,7 @@ __global__ __launch_bounds__(512) void patch_rows_fwd_lds_kernel(const float* __
 
 #include "patch_rows_unique.h"      // the same gather over distinct windows (window_index_kernel, patch_rows_fwd_unique_kernel)
 #include "patch_rows_cross.h"       // ... for every cloud of one set against every query of another (cross_index_kernel, patch_rows_cross_kernel)
+#include "patch_rows_field.h"       // ... for every cloud against queries of its own, any number of them (field_index_kernel, patch_rows_field_kernel)
 
 // Backward as a gather (patch_rows_bwd.h): block (c, slice) owns a slice of the voxels of cloud c
 __global__ __launch_bounds__(256) void patch_rows_bwd_kernel(const float* __restrict__ dX, const int32_t* __restrict__ vox,
@@ -826,6 +828,70 @@ extern "C" int dpd_cross_gather(const float* q, const int32_t* vox, const float*
     if (int rc2 = ensure_dyn_lds(lx_opt, (const void*)patch_rows_cross_kernel, lds)) return rc2;
     DPD_LAUNCH(patch_rows_cross_kernel, dim3(Ca_chunk * kCrossChunks), dim3(512), lds, (hipStream_t)stream, q, vox, mask, slot_of_vox, ucount, ucap,
                fv, Xu, ldu, Xt, uid, maskr, cnt, Ca_chunk, QN, rows_p, m, k, KP, make_axis(m), ssq, kMfvSlices, mg_k, mg_kk);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- per-point field (patch_rows_field.h) ----
+namespace {
+// slots of a chunk of n clouds with T queries each, before rounding; 0 for a shape no entry takes
+long field_slots(int n, int T, int m) {
+    if (n <= 0 || T <= 0 || m < 1 || m > 10 || (long)n * T > (1L << 30)) return 0;
+    return (long)n * std::min(m * m * m, T);
+}
+// THE shape predicate of the field gather (k <= 0: the window is not known to the caller, as for the capacity report): the shapes of the LDS
+// form of the distinct-window gather, and Xu addressable by the GEMM kernels
+bool field_shape_ok(int n, int T, int m, int k, int KP) {
+    const long cap = (field_slots(n, T, m) + 31) / 32 * 32;
+    if (cap <= 0 || cap > 0x7fffffffL) return false;
+    if (k <= 0) return true;
+    if (k < 3 || k > 7 || !(k & 1) || KP != dpd_padded_width(k) || k * k * k * dpd::kF < KP - 32) return false;
+    const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
+    for (int x = 0; x < k * k * k; ++x)
+        if ((int)((x * mg_kk) >> 16) != x / (k * k) || (int)(((x % (k * k)) * mg_k) >> 16) != (x % (k * k)) / k) return false;
+    if (cross_lds_bytes(m, KP) > 128 * 1024) return false;
+    return dpd::fits_gemm_offsets((size_t)(KP - 32), (size_t)cap);
+}
+}  // namespace
+
+extern "C" int dpd_field_slot_capacity(int n, int T, int m) {
+    return field_shape_ok(n, T, m, 0, 0) ? (int)((field_slots(n, T, m) + 31) / 32 * 32) : 0;
+}
+
+extern "C" int dpd_field_index(const float* q, long q_cloud_stride, const int32_t* qcounts, int t0, int n, int T, int m, float* mask,
+                               int32_t* vox, int32_t* slot_of_vox, int32_t* ucount, void* stream) {
+    using namespace dpd;
+    if (!q || !mask || !vox || !slot_of_vox || !ucount) return DPD_E_NULL;
+    if (n <= 0 || T <= 0 || t0 < 0 || q_cloud_stride < 0) return DPD_E_DIM;
+    if (!field_shape_ok(n, T, m, 0, 0)) return DPD_E_UNSUPPORTED;
+    StageProf prof(stream, DPD_STAGE_GATHER, (double)n * T * 20.0 + (double)n * m * m * m * 4.0);
+    DPD_LAUNCH(field_index_kernel, dim3(n), dim3(1024), 0, (hipStream_t)stream, q, q_cloud_stride, qcounts, t0, T, m, make_axis(m), mask, vox,
+               slot_of_vox, ucount);
+    DPD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dpd_field_gather(const float* q, long q_cloud_stride, const int32_t* vox, const float* mask, const int32_t* slot_of_vox,
+                                const int32_t* ucount, const float* fv, int n, int T, int m, int k, int KP, float* Xu, int ldu, float* Xt,
+                                int32_t* uid, float* maskr, int32_t* cnt, void* stream) {
+    using namespace dpd;
+    if (!q || !vox || !mask || !slot_of_vox || !ucount || !fv || !Xu || !Xt || !uid || !maskr || !cnt) return DPD_E_NULL;
+    if (n <= 0 || T <= 0 || q_cloud_stride < 0) return DPD_E_DIM;
+    if (!field_shape_ok(n, T, m, k, KP)) return DPD_E_UNSUPPORTED;
+    const int cap = dpd_field_slot_capacity(n, T, m), G = m * m * m;
+    if (ldu < cap) return DPD_E_DIM;
+    if (!fits_gemm_offsets((size_t)(KP - 32), (size_t)ldu)) return DPD_E_UNSUPPORTED;
+    const int rows_p = (int)(((long)n * T + 31) / 32 * 32);
+    const int chunks = std::min(32, (256 + n - 1) / n);      // workgroups per cloud: about one per CU for few clouds, one for many
+    const size_t lds = cross_lds_bytes(m, KP);
+    const unsigned mg_k = 65536u / k + 1, mg_kk = 65536u / (k * k) + 1;
+    // algorithmic bytes: the surface vectors and the queries in; the windows (an upper bound: the slot capacity) and the rows' tails out
+    StageProf prof(stream, DPD_STAGE_GATHER,
+                   (double)n * G * kF * 4.0 + (double)n * T * 20.0 + (double)cap * (KP - 32) * 4.0 + (double)rows_p * (32 * 4.0 + 8.0));
+    static LdsOptIn lf_opt;
+    if (int rc2 = ensure_dyn_lds(lf_opt, (const void*)patch_rows_field_kernel, lds)) return rc2;
+    DPD_LAUNCH(patch_rows_field_kernel, dim3(n * chunks), dim3(512), lds, (hipStream_t)stream, q, q_cloud_stride, vox, mask, slot_of_vox, ucount,
+               std::min(G, T), fv, Xu, ldu, Xt, uid, maskr, cnt, n, T, chunks, rows_p, m, k, KP, make_axis(m), mg_k, mg_kk);
     DPD_CHECK_LAUNCH();
     return 0;
 }

@@ -14,39 +14,22 @@
 // rows_p = the rows rounded up to 32 (the finish kernel works on 32-row tiles): pad rows get uid 0, Xt 0, mask 0.
 #pragma once
 
-// One workgroup: voxel and mask of every query (the cell rule of patch_rows_fwd_kernel), then the occupied voxels in ascending id.
-// An occupancy flag per voxel in LDS (plain stores of 1), a ballot prefix over the flags: integer only, one order.
-// CNT (dpd_cross_index_counts): query cloud j holds its first counts[j] queries of a row of N (clamped into [1, N] here); a padded query
-// is not read and is treated exactly like a query outside the cube, so nothing downstream knows about padding but the denominators.
-template <bool CNT>
-__device__ __forceinline__ void cross_index_block(const float* __restrict__ q, int QN, int m, const GridAxis& ax, float* __restrict__ mask,
-                                                  int32_t* __restrict__ vox, int32_t* __restrict__ slot_of_vox, int32_t* __restrict__ ucount,
-                                                  const int32_t* __restrict__ counts, int N) {
-    __shared__ int s_occ[1024];      // m <= 10: m^3 <= 1000
-    __shared__ int s_wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int G = m * m * m;
-    s_occ[tid] = 0;
-    __syncthreads();
-    for (int r = tid; r < QN; r += 1024) {
-        bool real = true;
-        if (CNT) {
-            const int j = r / N;
-            real = r - j * N < min(max(counts[j], 1), N);
-        }
-        int ix = -1, iy = -1, iz = -1;
-        if (real) {
-            const float qx = q[(size_t)r * 3], qy = q[(size_t)r * 3 + 1], qz = q[(size_t)r * 3 + 2];
-            ix = cell_of(ax, m, qx); iy = cell_of(ax, m, qy); iz = cell_of(ax, m, qz);
-        }
-        const bool valid = (ix >= 0) && (iy >= 0) && (iz >= 0);
-        if (!valid) { ix = 0; iy = 0; iz = 0; }      // a masked query shares the window of voxel 0 (patch_rows_fwd_kernel)
-        const int v = (iy * m + ix) * m + iz;
-        mask[r] = valid ? 1.f : 0.f;
-        vox[r] = v;
-        s_occ[v] = 1;
+// ---- the two steps of an index workgroup of 1024 threads, shared with patch_rows_field.h ----
+// voxel and mask of one query (the cell rule of patch_rows_fwd_kernel); a query that is not `real` (padding) is not read and is masked
+__device__ __forceinline__ int index_query(const float* __restrict__ q, bool real, int m, const GridAxis& ax, bool* valid) {
+    int ix = -1, iy = -1, iz = -1;
+    if (real) {
+        const float qx = q[0], qy = q[1], qz = q[2];
+        ix = cell_of(ax, m, qx); iy = cell_of(ax, m, qy); iz = cell_of(ax, m, qz);
     }
-    __syncthreads();
+    *valid = (ix >= 0) && (iy >= 0) && (iz >= 0);
+    if (!*valid) { ix = 0; iy = 0; iz = 0; }      // a masked query shares the window of voxel 0 (patch_rows_fwd_kernel)
+    return (iy * m + ix) * m + iz;
+}
+// ballot prefix over the occupancy flags s_occ [1024] (complete, behind a barrier): slot_of_vox [G], ucount [1]
+__device__ __forceinline__ void index_slots(const int* s_occ, int* s_wsum, int G, int32_t* __restrict__ slot_of_vox,
+                                            int32_t* __restrict__ ucount) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool occ = tid < G && s_occ[tid];
     const unsigned long long b = __ballot(occ);
     if (lane == 0) s_wsum[wave] = __popcll(b);
@@ -59,6 +42,35 @@ __device__ __forceinline__ void cross_index_block(const float* __restrict__ q, i
     }
     if (tid < G) slot_of_vox[tid] = occ ? before + __popcll(b & ((1ull << lane) - 1ull)) : -1;
     if (tid == 0) ucount[0] = all;
+}
+
+// One workgroup: voxel and mask of every query (the cell rule of patch_rows_fwd_kernel), then the occupied voxels in ascending id.
+// An occupancy flag per voxel in LDS (plain stores of 1), a ballot prefix over the flags: integer only, one order.
+// CNT (dpd_cross_index_counts): query cloud j holds its first counts[j] queries of a row of N (clamped into [1, N] here); a padded query
+// is not read and is treated exactly like a query outside the cube, so nothing downstream knows about padding but the denominators.
+template <bool CNT>
+__device__ __forceinline__ void cross_index_block(const float* __restrict__ q, int QN, int m, const GridAxis& ax, float* __restrict__ mask,
+                                                  int32_t* __restrict__ vox, int32_t* __restrict__ slot_of_vox, int32_t* __restrict__ ucount,
+                                                  const int32_t* __restrict__ counts, int N) {
+    __shared__ int s_occ[1024];      // m <= 10: m^3 <= 1000
+    __shared__ int s_wsum[16];
+    const int tid = threadIdx.x;
+    s_occ[tid] = 0;
+    __syncthreads();
+    for (int r = tid; r < QN; r += 1024) {
+        bool real = true;
+        if (CNT) {
+            const int j = r / N;
+            real = r - j * N < min(max(counts[j], 1), N);
+        }
+        bool valid;
+        const int v = index_query(q + (size_t)r * 3, real, m, ax, &valid);
+        mask[r] = valid ? 1.f : 0.f;
+        vox[r] = v;
+        s_occ[v] = 1;
+    }
+    __syncthreads();
+    index_slots(s_occ, s_wsum, m * m * m, slot_of_vox, ucount);
 }
 
 __global__ __launch_bounds__(1024) void cross_index_kernel(const float* __restrict__ q, int QN, int m, GridAxis ax, float* __restrict__ mask,

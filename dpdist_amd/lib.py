@@ -111,6 +111,11 @@ SIGNATURES = {
     "dpd_patch_rows_fwd_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_pairs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(DecoderParams)] + [c_void_p] * 6),
     "dpd_pairs_combine": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # per-point field (dpdist_amd/field.py)
+    "dpd_field_slot_capacity": (c_int, [c_int] * 3),
+    "dpd_field_index": (c_int, [c_void_p, c_long, c_void_p] + [c_int] * 4 + [c_void_p] * 5),
+    "dpd_field_gather": (c_int, [c_void_p, c_long] + [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_int] + [c_void_p] * 5),
+    "dpd_decoder_fwd_field": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int] * 3 + [POINTER(DecoderParams)] + [c_void_p] * 5),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

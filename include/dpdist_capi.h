@@ -399,6 +399,47 @@ int dpd_decoder_out_pairs(const float* h3, const float* mask, int P, int Wa, int
 int dpd_pairs_combine(const float* dptsA, const float* dptsB, const float* dX, const float* G_ab, const float* G_ba, int P, int Wa, int Wb,
                       const int32_t* countsA, const int32_t* countsB, int k, int KP, float* gA, float* gB, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PER-POINT FIELD (DPD_F32): the decoder's answer at queries of the caller's choosing, not averaged.  A chunk is n surface clouds
+ * fv [n, m^3, 20] (normalised Fisher vectors) times T consecutive queries of each; cloud c's queries start at q + c * q_cloud_stride floats
+ * (3 M for clouds with M queries of their own, 0 for one query set shared by all clouds; q points at query t0 of the chunk's first
+ * cloud).  Rows are ordered (c, t), rows = n T, rows_p = rows rounded up to 32.  A window depends on (cloud, voxel) only, so layer 1
+ * contracts its first KP - 32 columns once per occupied (cloud, voxel) -- at most min(m^3, T) per cloud -- instead of once per row.  The
+ * caller owns all memory; the host never reads a device word; every chunk has its own index, slots and slot product.
+ *
+ * dpd_field_slot_capacity: n * min(m^3, T) rounded up to 32: the columns of Xu and the rows of Pu are sized by it.  0 = refused
+ *   (n, T < 1, m outside 1..10, n T > 2^30).
+ * dpd_field_index: one workgroup per cloud -> vox [n T], mask [n T] (the cell rule and the bits of dpd_patch_rows_fwd; a masked query
+ *   uses voxel 0's window), slot_of_vox [n, m^3] (the dense slot INSIDE cloud c of every voxel its queries occupy, in ascending voxel id,
+ *   else -1) and ucount [n] = U_c.  One launch, integer only, deterministic.  qcounts [n] (int32, DEVICE memory; may be NULL = every query
+ *   is real): row (c, t) is padding when t0 + t >= max(qcounts[c], 1); a padded query is not read by the index and is a masked query of
+ *   voxel 0, as in dpd_cross_index_counts.
+ * dpd_field_gather: the windows and the rows' tails of the chunk, one launch:
+ *     Xu [KP - 32, ldu]  K-MAJOR: column base_c + s = columns [0, KP - 32) of the window of surface c around the voxel of its slot s, the
+ *                        bits dpd_patch_rows_fwd writes for such a row; base_c = sum of U_c' over c' < c (cloud-major, ascending voxel id
+ *                        inside a cloud); nothing beyond the sum U_c live columns is written;
+ *     Xt [rows_p, 32]    columns [KP - 32, KP) of every row (the window's last values, q - centre, the zero pad); the q - centre of a
+ *                        padded query is formed from the padding, which must be finite;
+ *     uid [rows_p]       base_c + slot_of_vox[c][vox(c, t)];   maskr [rows_p] the mask of the row's query;
+ *     cnt [4]            {n, sum U_c, 0, 0}: cnt[1] is the live slot count the decoder reads on the device;
+ *   pad rows (rows <= r < rows_p) get uid 0, Xt 0, mask 0.  Needs k odd in 3..7, KP == dpd_padded_width(k), m <= 10, n T <= 2^30, and
+ *   Xu [KP - 32, ldu] below the 4 GiB the GEMMs address (else DPD_E_UNSUPPORTED); ldu >= dpd_field_slot_capacity(n, T, m) (else DPD_E_DIM).
+ * dpd_decoder_fwd_field: the launches of dpd_decoder_fwd_cross on those buffers (Pu [slot_cap, H], two ping-pong activation buffers
+ *   act0 != act1 [rows_p, H]) without the pair means: y and pred [rows_p, 3] have the bits of dpd_decoder_fwd on the plain rows.  Needs
+ *   H % 64 == 0, KP % 32 == 0, slot_cap % 4 == 0, ldu % 4 == 0, rows <= 2^30 and Xu, Pu and the activations below 4 GiB each.
+ * The backward is existing entries: dpd_decoder_fwd_cross_keep(pairs = n, N = T, Dd = NULL), dpd_decoder_bwd_data with dX,
+ * dpd_patch_rows_bwd(dX, vox, n, T) -> dq [n, T, 3] and dfv, dpd_mfv3d_bwd*.
+ * NULL argument: DPD_E_NULL; n, T < 1, t0 < 0, a negative stride: DPD_E_DIM; a refused shape: DPD_E_UNSUPPORTED; all before any launch. */
+int dpd_field_slot_capacity(int n, int T, int m);
+int dpd_field_index(const float* q, long q_cloud_stride, const int32_t* qcounts, int t0, int n, int T, int m, float* mask, int32_t* vox,
+                    int32_t* slot_of_vox, int32_t* ucount, void* stream);
+int dpd_field_gather(const float* q, long q_cloud_stride, const int32_t* vox, const float* mask, const int32_t* slot_of_vox,
+                     const int32_t* ucount, const float* fv, int n, int T, int m, int k, int KP, float* Xu, int ldu, float* Xt, int32_t* uid,
+                     float* maskr, int32_t* cnt, void* stream);
+int dpd_decoder_fwd_field(const float* Xu, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
+                          const float* maskr, int rows, int KP, int H, const dpd_decoder_params* p, float* act0, float* act1, float* y,
+                          float* pred, void* stream);
+
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in
  *               dpd_decoder_fwd / dpd_decoder_bwd_data (ws may be NULL);
