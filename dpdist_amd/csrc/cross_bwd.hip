@@ -10,16 +10,15 @@
 #include "common.h"
 #include "cross_chunk.h"
 #include "gemm_host.h"
+#include "slot_bwd.h"
 
 namespace dpd {
 
 constexpr int kCF = DPD_FV_CHANNELS;
-constexpr int kCrossMaxH = 4096;      // slot_sum_kernel: one wave per 256 columns, at most 16 waves
+constexpr int kCrossMaxH = kSlotMaxH;      // slot_sum_kernel: one wave per 256 columns, at most 16 waves
 
-// One workgroup: the queries sorted by slot (a stable counting sort: ascending query id inside a slot), the start offset of every slot
-// and the voxel of every slot.  Counts by integer LDS atomics (any order gives the same counts), an exclusive prefix over the voxels,
-// then wave 0 places the queries 64 at a time in query order: lanes of one slot take consecutive positions by their rank among the
-// lanes of that slot (a ballot), so the order inside a slot is the query id.  Integer only, one order.
+// One workgroup: the queries sorted by slot (invert_block of slot_bwd.h: a stable counting sort, ascending query id inside a slot), the
+// start offset of every slot and the voxel of every slot.  Integer only, one order.
 //   slot_start [m^3 + 1]  start of slot s in qlist for s < U, QN for s >= U (so slot s holds [slot_start[s], slot_start[s + 1]))
 //   qlist [QN]            query ids sorted by (slot, query id)
 //   slot_vox [m^3]        voxel id of slot s for s < U, -1 for s >= U
@@ -29,64 +28,11 @@ __global__ __launch_bounds__(1024) void cross_invert_kernel(const int32_t* __res
                                                             int32_t* __restrict__ slot_vox) {
     __shared__ int s_cnt[1024];      // per voxel: the count, then the running position of the voxel's slot
     __shared__ int s_wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    s_cnt[tid] = 0;
-    __syncthreads();
-    for (int r = tid; r < QN; r += 1024) {
-        int v = vox[r];
-        if ((unsigned)v >= (unsigned)G) v = 0;
-        atomicAdd(&s_cnt[v], 1);
-    }
-    __syncthreads();
-    // exclusive prefix of the counts in voxel order (= slot order: the slots are the occupied voxels in ascending voxel id)
-    const int c = s_cnt[tid];
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < 16; ++w) before += (w < wave) ? s_wsum[w] : 0;
-    const int start = before + incl - c;
-    __syncthreads();
-    s_cnt[tid] = start;
+    const int tid = threadIdx.x;
     const int U = min(max(ucount[0], 0), G);
-    if (tid < G) {
-        const int sl = slot_of_vox[tid];
-        if (sl >= 0 && sl < U) { slot_start[sl] = start; slot_vox[sl] = tid; }
-    }
     if (tid >= U && tid < G) slot_vox[tid] = -1;
     if (tid >= U && tid <= G) slot_start[tid] = QN;
-    __syncthreads();
-    if (wave != 0) return;
-    volatile int* pos_of = s_cnt;      // written by one lane, read by others of the same wave in the next round
-    for (int r0 = 0; r0 < QN; r0 += 64) {
-        const int r = r0 + lane;
-        const bool live = r < QN;
-        int v = live ? vox[r] : 0;
-        if ((unsigned)v >= (unsigned)G) v = 0;
-        unsigned long long todo = __ballot(live);
-        int rank = 0, total = 0;
-        while (todo) {
-            const int leader = __ffsll((long long)todo) - 1;
-            const int v0 = __shfl(v, leader, 64);
-            const unsigned long long same = __ballot(live && v == v0);
-            if (live && v == v0) {
-                rank = __popcll(same & ((1ull << lane) - 1ull));
-                total = __popcll(same);
-            }
-            todo &= ~same;
-        }
-        if (live) {
-            const int pos = pos_of[v] + rank;
-            if ((unsigned)pos < (unsigned)QN) qlist[pos] = r;      // (the counts bound every position)
-        }
-        // one lane per voxel advances its position (LDS is in order inside one wave)
-        if (live && rank == total - 1) pos_of[v] = pos_of[v] + total;
-    }
+    invert_block(vox, slot_of_vox, U, QN, G, 0, slot_start, qlist, slot_vox, s_cnt, s_wsum);
 }
 
 // Upstream spread, the inverse of pair_mean_kernel: dpred[r] = (Gd[pair of r] / N, 0, 0) for the real rows, 0 for the pad rows.
@@ -120,126 +66,44 @@ __global__ __launch_bounds__(256) void cross_spread_counts_kernel(const float* _
 //   dq[(i, qn), c] = sum_w wave_sum( g1[(i, qn), cols of w] . W1p[E + c, cols of w] ),  c = 0..2   (fixed tree per wave, waves ascending)
 // Workgroups Ca U <= t < slot_cap write ZERO rows of gs: the slot product runs over the capacity.
 // gs = NULL: the surface set needs no gradient (only dq); dq = NULL: the query set needs none (only gs).
-constexpr int kSlotRows = 32;         // rows between two exchanges of the waves' partial dot products
 __global__ __launch_bounds__(1024) void slot_sum_kernel(const float* __restrict__ g1, const int32_t* __restrict__ cnt,
                                                         const int32_t* __restrict__ slot_start, const int32_t* __restrict__ qlist,
                                                         const float* __restrict__ Wq /* W1p + E H: three rows */, int Ca, int QN, int H, int ucap,
                                                         float* __restrict__ gs, float* __restrict__ dq) {
     __shared__ float s_part[kSlotRows][16][3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int U = min(max(cnt[0], 0), ucap);
     const int t = blockIdx.x;
     const int col = 256 * wave + 4 * lane;
-    const bool has = col < H;
     if (t >= Ca * U) {
-        if (gs && has) *reinterpret_cast<float4*>(gs + (size_t)t * H + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gs && col < H) *reinterpret_cast<float4*>(gs + (size_t)t * H + col) = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
     const int i = t / U, s = t % U;
     const int b = min(max(slot_start[s], 0), QN), e = min(max(slot_start[s + 1], b), QN);
-    float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, acc = w0;
-    if (dq && has) {
-        w0 = *reinterpret_cast<const float4*>(Wq + col);
-        w1 = *reinterpret_cast<const float4*>(Wq + (size_t)H + col);
-        w2 = *reinterpret_cast<const float4*>(Wq + 2 * (size_t)H + col);
-    }
-    for (int p0 = b; p0 < e; p0 += kSlotRows) {
-        const int np = min(kSlotRows, e - p0);
-        for (int p = 0; p < np; ++p) {
-            int qn = qlist[p0 + p];
-            qn = min(max(qn, 0), QN - 1);
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (has) x = *reinterpret_cast<const float4*>(g1 + ((size_t)i * QN + qn) * H + col);
-            acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
-            if (dq) {
-                const float d0 = wave_sum(((x.x * w0.x + x.y * w0.y) + x.z * w0.z) + x.w * w0.w);
-                const float d1 = wave_sum(((x.x * w1.x + x.y * w1.y) + x.z * w1.z) + x.w * w1.w);
-                const float d2 = wave_sum(((x.x * w2.x + x.y * w2.y) + x.z * w2.z) + x.w * w2.w);
-                if (lane == 0) { s_part[p][wave][0] = d0; s_part[p][wave][1] = d1; s_part[p][wave][2] = d2; }
-            }
-        }
-        if (dq) {
-            __syncthreads();
-            for (int x = threadIdx.x; x < np * 3; x += blockDim.x) {
-                const int p = x / 3, c = x % 3;
-                float d = s_part[p][0][c];
-                for (int w = 1; w < nw; ++w) d += s_part[p][w][c];
-                int qn = qlist[p0 + p];
-                qn = min(max(qn, 0), QN - 1);
-                dq[((size_t)i * QN + qn) * 3 + c] = d;
-            }
-            __syncthreads();
-        }
-    }
-    if (gs && has) *reinterpret_cast<float4*>(gs + (size_t)t * H + col) = acc;
+    slot_sum_rows(g1 + (size_t)i * QN * H, qlist, b, e, QN, H, Wq, gs ? gs + (size_t)t * H : nullptr, dq ? dq + (size_t)i * QN * 3 : nullptr,
+                  s_part);
 }
 
-// Window scatter over the slots, as a gather (the form of patch_rows_bwd.h): workgroup (i, slice) owns a slice of the voxels of surface
-// i and, for every (voxel, float4 channel group), sums that window column of every slot of the surface whose window covers the voxel,
-// in ascending slot order.  A voxel outside the grid has no item: zero padding at the border.  U comes from device memory.  Every item
-// is computed by ONE thread from the same loads in the same order whatever the launch shape is.
+// Window scatter over the slots, as a gather (scatter_slots of slot_bwd.h): workgroup (i, slice) owns a slice of the voxels of surface i
+// and, for every (voxel, float4 channel group), sums that window column of every slot of the surface whose window covers the voxel, in
+// ascending slot order.  U comes from device memory.
 __global__ __launch_bounds__(256) void cross_scatter_kernel(const float* __restrict__ dXs, const int32_t* __restrict__ cnt,
                                                             const int32_t* __restrict__ slot_vox, float* __restrict__ dfv, int m, int k, int KP,
                                                             int ucap, int slices) {
     __shared__ int s_vox[1024];       // packed voxel coordinates of the slots (m <= 10: at most 1000)
-    const int tid = threadIdx.x;
     const int c = blockIdx.x / slices, sl = blockIdx.x % slices;
-    const int G = m * m * m, h = (k - 1) / 2;
+    const int G = m * m * m;
     const int U = min(min(max(cnt[0], 0), ucap), 1024);
-    for (int n = tid; n < U; n += 256) {
-        int v = slot_vox[n];
-        if ((unsigned)v >= (unsigned)G) v = 0;
-        s_vox[n] = (v / (m * m)) | (((v / m) % m) << 8) | ((v % m) << 16);
-    }
-    __syncthreads();
     const int gper = (G + slices - 1) / slices;
     const int gbeg = sl * gper, gend = min(G, gbeg + gper);
-    const float* dXc = dXs + (size_t)c * U * KP;
-    for (int item = tid; item < (gend - gbeg) * 5; item += 256) {
-        const int g = gbeg + item / 5, part = item % 5;
-        const int g0 = g / (m * m) + h, g1 = (g / m) % m + h, g2 = g % m + h;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int n0 = 0; n0 < U; n0 += 64) {
-            unsigned long long hm = 0;
-            const int lim = min(64, U - n0);
-            for (int j = 0; j < lim; ++j) {
-                const int pv = s_vox[n0 + j];
-                const int d0 = g0 - (pv & 255), d1 = g1 - ((pv >> 8) & 255), d2 = g2 - (pv >> 16);
-                if ((unsigned)d0 < (unsigned)k && (unsigned)d1 < (unsigned)k && (unsigned)d2 < (unsigned)k) hm |= 1ull << j;
-            }
-            while (__any(hm != 0)) {
-                float4 x[16];
-                bool hit[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    hit[j] = hm != 0;
-                    const int bit = hit[j] ? __ffsll((long long)hm) - 1 : 0;
-                    hm = hit[j] ? (hm & (hm - 1)) : 0;
-                    const int n = n0 + bit;
-                    const int pv = s_vox[n];
-                    const int d0 = g0 - (pv & 255), d1 = g1 - ((pv >> 8) & 255), d2 = g2 - (pv >> 16);
-                    const size_t off = hit[j] ? (size_t)n * KP + ((d0 * k + d1) * k + d2) * kCF + part * 4 : 0;
-                    x[j] = *reinterpret_cast<const float4*>(dXc + off);
-                }
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    acc.x = hit[j] ? acc.x + x[j].x : acc.x; acc.y = hit[j] ? acc.y + x[j].y : acc.y;
-                    acc.z = hit[j] ? acc.z + x[j].z : acc.z; acc.w = hit[j] ? acc.w + x[j].w : acc.w;
-                }
-            }
-        }
-        *reinterpret_cast<float4*>(dfv + ((size_t)c * G + g) * kCF + part * 4) = acc;
-    }
+    scatter_slots(dXs + (size_t)c * U * KP, slot_vox, U, dfv + (size_t)c * G * kCF, m, k, KP, gbeg, gend, false, s_vox);
 }
 
 // Query-route reduction: gQ[j, n, c] = gQ[j, n, c] + dq[(0, j, n), c] + dq[(1, j, n), c] + ... in ascending surface: the chain goes on
 // from the accumulated value, so a chunk boundary changes no bit (the caller zeroes gQ before the first chunk).
 __global__ __launch_bounds__(256) void cross_qreduce_kernel(const float* __restrict__ dq, int Ca, int QN3, float* __restrict__ gQ) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= QN3) return;
-    float acc = gQ[e];
-    for (int i = 0; i < Ca; ++i) acc = acc + dq[(size_t)i * QN3 + e];
-    gQ[e] = acc;
+    qreduce_chain(dq, Ca, QN3, gQ);
 }
 
 }  // namespace dpd

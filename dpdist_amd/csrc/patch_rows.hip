@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "cross_chunk.h"
+#include "field_shape.h"
 #include "gemm_shared.h"
 #include "patch_rows_bwd.h"
 
@@ -833,14 +834,14 @@ extern "C" int dpd_cross_gather(const float* q, const int32_t* vox, const float*
 }
 
 // ---- per-point field (patch_rows_field.h) ----
-namespace {
+namespace dpd {
 // slots of a chunk of n clouds with T queries each, before rounding; 0 for a shape no entry takes
-long field_slots(int n, int T, int m) {
+static long field_slots(int n, int T, int m) {
     if (n <= 0 || T <= 0 || m < 1 || m > 10 || (long)n * T > (1L << 30)) return 0;
     return (long)n * std::min(m * m * m, T);
 }
 // THE shape predicate of the field gather (k <= 0: the window is not known to the caller, as for the capacity report): the shapes of the LDS
-// form of the distinct-window gather, and Xu addressable by the GEMM kernels
+// form of the distinct-window gather, and Xu addressable by the GEMM kernels (declared in field_shape.h: field_bwd.hip builds on it)
 bool field_shape_ok(int n, int T, int m, int k, int KP) {
     const long cap = (field_slots(n, T, m) + 31) / 32 * 32;
     if (cap <= 0 || cap > 0x7fffffffL) return false;
@@ -852,10 +853,10 @@ bool field_shape_ok(int n, int T, int m, int k, int KP) {
     if (cross_lds_bytes(m, KP) > 128 * 1024) return false;
     return dpd::fits_gemm_offsets((size_t)(KP - 32), (size_t)cap);
 }
-}  // namespace
+}  // namespace dpd
 
 extern "C" int dpd_field_slot_capacity(int n, int T, int m) {
-    return field_shape_ok(n, T, m, 0, 0) ? (int)((field_slots(n, T, m) + 31) / 32 * 32) : 0;
+    return dpd::field_shape_ok(n, T, m, 0, 0) ? (int)((dpd::field_slots(n, T, m) + 31) / 32 * 32) : 0;
 }
 
 extern "C" int dpd_field_index(const float* q, long q_cloud_stride, const int32_t* qcounts, int t0, int n, int T, int m, float* mask,

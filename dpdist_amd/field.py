@@ -15,9 +15,13 @@ dpd_patch_rows_fwd + dpd_decoder_fwd on the plain rows, whatever the chunking.  
 synchronisation.  There is no fallback.
 
 `dpdist_field` is the forward alone (no_grad).  `DPDistField` is the same as ONE autograd node in as-loss mode (the decoder is frozen,
-gradients go to the surfaces and the queries), built from existing entries: dpd_decoder_fwd_cross_keep, dpd_decoder_bwd_data with dX,
-dpd_patch_rows_bwd and the encoder backward, per chunk of whole clouds.  The slot-summed backward of the all-pairs matrix
-(csrc/cross_bwd.hip) is not used for this layout: its data gradient runs over the rows.
+gradients go to the surfaces and the queries), with two backward forms behind the `backward` keyword:
+
+  "rows"   (the default) built from existing entries: dpd_decoder_fwd_cross_keep, dpd_decoder_bwd_data with dX [rows_p, KP],
+           dpd_patch_rows_bwd and the encoder backward, per chunk of whole clouds (M <= max_rows, M <= 8192);
+  "slots"  the slot-summed form (csrc/field_bwd.hip: dpd_field_invert, dpd_field_bwd): the g1 rows of the queries that share a slot are
+           summed, layer 1's data gradient runs once per slot, and the tiles of one cloud accumulate into its Fisher-vector gradient.  It
+           walks the forward's plan, tiles included, so M has no limit of its own, and it never holds a [rows_p, KP] matrix.
 """
 import torch
 
@@ -42,8 +46,16 @@ def plan_chunks(C, M, max_rows):
     return [(c, 1, t0, min(max_rows, M - t0)) for c in range(C) for t0 in range(0, M, max_rows)]
 
 
-def _prepare(model_or_params, surfaces, queries, counts, query_counts, max_rows, Embedding_Size, sigma3dmfv, backward=False):
-    """every argument check, before anything is launched -> (P, m, sigma, S, Q, cS, cQ, shared): the counts as int32 device tensors | None"""
+BACKWARDS = ("rows", "slots")
+MAX_SLOT_H = 4096           # dpd_field_slot_sum: one wave per 256 columns, at most 16 waves
+
+
+def _prepare(model_or_params, surfaces, queries, counts, query_counts, max_rows, Embedding_Size, sigma3dmfv, backward=None):
+    """every argument check, before anything is launched -> (P, m, sigma, S, Q, cS, cQ, shared): the counts as int32 device tensors | None.
+    backward: None (forward only), "rows" or "slots": the backward form whose limits apply as well"""
+    if backward not in (None,) + BACKWARDS:
+        raise ValueError("backward must be one of %s" % (BACKWARDS,))
+    rows_mode, slots_mode = backward == "rows", backward == "slots"
     P, m, sigma = _resolve(model_or_params, Embedding_Size, sigma3dmfv)
     _check_shape(surfaces, "surfaces")
     C = surfaces.shape[0]
@@ -69,15 +81,18 @@ def _prepare(model_or_params, surfaces, queries, counts, query_counts, max_rows,
     for c, name in ((cS, "counts"), (cQ, "query_counts")):
         if c is not None and c.is_cuda and c.device != S.device:
             raise ValueError("%s and the clouds must live on the same device" % name)
-    if backward and M > int(max_rows):
+    if rows_mode and M > int(max_rows):
         raise ValueError("DPDistField: the backward takes whole clouds: M = %d queries per cloud exceed max_rows = %d" % (M, int(max_rows)))
-    # what the entries would refuse: the encoder's sizes (its backward: m <= 8), the window scatter's query count, and a chunk beyond the
-    # GEMMs' 32-bit byte offsets
+    if slots_mode and not (0 < P.H <= MAX_SLOT_H and P.H % 64 == 0):
+        raise ValueError("DPDistField: the slots backward needs a decoder width H <= %d that is a multiple of 64, not %d" % (MAX_SLOT_H, P.H))
+    # what the entries would refuse: the encoder's sizes (its backward: m <= 8), the window scatter's query count (rows backward), and a
+    # chunk beyond the GEMMs' 32-bit byte offsets (the widest matrix: dX [rows_p, KP] of the rows backward, dXs [cap, KP] of the slots one)
     lib = L.load()
-    ok = S.shape[1] <= MAX_WIDTH and 1 <= m <= (8 if backward else 10) and not (backward and M > MAX_BWD_QUERIES)
+    ok = S.shape[1] <= MAX_WIDTH and 1 <= m <= (8 if backward else 10) and not (rows_mode and M > MAX_BWD_QUERIES)
     for n, T in {(n, T) for _, n, _, T in plan_chunks(C, M, max_rows)} if ok else ():
         cap, rows_p = lib.dpd_field_slot_capacity(n, T, m), (n * T + 31) // 32 * 32
-        ok = ok and cap > 0 and max((P.KP - 32) * cap, cap * P.H, rows_p * (P.KP if backward else P.H)) * 4 < 1 << 32
+        widest = max((P.KP - 32) * cap, cap * P.H, rows_p * (P.KP if rows_mode else P.H), cap * P.KP if slots_mode else 0)
+        ok = ok and cap > 0 and widest * 4 < 1 << 32
     if not ok:
         raise ValueError("dpdist_field: shape not supported%s (%d clouds of width %d, %d queries each, m %d, k %d, H %d; max_rows %d)"
                          % (" by the backward" if backward else "", C, S.shape[1], M, m, P.k, P.H, max_rows))
@@ -99,7 +114,8 @@ def _encode(lib, s, pts, m, sigma, counts):
 
 class _Chunk:
     """the buffers of one chunk of n clouds times T queries.  Forward: index, slots (Xu, Pu over the slot capacity), the rows' tails, two
-    ping-pong activations, y, pred.  Backward: three activations, two gradient buffers of [rows_p, H] and dX [rows_p, KP]."""
+    ping-pong activations, y, pred.  Backward: three activations and two gradient buffers of [rows_p, H]; "rows" adds dX [rows_p, KP];
+    "slots" adds gs [cap, H], dXs [cap, KP], dq [rows_p, 3] and the integer inverted index instead."""
 
     def __init__(self, lib, P, n, T, m, dev, backward):
         f = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)                  # noqa: E731
@@ -112,12 +128,16 @@ class _Chunk:
         self.Pu, self.h1, self.h2 = f(cap, P.H), f(rows_p, P.H), f(rows_p, P.H)
         self.y, self.pred = f(rows_p, 3), f(rows_p, 3)
         if backward:
-            self.h3, self.ga, self.gb, self.dX = f(rows_p, P.H), f(rows_p, P.H), f(rows_p, P.H), f(rows_p, P.KP)
+            self.h3, self.ga, self.gb = f(rows_p, P.H), f(rows_p, P.H), f(rows_p, P.H)
             self.dy, self.dpred = f(rows_p, 3), torch.zeros(rows_p, 3, device=dev, dtype=torch.float32)      # (the pad rows stay zero)
-            self.dq, self.dfv = f(n, T, 3), f(n, m ** 3, F)
+        if backward == "rows":
+            self.dX, self.dq, self.dfv = f(rows_p, P.KP), f(n, T, 3), f(n, m ** 3, F)
+        if backward == "slots":
+            self.gs, self.dXs, self.dq = f(cap, P.H), f(cap, P.KP), f(rows_p, 3)
+            self.slot_start, self.qlist, self.slot_vox, self.slot_cloud = i(cap + 1), i(n * T), i(cap), i(cap)
 
 
-def _walk(lib, P, m, C, M, max_rows, dev, backward=False):
+def _walk(lib, P, m, C, M, max_rows, dev, backward=None):
     """the chunks -> (first cloud, first query, the chunk's buffers: one set per shape)"""
     chunks = {}
     for c0, n, t0, T in plan_chunks(C, M, max_rows):
@@ -183,8 +203,8 @@ class _FieldFn(torch.autograd.Function):
     """(pred, mask) of the surfaces at the queries as one autograd node"""
 
     @staticmethod
-    def forward(ctx, surfaces, queries, P, m, sigma, max_rows, cS, cQ):
-        ctx.cfg = (P, m, sigma, max_rows)
+    def forward(ctx, surfaces, queries, P, m, sigma, max_rows, cS, cQ, mode):
+        ctx.cfg = (P, m, sigma, max_rows, mode)
         ctx.counts = (cS, cQ)                                           # int32 device tensors | None: no gradient exists w.r.t. counts
         ctx.set_materialize_grads(False)
         S, Q = surfaces.detach().contiguous(), queries.detach().contiguous()
@@ -195,12 +215,12 @@ class _FieldFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gpred, _gmask):
-        P, m, sigma, max_rows = ctx.cfg
+        P, m, sigma, max_rows, mode = ctx.cfg
         cS, cQ = ctx.counts
         S, Q = ctx.saved_tensors
         needS, needQ = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if gpred is None or not (needS or needQ):
-            return (None,) * 8
+            return (None,) * 9
         shared = Q.dim() == 2
         C, W, M, dev = S.shape[0], S.shape[1], Q.shape[-2], S.device
         lib = L.load()
@@ -214,10 +234,16 @@ class _FieldFn(torch.autograd.Function):
             gQ = (torch.zeros_like(Q) if shared else torch.empty_like(Q)) if needQ else None
             per = plan_chunks(C, M, max_rows)[0][1]
             ws = torch.empty(lib.dpd_mfv3d_bwd_workspace_bytes(per, m), device=dev, dtype=torch.uint8) if needS else None
-            for c0, t0, ck in _walk(lib, P, m, C, M, max_rows, dev, backward=True):      # whole clouds: t0 = 0, T = M
+
+            def encoder_bwd(c0, n, dfv):      # dfv [n, m^3, 20] of the clouds [c0, c0 + n) -> their rows of gS
+                if cS is not None:
+                    _check(*ops.encode_bwd_counts(lib, L.ptr(S[c0:c0 + n]), L.ptr(cS[c0:c0 + n]), L.ptr(dfv), n, W, m, sigma, L.ptr(gS[c0:c0 + n]),
+                                                  L.ptr(ws), ws.numel(), s))
+                else:
+                    _check(*ops.encode_bwd(lib, L.ptr(S[c0:c0 + n]), L.ptr(dfv), n, W, m, sigma, L.ptr(gS[c0:c0 + n]), L.ptr(ws), ws.numel(), s))
+
+            def rows_chunk(ck, c0, t0):      # whole clouds (t0 = 0, T = M) -> the chunk's dfv
                 n = ck.n
-                _rows(lib, s, P, cp, m, ck, c0, t0, fv, Q, cQ, shared, True)
-                ck.dpred[:ck.rows].copy_(g[c0:c0 + n].reshape(ck.rows, 3))
                 # g3 (ga) -> g2 (gb) -> g1 (ga) -> dX; a masked or padded query and the pad rows carry exact zeros through the mask
                 _check(lib.dpd_decoder_bwd_data(L.ptr(ck.dpred), L.ptr(ck.maskr), L.ptr(ck.y), L.ptr(ck.h1), L.ptr(ck.h2), L.ptr(ck.h3), ck.rows_p,
                                                 P.KP, P.H, cp, 0, L.ptr(ck.dy), L.ptr(ck.ga), L.ptr(ck.gb), L.ptr(ck.ga), L.ptr(ck.dX), None, None,
@@ -228,13 +254,31 @@ class _FieldFn(torch.autograd.Function):
                 if needQ and shared:
                     for i in range(n):      # ascending c, one chain across the chunks: a chunk boundary changes no bit
                         gQ.add_(ck.dq[i])
-                if needS and cS is not None:
-                    _check(*ops.encode_bwd_counts(lib, L.ptr(S[c0:c0 + n]), L.ptr(cS[c0:c0 + n]), L.ptr(ck.dfv), n, W, m, sigma,
-                                                  L.ptr(gS[c0:c0 + n]), L.ptr(ws), ws.numel(), s))
-                elif needS:
-                    _check(*ops.encode_bwd(lib, L.ptr(S[c0:c0 + n]), L.ptr(ck.dfv), n, W, m, sigma, L.ptr(gS[c0:c0 + n]), L.ptr(ws), ws.numel(), s))
+                return ck.dfv
+
+            # slots mode: the tiles of one cloud come consecutively (plan_chunks: cloud outer, tile inner) and share one dfv: the first tile
+            # stores it, the later ones continue the chain; a shared query set continues one chain in ascending cloud across chunks and tiles
+            dfv_slots = torch.empty(per, m ** 3, F, device=dev, dtype=torch.float32) if needS and mode == "slots" else None
+
+            def slots_chunk(ck, c0, t0):
+                n, T = ck.n, ck.T
+                _check(lib.dpd_field_invert(L.ptr(ck.vox), L.ptr(ck.slot), L.ptr(ck.ucount), n, T, m, ck.cap, L.ptr(ck.slot_start), L.ptr(ck.qlist),
+                                            L.ptr(ck.slot_vox), L.ptr(ck.slot_cloud), s), "dpd_field_invert")
+                gq = None if not needQ else (gQ[t0:] if shared else gQ[c0:, t0:])
+                _check(lib.dpd_field_bwd(L.ptr(ck.dpred), L.ptr(ck.maskr), L.ptr(ck.y), L.ptr(ck.h1), L.ptr(ck.h2), L.ptr(ck.h3), L.ptr(ck.cnt),
+                                         L.ptr(ck.ucount), L.ptr(ck.slot_start), L.ptr(ck.qlist), L.ptr(ck.slot_vox), L.ptr(ck.slot_cloud), n, T, m,
+                                         P.k, P.KP, P.H, ck.cap, cp, L.ptr(ck.dy), L.ptr(ck.ga), L.ptr(ck.gb), L.ptr(ck.dq), L.ptr(ck.gs),
+                                         L.ptr(ck.dXs), L.ptr(dfv_slots), int(t0 > 0), L.ptr(gq), 0 if shared else 3 * M, s), "dpd_field_bwd")
+                return dfv_slots
+
+            for c0, t0, ck in _walk(lib, P, m, C, M, max_rows, dev, backward=mode):
+                _rows(lib, s, P, cp, m, ck, c0, t0, fv, Q, cQ, shared, True)
+                ck.dpred[:ck.rows].copy_(g[c0:c0 + ck.n, t0:t0 + ck.T].reshape(ck.rows, 3))
+                dfv = (slots_chunk if mode == "slots" else rows_chunk)(ck, c0, t0)
+                if needS and t0 + ck.T == M:      # after the last tile of a cloud, or once per chunk of whole clouds
+                    encoder_bwd(c0, ck.n, dfv)
             del cp
-        return gS, gQ, None, None, None, None, None, None
+        return gS, gQ, None, None, None, None, None, None, None
 
 
 class DPDistField(torch.nn.Module):
@@ -243,17 +287,33 @@ class DPDistField(torch.nn.Module):
     launches).
 
     One autograd node over the library, on the current stream, without a host synchronisation.  The node saves the two inputs only and
-    RECOMPUTES every chunk in the backward (as DPDistPairs does).  The backward takes whole clouds: M > max_rows raises a ValueError when
-    an input requires a gradient (the forward has no such limit), and so does M > 8192 (the window scatter's LDS).  A backward chunk of
-    rows_p rows holds three activation and two gradient buffers of [rows_p, H] and dX [rows_p, KP].  The gradient of a shared query set
-    [M, 3] is the sum over the clouds in ascending order, one chain across the chunks, so the gradients do not depend on max_rows.
+    RECOMPUTES every chunk in the backward (as DPDistPairs does).  The gradient of a shared query set [M, 3] is the sum over the clouds
+    in ascending order, one chain across the chunks (and tiles), so it does not depend on max_rows.
+
+    backward="rows" (the default): layer 1's data gradient runs over the rows.  The backward takes whole clouds: M > max_rows raises a
+    ValueError when an input requires a gradient (the forward has no such limit), and so does M > 8192 (the window scatter's LDS).  A
+    backward chunk of rows_p rows holds three activation and two gradient buffers of [rows_p, H] and dX [rows_p, KP].  No gradient
+    depends on max_rows.
+
+    backward="slots": the slot-summed backward (dpd_field_invert, dpd_field_bwd).  The same forward launches and bits.  The g1 rows of the
+    queries that share a (cloud, voxel) slot are summed, layer 1's data gradient is one product per slot, and the node walks the forward's
+    plan, tiles included: M is bounded by neither max_rows nor 8192.  A chunk holds three activation and two gradient buffers of
+    [rows_p, H], gs [cap, H], dXs [cap, KP], dq [rows_p, 3] and the integer index; never a [rows_p, KP] matrix.  The gradient at a query
+    depends on its own row only, so the query gradients do not depend on max_rows.  The surface gradients do not either while a cloud's
+    queries fit into one chunk (M <= max_rows).  With tiles (M > max_rows) a slot's sum is formed per tile and the tiles are added in
+    ascending order, so the bits of the surface gradients depend on max_rows; for a given max_rows they are the same on every run, and
+    they stay inside the oracle's bar.  Needs H % 64 == 0 and H <= 4096 (ValueError before any launch).  The values of the two forms
+    differ by rounding only; their bits differ.
 
     counts / query_counts (keywords of forward): as dpdist_field.  The gradients at padded queries and padded surface points are 0; there
     is no gradient w.r.t. the counts.  An input that needs no gradient gets None and its share of the work is skipped.  Argument checks
     and errors as dpdist_field, before the first launch."""
 
-    def __init__(self, model_or_params, max_rows=16384, Embedding_Size=None, sigma3dmfv=None):
+    def __init__(self, model_or_params, max_rows=16384, Embedding_Size=None, sigma3dmfv=None, backward="rows"):
         super().__init__()
+        if backward not in BACKWARDS:
+            raise ValueError("backward must be one of %s, not %r" % (BACKWARDS, backward))
+        self.backward = backward
         self._src = (model_or_params, Embedding_Size, sigma3dmfv)
         _resolve(model_or_params, Embedding_Size, sigma3dmfv)
         if int(max_rows) < 1:
@@ -263,10 +323,11 @@ class DPDistField(torch.nn.Module):
     def forward(self, surfaces, queries, return_mask=False, *, counts=None, query_counts=None):
         mp, es, sg = self._src
         want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (surfaces, queries))
-        P, m, sigma, S, Q, cS, cQ, shared = _prepare(mp, surfaces, queries, counts, query_counts, self.max_rows, es, sg, backward=want_grad)
+        P, m, sigma, S, Q, cS, cQ, shared = _prepare(mp, surfaces, queries, counts, query_counts, self.max_rows, es, sg,
+                                                     backward=self.backward if want_grad else None)
         if not want_grad:
             with torch.no_grad():
                 pred, mask = _forward(P, m, sigma, S, Q, cS, cQ, shared, self.max_rows)
         else:
-            pred, mask = _FieldFn.apply(surfaces, queries, P, m, sigma, self.max_rows, cS, cQ)
+            pred, mask = _FieldFn.apply(surfaces, queries, P, m, sigma, self.max_rows, cS, cQ, self.backward)
         return (pred, mask) if return_mask else pred

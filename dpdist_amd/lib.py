@@ -116,6 +116,11 @@ SIGNATURES = {
     "dpd_field_index": (c_int, [c_void_p, c_long, c_void_p] + [c_int] * 4 + [c_void_p] * 5),
     "dpd_field_gather": (c_int, [c_void_p, c_long] + [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_int] + [c_void_p] * 5),
     "dpd_decoder_fwd_field": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int] * 3 + [POINTER(DecoderParams)] + [c_void_p] * 5),
+    # ... its slot-summed backward (csrc/field_bwd.hip)
+    "dpd_field_invert": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 5),
+    "dpd_field_slot_sum": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_void_p, c_long, c_void_p]),
+    "dpd_field_scatter": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
+    "dpd_field_bwd": (c_int, [c_void_p] * 12 + [c_int] * 7 + [POINTER(DecoderParams)] + [c_void_p] * 7 + [c_int, c_void_p, c_long, c_void_p]),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

@@ -427,8 +427,8 @@ int dpd_pairs_combine(const float* dptsA, const float* dptsB, const float* dX, c
  * dpd_decoder_fwd_field: the launches of dpd_decoder_fwd_cross on those buffers (Pu [slot_cap, H], two ping-pong activation buffers
  *   act0 != act1 [rows_p, H]) without the pair means: y and pred [rows_p, 3] have the bits of dpd_decoder_fwd on the plain rows.  Needs
  *   H % 64 == 0, KP % 32 == 0, slot_cap % 4 == 0, ldu % 4 == 0, rows <= 2^30 and Xu, Pu and the activations below 4 GiB each.
- * The backward is existing entries: dpd_decoder_fwd_cross_keep(pairs = n, N = T, Dd = NULL), dpd_decoder_bwd_data with dX,
- * dpd_patch_rows_bwd(dX, vox, n, T) -> dq [n, T, 3] and dfv, dpd_mfv3d_bwd*.
+ * The backward over the rows is existing entries: dpd_decoder_fwd_cross_keep(pairs = n, N = T, Dd = NULL), dpd_decoder_bwd_data with dX,
+ * dpd_patch_rows_bwd(dX, vox, n, T) -> dq [n, T, 3] and dfv, dpd_mfv3d_bwd*; the slot-summed backward is the next block.
  * NULL argument: DPD_E_NULL; n, T < 1, t0 < 0, a negative stride: DPD_E_DIM; a refused shape: DPD_E_UNSUPPORTED; all before any launch. */
 int dpd_field_slot_capacity(int n, int T, int m);
 int dpd_field_index(const float* q, long q_cloud_stride, const int32_t* qcounts, int t0, int n, int T, int m, float* mask, int32_t* vox,
@@ -439,6 +439,61 @@ int dpd_field_gather(const float* q, long q_cloud_stride, const int32_t* vox, co
 int dpd_decoder_fwd_field(const float* Xu, int ldu, int slot_cap, const float* Xt, const int32_t* uid, const int32_t* cnt, float* Pu,
                           const float* maskr, int rows, int KP, int H, const dpd_decoder_params* p, float* act0, float* act1, float* y,
                           float* pred, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SLOT-SUMMED BACKWARD of the per-point field (DPD_F32, as-loss mode: the decoder is frozen, gradients go to the surfaces and the
+ * queries).  Per chunk of the forward's plan -- n clouds times T consecutive queries of each, which may be a TILE of one cloud's
+ * queries --, on the chunk's own index (dpd_field_index), slots (dpd_field_gather: ucount, cnt) and kept activations
+ * (dpd_decoder_fwd_cross_keep with pairs = n, N = T, Dd = NULL).  The layer-1 data gradient is linear, so the g1 rows of all queries of a
+ * cloud that share a slot are summed first and multiplied by W1p^T once per slot: no [rows_p, KP] matrix exists and T has no limit of
+ * its own.  Slots are the forward's: cloud-major, global slot g = base_c + s, base_c = the sum of U_c' over c' < c, total = the sum of
+ * the U_c = cnt[1]; slot_cap = dpd_field_slot_capacity(n, T, m).  Deterministic: no float atomics, one summation order per element,
+ * independent of the launch shape.  The caller owns all memory; the host never reads a device word, and the kernels clamp every word
+ * they read (counts into [0, min(m^3, T)], clouds into [0, n), list bounds into the cloud's rows, query ids into [0, T)), so no store
+ * passes the capacity the host sized.
+ *
+ * dpd_field_invert: the inverted index of one chunk, one workgroup per cloud (one launch, integer only):
+ *     qlist [n, T]               row c: the chunk-local query ids of cloud c sorted by slot, ascending query id inside a slot (a stable
+ *                                counting sort);
+ *     slot_start [slot_cap + 1]  slot g holds the flat positions [slot_start[g], slot_start[g + 1]) of qlist, i.e. c T + the cloud's own
+ *                                prefix; n T for total <= g <= slot_cap;
+ *     slot_vox [slot_cap]        the voxel id of slot g;   slot_cloud [slot_cap]  its cloud;   both -1 for the dead slots g >= total.
+ * dpd_field_slot_sum: g1 [rows_p, H] streamed once, one workgroup per slot up to the capacity:
+ *     gs [slot_cap, H]           row g = the sum of the g1 rows (c, t) of the slot's list, added in list order; the DEAD rows are ZEROS;
+ *     dq                         dq[c dq_cloud_stride + 3 t + j] = g1[(c, t), :] . W1p[E + j, :], E = 20 k^3, j = 0..2, for every row of the
+ *                                chunk (a masked or padded query lies in voxel 0's slot: its g1 row is 0 through the mask, its dq is 0);
+ *                                dq_cloud_stride >= 3 T floats (else DPD_E_DIM): 3 T for a buffer [n, T, 3], 3 M to write the rows of a
+ *                                gradient tensor [C, M, 3] in place;
+ *   in the form and fixed reduction tree of dpd_cross_slot_sum (the same device routine).  gs = NULL or dq = NULL (not both): that half
+ *   is skipped.  H % 64 == 0, H <= 4096.
+ * dpd_field_scatter: dXs [slot_cap, KP] (row g = the dX of slot g) -> dfv [n, m^3, 20]: dfv[c, v, ch] = the sum over the cloud's OWN slots
+ *   [base_c, base_c + U_c) whose window covers voxel v, in ascending slot order, of that window column; zero padding at the grid border.
+ *   accumulate != 0: the chain continues from the value dfv holds (the tiles of one cloud add up in ascending tile order without a
+ *   second buffer); accumulate == 0: a plain store, +0.0 for a voxel no slot covers.
+ * dpd_field_bwd: one chunk in one call.  dpred [rows_p, 3] is the upstream gradient of pred, FILLED BY THE CALLER with zero pad rows.
+ *   dpd_decoder_bwd_data (phases 7, no dX; p needs W2T / W3T, and W1pT when dfv is wanted) with g3 -> ga, g2 -> gb, g1 -> ga;
+ *   dpd_field_slot_sum; dXs = gs W1pT (one NN GEMM over the capacity); dpd_field_scatter -> dfv with `accumulate` (feed it to dpd_mfv3d_bwd*
+ *   with the chunk's surface clouds after the cloud's last tile); the query route -> gq, which points at query t0 of the chunk's first
+ *   cloud as q does in the forward: gq_cloud_stride = 3 M (>= 3 T, else DPD_E_DIM): cloud c's rows are written in place at
+ *   gq + c gq_cloud_stride (dq may be NULL); gq_cloud_stride = 0, one shared set: gq[t] = gq[t] + dq[(0, t)] + dq[(1, t)] + ... in ascending
+ *   cloud through dq [n, T, 3], continued from the accumulated value (the caller zeroes gq before the first chunk: chunk and tile
+ *   boundaries change no bit).  dfv = NULL: the surfaces need no gradient (gs half, slot product and scatter skipped; ucount, slot_vox,
+ *   gs, dXs may be NULL); gq = NULL: the queries need none (dq half skipped).  Both NULL: DPD_E_NULL.
+ * One predicate for all four: the forward's (dpd_field_gather's shapes), H % 64 == 0 and H <= 4096, and g1 [rows_p, H], gs [slot_cap, H]
+ * and dXs [slot_cap, KP] below the 4 GiB the GEMMs address.  NULL argument: DPD_E_NULL; n, T, k, H < 1, slot_cap !=
+ * dpd_field_slot_capacity(n, T, m), a stride below 3 T: DPD_E_DIM; a refused shape: DPD_E_UNSUPPORTED; all before any launch.          */
+int dpd_field_invert(const int32_t* vox, const int32_t* slot_of_vox, const int32_t* ucount, int n, int T, int m, int slot_cap,
+                     int32_t* slot_start, int32_t* qlist, int32_t* slot_vox, int32_t* slot_cloud, void* stream);
+int dpd_field_slot_sum(const float* g1, const int32_t* cnt, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_cloud,
+                       const float* W1p, int n, int T, int m, int k, int KP, int H, int slot_cap, float* gs, float* dq, long dq_cloud_stride,
+                       void* stream);
+int dpd_field_scatter(const float* dXs, const int32_t* ucount, const int32_t* slot_vox, int n, int T, int m, int k, int KP, int accumulate,
+                      float* dfv, void* stream);
+int dpd_field_bwd(const float* dpred, const float* maskr, const float* y, const float* h1, const float* h2, const float* h3,
+                  const int32_t* cnt, const int32_t* ucount, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox,
+                  const int32_t* slot_cloud, int n, int T, int m, int k, int KP, int H, int slot_cap, const dpd_decoder_params* p, float* dy,
+                  float* ga, float* gb, float* dq, float* gs, float* dXs, float* dfv, int accumulate, float* gq, long gq_cloud_stride,
+                  void* stream);
 
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in

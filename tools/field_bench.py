@@ -2,14 +2,17 @@
 plain entries (dpd_patch_rows_fwd + dpd_decoder_fwd: layer 1 once per row), in one process, at decoder width 1024 on
 synth.s2_modelnet_shaped clouds, C = 8 clouds with M = 64, 1024, 10 000 queries each (uniform in the cube):
 
-    field    dpdist_field(model, S, Q)                                  forward+backward: DPDistField, loss = (G * pred).sum()
+    field    dpdist_field(model, S, Q)                                  forward+backward: DPDistField, loss = (G * pred).sum(), with
+                                                                        backward="rows" and backward="slots"
     rows     the encoder, then per chunk the plain gather and dpd_decoder_fwd on [rows, KP]
 
     python tools/field_bench.py [--out profiles/field_bench.txt]
 
 The two forms have the same bits (checked with torch.equal before anything is timed) and walk the same chunks.  They alternate, `--rounds`
-calls after two warm-up calls, each timed with an in-stream device event pair.  The backward leg has no plain twin and is timed alone; it
-takes whole clouds of at most 8192 queries, so M = 10 000 has none.  No threshold is set on the times."""
+calls after two warm-up calls, each timed with an in-stream device event pair.  The backward leg has no plain twin: its two forms
+alternate with each other.  Before they are timed each form is run twice and must give the same bits both times, and the two forms must
+agree to 1e-3 of the largest gradient.  The rows backward takes whole clouds of at most 8192 queries, so at M = 10 000 only the slots
+backward runs.  No threshold is set on the times."""
 import argparse
 import json
 import os
@@ -98,21 +101,37 @@ def main():
         lines.append("M = %d: %d decoder rows in %d chunk(s); same bits" % (M, C * M, len(plan_chunks(C, M, a.max_rows))))
         lines.append("    forward            field %9.3f [%9.3f .. %9.3f]   plain rows %9.3f [%9.3f .. %9.3f]   ratio %6.2f"
                      % (med["field"], min(t["field"]), max(t["field"]), med["rows"], min(t["rows"]), max(t["rows"]), med["rows"] / med["field"]))
+        mods = {}
         if M <= min(a.max_rows, MAX_BWD_QUERIES):
-            mod = DPDistField(model, max_rows=a.max_rows)
+            mods["rows"] = DPDistField(model, max_rows=a.max_rows)
+        mods["slots"] = DPDistField(model, max_rows=a.max_rows, backward="slots")
 
-            def both():
-                s, q = S.detach().requires_grad_(True), Q.detach().requires_grad_(True)
-                (G * mod(s, q)).sum().backward()
-                return s.grad, q.grad
+        def both(mod):
+            s, q = S.detach().requires_grad_(True), Q.detach().requires_grad_(True)
+            (G * mod(s, q)).sum().backward()
+            return s.grad, q.grad
 
-            both(), both()
-            tb = [timed(both) for _ in range(a.rounds)]
-            shape["field_fwd_bwd_ms"] = round(float(np.median(tb)), 4)
-            lines.append("    forward+backward   field %9.3f [%9.3f .. %9.3f]" % (float(np.median(tb)), min(tb), max(tb)))
-        else:
-            shape["field_fwd_bwd_ms"] = None
-            lines.append("    forward+backward   not supported (the backward takes whole clouds of at most %d queries)" % MAX_BWD_QUERIES)
+        grads = {}
+        for form, mod in mods.items():
+            grads[form], again = both(mod), both(mod)
+            torch.cuda.synchronize()
+            if not all(torch.equal(x, y) for x, y in zip(grads[form], again)):
+                raise SystemExit("M = %d: the %s backward is not reproducible" % (M, form))
+        if "rows" in grads:
+            for x, y in zip(grads["rows"], grads["slots"]):
+                if float((x - y).abs().max()) > 1e-3 * float(x.abs().max()):
+                    raise SystemExit("M = %d: the two backward forms differ by %.3e" % (M, float((x - y).abs().max())))
+        tb = {form: [] for form in mods}
+        for _ in range(a.rounds):
+            for form, mod in mods.items():
+                tb[form].append(timed(lambda: both(mod)))
+        for form in ("rows", "slots"):
+            if form in tb:
+                shape["field_fwd_bwd_%s_ms" % form] = round(float(np.median(tb[form])), 4)
+                lines.append("    forward+backward   %-5s %9.3f [%9.3f .. %9.3f]" % (form, float(np.median(tb[form])), min(tb[form]), max(tb[form])))
+            else:
+                shape["field_fwd_bwd_%s_ms" % form] = None
+                lines.append("    forward+backward   rows  not supported (the rows backward takes whole clouds of at most %d queries)" % MAX_BWD_QUERIES)
         lines.append("")
     text = "\n".join(lines)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
