@@ -117,9 +117,7 @@ __global__ __launch_bounds__(256) void field_qreduce_kernel(const float* __restr
     qreduce_chain(dq, n, T3, gq);
 }
 
-}  // namespace dpd
 
-namespace {
 // THE shape predicate of the field's backward entries: a chunk the forward takes (field_shape_ok; k <= 0: the window is not known to the
 // caller) at a width slot_sum_rows covers (H <= 0: not known either), whose g1 [rows_p, H], gs [slot_cap, H] and slot product
 // dXs [slot_cap, KP] are addressable by the GEMM kernels.  -> the slot capacity, 0 = refused
@@ -133,7 +131,39 @@ int field_bwd_cap(int n, int T, int m, int k, int KP, int H) {
     if (H > 0 && !dpd::fits_gemm_offsets(((size_t)n * T + 31) / 32 * 32, (size_t)H)) return 0;      // g1 [rows_p, H]
     return cap;
 }
-}  // namespace
+
+// What follows the decoder chain in dpd_field_bwd, on the chunk's g1 rows (arguments as there, already checked; cap = the slot capacity):
+// the slot sum and the query route, then -- for the surfaces -- the slot product and the window scatter, then the chain of a shared
+// query set.  keep_gs: gs is formed even when no surface gradient is wanted (dpd_field_bwd_train contracts it with Xu).
+int field_routes(const float* g1, const int32_t* cnt, const int32_t* ucount, const int32_t* slot_start, const int32_t* qlist,
+                 const int32_t* slot_vox, const int32_t* slot_cloud, int n, int T, int m, int k, int KP, int H, int cap,
+                 const dpd_decoder_params* p, float* dq, float* gs, float* dXs, float* dfv, int accumulate, float* gq, long gq_cloud_stride,
+                 bool keep_gs, void* stream) {
+    const bool surface = dfv != nullptr, query = gq != nullptr;
+    const bool shared = query && gq_cloud_stride == 0;
+    hipStream_t s = (hipStream_t)stream;
+    // slot sum + query route: a cloud's own queries get their rows of gq in place, a shared set goes through dq [n, T, 3]
+    if (int rc = dpd_field_slot_sum(g1, cnt, slot_start, qlist, slot_cloud, p->W1p, n, T, m, k, KP, H, cap, (surface || keep_gs) ? gs : nullptr,
+                                    query ? (shared ? dq : gq) : nullptr, shared ? 3L * T : gq_cloud_stride, stream))
+        return rc;
+    if (surface) {
+        // slot product over the capacity (the dead rows of gs are zero): dXs [slot_cap, KP] = gs W1p^T, NN on the transposed copy
+        GemmF32Call f;
+        f.M = cap; f.N = KP; f.K = H;
+        f.A = gs; f.lda = H; f.B = p->W1pT; f.ldb = KP; f.C = dXs; f.ldc = KP;
+        f.epilogue = EPI_NONE; f.split_k = 1; f.s = s;
+        f.tile = ((long)((cap + 127) / 128) * ((KP + 127) / 128) >= 512) ? 30 : 32;      // the tile rule of the matrix's slot product
+        if (int rc = gemm_f32(f)) return rc;
+        if (int rc = dpd_field_scatter(dXs, ucount, slot_vox, n, T, m, k, KP, accumulate, dfv, stream)) return rc;
+    }
+    if (shared) {
+        StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)n * T * 12.0 + T * 24.0);
+        DPD_LAUNCH(field_qreduce_kernel, dim3((T * 3 + 255) / 256), dim3(256), 0, s, (const float*)dq, n, T * 3, gq);
+        DPD_CHECK_LAUNCH();
+    }
+    return 0;
+}
+}  // namespace dpd
 
 extern "C" int dpd_field_invert(const int32_t* vox, const int32_t* slot_of_vox, const int32_t* ucount, int n, int T, int m, int slot_cap,
                                 int32_t* slot_start, int32_t* qlist, int32_t* slot_vox, int32_t* slot_cloud, void* stream) {
@@ -204,30 +234,11 @@ extern "C" int dpd_field_bwd(const float* dpred, const float* maskr, const float
     const int cap = field_bwd_cap(n, T, m, k, KP, H);
     if (!cap) return DPD_E_UNSUPPORTED;
     if (slot_cap != cap) return DPD_E_DIM;
-    hipStream_t s = (hipStream_t)stream;
     const int rows_p = (int)(((long)n * T + 31) / 32 * 32);
     // layers 4..2: g3 -> ga, g2 -> gb, g1 -> ga (masked and padded queries and the pad rows: exact zeros through the mask)
     if (int rc = dpd_decoder_bwd_data(dpred, maskr, y, h1, h2, h3, rows_p, KP, H, p, DPD_F32, dy, ga, gb, ga, nullptr, nullptr, nullptr, 0, nullptr, 7,
                                       stream))
         return rc;
-    // slot sum + query route: a cloud's own queries get their rows of gq in place, a shared set goes through dq [n, T, 3]
-    if (int rc = dpd_field_slot_sum(ga, cnt, slot_start, qlist, slot_cloud, p->W1p, n, T, m, k, KP, H, cap, surface ? gs : nullptr,
-                                    query ? (shared ? dq : gq) : nullptr, shared ? 3L * T : gq_cloud_stride, stream))
-        return rc;
-    if (surface) {
-        // slot product over the capacity (the dead rows of gs are zero): dXs [slot_cap, KP] = gs W1p^T, NN on the transposed copy
-        GemmF32Call f;
-        f.M = cap; f.N = KP; f.K = H;
-        f.A = gs; f.lda = H; f.B = p->W1pT; f.ldb = KP; f.C = dXs; f.ldc = KP;
-        f.epilogue = EPI_NONE; f.split_k = 1; f.s = s;
-        f.tile = ((long)((cap + 127) / 128) * ((KP + 127) / 128) >= 512) ? 30 : 32;      // the tile rule of the matrix's slot product
-        if (int rc = gemm_f32(f)) return rc;
-        if (int rc = dpd_field_scatter(dXs, ucount, slot_vox, n, T, m, k, KP, accumulate, dfv, stream)) return rc;
-    }
-    if (shared) {
-        StageProf prof(stream, DPD_STAGE_SMALL_REDUCE, (double)n * T * 12.0 + T * 24.0);
-        DPD_LAUNCH(field_qreduce_kernel, dim3((T * 3 + 255) / 256), dim3(256), 0, s, (const float*)dq, n, T * 3, gq);
-        DPD_CHECK_LAUNCH();
-    }
-    return 0;
+    return field_routes(ga, cnt, ucount, slot_start, qlist, slot_vox, slot_cloud, n, T, m, k, KP, H, cap, p, dq, gs, dXs, dfv, accumulate, gq,
+                        gq_cloud_stride, false, stream);
 }

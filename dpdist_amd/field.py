@@ -203,12 +203,14 @@ class _FieldFn(torch.autograd.Function):
     """(pred, mask) of the surfaces at the queries as one autograd node"""
 
     @staticmethod
-    def forward(ctx, surfaces, queries, P, m, sigma, max_rows, cS, cQ, mode):
+    def forward(ctx, surfaces, queries, P, m, sigma, max_rows, cS, cQ, mode, flat=None):
+        # flat: P.flat as an input of the node (decoder_grad), else None: the decoder is frozen and the node is what it was
         ctx.cfg = (P, m, sigma, max_rows, mode)
         ctx.counts = (cS, cQ)                                           # int32 device tensors | None: no gradient exists w.r.t. counts
         ctx.set_materialize_grads(False)
         S, Q = surfaces.detach().contiguous(), queries.detach().contiguous()
-        ctx.save_for_backward(S, Q)                                     # activation checkpointing: the two inputs only
+        ctx.train = flat is not None
+        ctx.save_for_backward(*((S, Q) if flat is None else (S, Q, flat)))      # activation checkpointing: the inputs only
         pred, mask = _forward(P, m, sigma, S, Q, cS, cQ, Q.dim() == 2, max_rows)
         ctx.mark_non_differentiable(mask)
         return pred, mask
@@ -217,18 +219,34 @@ class _FieldFn(torch.autograd.Function):
     def backward(ctx, gpred, _gmask):
         P, m, sigma, max_rows, mode = ctx.cfg
         cS, cQ = ctx.counts
-        S, Q = ctx.saved_tensors
+        S, Q = ctx.saved_tensors[:2]
         needS, needQ = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if gpred is None or not (needS or needQ):
-            return (None,) * 9
+        needW = ctx.train and ctx.needs_input_grad[9]
+        if gpred is None or not (needS or needQ or needW):
+            return (None,) * (10 if ctx.train else 9)
         shared = Q.dim() == 2
         C, W, M, dev = S.shape[0], S.shape[1], Q.shape[-2], S.device
         lib = L.load()
-        flat = P.flat
+        flat = ctx.saved_tensors[2] if ctx.train else P.flat
         with torch.cuda.device(dev), torch.no_grad():
             s = L.cur_stream()
             g = gpred.to(torch.float32).contiguous()
-            cp = L.make_params(*P.views(flat), *P.transposed(flat))
+            if ctx.train:
+                # an optimizer that writes through raw pointers bumps no version, so the cache of P.transposed would serve the weights of
+                # the step before: with the decoder in training its transposed copies are derived afresh in every backward
+                wT = [torch.empty(P.H, P.H, device=dev), torch.empty(P.H, P.H, device=dev), torch.empty(P.H, P.KP, device=dev)]
+                _check(lib.dpd_weights_transpose(L.make_params(*P.views(flat)), P.KP, P.H, L.ptr(wT[0]), L.ptr(wT[1]), L.ptr(wT[2]), s),
+                       "dpd_weights_transpose")
+            else:
+                wT = P.transposed(flat)
+            cp = L.make_params(*P.views(flat), *wT)
+            gW = torch.zeros_like(flat) if needW else None                  # the alignment gaps between the segments stay zero
+            dW = [L.ptr(t) for t in P.views(gW)] if needW else None
+            wws = None
+            if needW:
+                nbytes = max(lib.dpd_field_bwd_train_workspace_bytes(n, T, m, P.k, P.KP, P.H) for _, n, _, T in plan_chunks(C, M, max_rows))
+                wws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            first = [True]                                                  # the first chunk stores the weight gradients, the later ones add
             fv = _encode(lib, s, S, m, sigma, cS)
             gS = torch.empty_like(S) if needS else None
             gQ = (torch.zeros_like(Q) if shared else torch.empty_like(Q)) if needQ else None
@@ -265,6 +283,15 @@ class _FieldFn(torch.autograd.Function):
                 _check(lib.dpd_field_invert(L.ptr(ck.vox), L.ptr(ck.slot), L.ptr(ck.ucount), n, T, m, ck.cap, L.ptr(ck.slot_start), L.ptr(ck.qlist),
                                             L.ptr(ck.slot_vox), L.ptr(ck.slot_cloud), s), "dpd_field_invert")
                 gq = None if not needQ else (gQ[t0:] if shared else gQ[c0:, t0:])
+                if needW:
+                    _check(lib.dpd_field_bwd_train(L.ptr(ck.dpred), L.ptr(ck.maskr), L.ptr(ck.y), L.ptr(ck.h1), L.ptr(ck.h2), L.ptr(ck.h3),
+                                                   L.ptr(ck.cnt), L.ptr(ck.ucount), L.ptr(ck.slot_start), L.ptr(ck.qlist), L.ptr(ck.slot_vox),
+                                                   L.ptr(ck.slot_cloud), L.ptr(ck.Xu), ck.cap, L.ptr(ck.Xt), n, T, m, P.k, P.KP, P.H, ck.cap, cp,
+                                                   L.ptr(ck.dy), L.ptr(ck.ga), L.ptr(ck.gb), L.ptr(ck.dq), L.ptr(ck.gs), L.ptr(ck.dXs),
+                                                   L.ptr(dfv_slots), int(t0 > 0), L.ptr(gq), 0 if shared else 3 * M, *dW, int(not first[0]),
+                                                   L.ptr(wws), wws.numel(), s), "dpd_field_bwd_train")
+                    first[0] = False
+                    return dfv_slots
                 _check(lib.dpd_field_bwd(L.ptr(ck.dpred), L.ptr(ck.maskr), L.ptr(ck.y), L.ptr(ck.h1), L.ptr(ck.h2), L.ptr(ck.h3), L.ptr(ck.cnt),
                                          L.ptr(ck.ucount), L.ptr(ck.slot_start), L.ptr(ck.qlist), L.ptr(ck.slot_vox), L.ptr(ck.slot_cloud), n, T, m,
                                          P.k, P.KP, P.H, ck.cap, cp, L.ptr(ck.dy), L.ptr(ck.ga), L.ptr(ck.gb), L.ptr(ck.dq), L.ptr(ck.gs),
@@ -278,7 +305,7 @@ class _FieldFn(torch.autograd.Function):
                 if needS and t0 + ck.T == M:      # after the last tile of a cloud, or once per chunk of whole clouds
                     encoder_bwd(c0, ck.n, dfv)
             del cp
-        return gS, gQ, None, None, None, None, None, None, None
+        return (gS, gQ) + (None,) * 7 + ((gW,) if ctx.train else ())
 
 
 class DPDistField(torch.nn.Module):
@@ -305,15 +332,31 @@ class DPDistField(torch.nn.Module):
     they stay inside the oracle's bar.  Needs H % 64 == 0 and H <= 4096 (ValueError before any launch).  The values of the two forms
     differ by rounding only; their bits differ.
 
+    decoder_grad=True (needs backward="slots"; with "rows" the constructor raises a ValueError): the decoder is no longer frozen.  When
+    P.flat requires grad and grad is enabled, it is an input of the node and the backward returns its gradient in the flat segment layout
+    (dpd_field_bwd_train), as the training node of DPDistModel does: after backward() P.flat.grad holds it, P.view(name, P.flat.grad) is a
+    variable's block, P.tf_state_dict(P.flat.grad) has it under the TF names, and the alignment gaps between the segments are exact zeros.
+    Layer 1's weight gradient contracts its window rows once per slot (Xu gs) and only its 32 tail columns over the rows; the chunks of the
+    plan add up in ascending order.  Surfaces, queries and the decoder may need gradients in any combination; the share of an input that
+    needs none is skipped.  The forward is unchanged (the launches and bits of dpdist_field).  For a given max_rows the weight gradients
+    are the same bits on every run; across different max_rows they differ by rounding only, because chunks add in ascending order.  The
+    surface and query gradients are bit for bit those of the frozen backward="slots" node.  The transposed weight copies are derived
+    afresh in every backward, so an optimizer that updates P.flat through raw pointers (optim.TFAdam) needs no invalidate_derived() here.
+    decoder_grad=False (the default): the node, its launches and every bit are those described above.
+
     counts / query_counts (keywords of forward): as dpdist_field.  The gradients at padded queries and padded surface points are 0; there
     is no gradient w.r.t. the counts.  An input that needs no gradient gets None and its share of the work is skipped.  Argument checks
     and errors as dpdist_field, before the first launch."""
 
-    def __init__(self, model_or_params, max_rows=16384, Embedding_Size=None, sigma3dmfv=None, backward="rows"):
+    def __init__(self, model_or_params, max_rows=16384, Embedding_Size=None, sigma3dmfv=None, backward="rows", decoder_grad=False):
         super().__init__()
         if backward not in BACKWARDS:
             raise ValueError("backward must be one of %s, not %r" % (BACKWARDS, backward))
+        if decoder_grad and backward != "slots":
+            raise ValueError("decoder_grad=True needs backward=\"slots\" (the field never holds the rows that backward=%r would contract "
+                             "the layer-1 weight gradient with)" % (backward,))
         self.backward = backward
+        self.decoder_grad = bool(decoder_grad)
         self._src = (model_or_params, Embedding_Size, sigma3dmfv)
         _resolve(model_or_params, Embedding_Size, sigma3dmfv)
         if int(max_rows) < 1:
@@ -322,12 +365,16 @@ class DPDistField(torch.nn.Module):
 
     def forward(self, surfaces, queries, return_mask=False, *, counts=None, query_counts=None):
         mp, es, sg = self._src
-        want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (surfaces, queries))
+        flat = getattr(getattr(mp, "params_", mp), "flat", None)
+        train = self.decoder_grad and torch.is_grad_enabled() and torch.is_tensor(flat) and flat.requires_grad
+        want_grad = train or (torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (surfaces, queries)))
         P, m, sigma, S, Q, cS, cQ, shared = _prepare(mp, surfaces, queries, counts, query_counts, self.max_rows, es, sg,
                                                      backward=self.backward if want_grad else None)
         if not want_grad:
             with torch.no_grad():
                 pred, mask = _forward(P, m, sigma, S, Q, cS, cQ, shared, self.max_rows)
+        elif train:
+            pred, mask = _FieldFn.apply(surfaces, queries, P, m, sigma, self.max_rows, cS, cQ, self.backward, P.flat)
         else:
             pred, mask = _FieldFn.apply(surfaces, queries, P, m, sigma, self.max_rows, cS, cQ, self.backward)
         return (pred, mask) if return_mask else pred

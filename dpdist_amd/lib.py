@@ -121,6 +121,10 @@ SIGNATURES = {
     "dpd_field_slot_sum": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_void_p, c_long, c_void_p]),
     "dpd_field_scatter": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 2),
     "dpd_field_bwd": (c_int, [c_void_p] * 12 + [c_int] * 7 + [POINTER(DecoderParams)] + [c_void_p] * 7 + [c_int, c_void_p, c_long, c_void_p]),
+    # ... with the decoder's own gradients (csrc/field_train.hip)
+    "dpd_field_bwd_train_workspace_bytes": (c_size_t, [c_int] * 6),
+    "dpd_field_bwd_train": (c_int, [c_void_p] * 12 + [c_void_p, c_int, c_void_p] + [c_int] * 7 + [POINTER(DecoderParams)] + [c_void_p] * 7 +
+                            [c_int, c_void_p, c_long] + [c_void_p] * 8 + [c_int, c_void_p, c_size_t, c_void_p]),
     "dpd_decoder_out_asloss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "dpd_decoder_out_asloss_planes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecoderParams), c_float, c_void_p, c_void_p, c_void_p,

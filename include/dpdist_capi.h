@@ -495,6 +495,34 @@ int dpd_field_bwd(const float* dpred, const float* maskr, const float* y, const 
                   float* ga, float* gb, float* dq, float* gs, float* dXs, float* dfv, int accumulate, float* gq, long gq_cloud_stride,
                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DECODER GRADIENTS of the per-point field (DPD_F32): dpd_field_bwd with the gradients of the decoder's eight variables, per chunk of the
+ * field's plan.  Arguments as dpd_field_bwd, plus the chunk's Xu [KP - 32, ldu] and Xt [rows_p, 32] of dpd_field_gather and eight outputs
+ * in the layout of the flat parameter buffer: dW1p [KP, H], db1 [H], dW2 [H, H], db2 [H], dW3 [H, H], db3 [H], dW4 [H, 3], db4 [3]
+ * (all eight, or all NULL = no weight gradient wanted: the call is then dpd_field_bwd).
+ *   dW1p[0 : KP - 32]  = Xu gs        ONCE PER SLOT: the window part of a row is column uid[r] of Xu, so the sum over the rows of
+ *                                     x_r (x) g1_r is Xu times the slot sums gs [slot_cap, H] that dpd_field_slot_sum forms;
+ *   dW1p[KP - 32 : KP] = Xt^T g1      over the rows ([32, H]; the rows E + 3 .. KP - 1, the zero pad of Xt, are exact +0.0);
+ *   db1 = colsum(g1);  dW2 = h1^T g2, db2 = colsum(g2);  dW3 = h2^T g3, db3 = colsum(g3);  dW4 = h3^T dy, db4 = colsum(dy).
+ * The decoder chain runs by phases (1, dW3 / dW4; 2, dW2; 4, the layer-1 parts), because g1 overwrites g3 in ga; g3, g2, g1 and with them
+ * dfv and gq have the bits of dpd_field_bwd (the same launches), with and without the weight outputs.  dfv = gq = NULL with the weight
+ * outputs: the slot product, the scatter and the query route are skipped, gs is still formed (gs must then be given).
+ * Xu is NOT const: nothing beyond the cnt[1] live columns is written by the gather and 0 * NaN is NaN, so the entry ZEROES the columns
+ * cnt[1] .. slot_cap - 1 of Xu before the product; the result does not depend on what they held.
+ * accumulate_w != 0: the chunk's gradients are ADDED onto what the eight outputs hold (chunks and tiles add up in ascending plan
+ * order); == 0: stored.  The chunk's own contribution is formed completely first, in the workspace, so its bits do not depend on what
+ * the outputs held.  Deterministic: no float atomics, one summation order per element (two-step column sums over fixed row chunks).
+ * ws: dpd_field_bwd_train_workspace_bytes(n, T, m, k, KP, H) bytes (0 = refused shape), 256-byte aligned.
+ * NULL argument: DPD_E_NULL; the dims of dpd_field_bwd, ldu < slot_cap: DPD_E_DIM; the predicate of dpd_field_bwd, ldu % 4, or
+ * Xu [KP - 32, ldu] beyond the 4 GiB the GEMMs address: DPD_E_UNSUPPORTED; a small workspace: DPD_E_WORKSPACE; all before any launch. */
+size_t dpd_field_bwd_train_workspace_bytes(int n, int T, int m, int k, int KP, int H);
+int dpd_field_bwd_train(const float* dpred, const float* maskr, const float* y, const float* h1, const float* h2, const float* h3,
+                        const int32_t* cnt, const int32_t* ucount, const int32_t* slot_start, const int32_t* qlist, const int32_t* slot_vox,
+                        const int32_t* slot_cloud, float* Xu, int ldu, const float* Xt, int n, int T, int m, int k, int KP, int H,
+                        int slot_cap, const dpd_decoder_params* p, float* dy, float* ga, float* gb, float* dq, float* gs, float* dXs,
+                        float* dfv, int accumulate, float* gq, long gq_cloud_stride, float* dW1p, float* db1, float* dW2, float* db2,
+                        float* dW3, float* db3, float* dW4, float* db4, int accumulate_w, void* ws, size_t ws_bytes, void* stream);
+
 /* `dtype` of the decoder entry points = compute type of the three wide layers (inputs/outputs are always fp32):
  *   DPD_F32     exact fp32 on the fp32 matrix-core instruction (bitwise an fmaf chain), no workspace needed in
  *               dpd_decoder_fwd / dpd_decoder_bwd_data (ws may be NULL);

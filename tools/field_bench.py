@@ -12,7 +12,13 @@ The two forms have the same bits (checked with torch.equal before anything is ti
 calls after two warm-up calls, each timed with an in-stream device event pair.  The backward leg has no plain twin: its two forms
 alternate with each other.  Before they are timed each form is run twice and must give the same bits both times, and the two forms must
 agree to 1e-3 of the largest gradient.  The rows backward takes whole clouds of at most 8192 queries, so at M = 10 000 only the slots
-backward runs.  No threshold is set on the times."""
+backward runs.  No threshold is set on the times.
+
+--decoder-grad adds a leg per M: forward + backward with the DECODER's gradients alone (DPDistField(backward="slots", decoder_grad=True),
+dpd_field_bwd_train: layer 1's weight gradient once per slot) against the same eight gradients composed over the same chunks from the
+row entries (dpd_patch_rows_fwd, dpd_decoder_fwd, dpd_decoder_bwd_data with its small-gradient by-products, dpd_decoder_bwd_weights x 3
+on the materialised [rows, KP] matrix).  Before they are timed the two must agree per variable within 2e-4 max(1, max |gradient|), the
+relative bar of the tests.  A record, not a gate."""
 import argparse
 import json
 import os
@@ -60,6 +66,68 @@ def plain_rows(model, S, Q, max_rows):
     return out
 
 
+def rows_weight_grads(model, S, Q, G, max_rows):
+    """the eight decoder gradients of (G * pred).sum() composed from the row entries over the chunks of plan_chunks -> flat [numel]"""
+    lib, s, P = L.load(), L.cur_stream(), model.params_
+    C, M, dev = S.shape[0], Q.shape[1], S.device
+    params, wT = P.views(), P.transposed()
+    fv = ops.mfv3d_fwd(S, 8, 0.125)
+    total, part = torch.zeros_like(P.flat), torch.zeros_like(P.flat)
+    d = P.views(part)
+    buf = {}
+    for c0, n, t0, T in plan_chunks(C, M, max_rows):
+        rows, rows_p = n * T, (n * T + 31) // 32 * 32
+        if (n, T) not in buf:
+            buf[n, T] = (torch.zeros(rows_p, P.KP, device=dev), torch.zeros(rows_p, device=dev), torch.empty(rows_p, device=dev, dtype=torch.int32),
+                         torch.zeros(rows_p, 3, device=dev), ops.workspace(rows_p, P.KP, P.H, dev))
+        X, mask, vox, dpred, ws = buf[n, T]
+        q = Q[c0:c0 + n, t0:t0 + T].contiguous()
+        L.check(lib.dpd_patch_rows_fwd(L.ptr(q), L.ptr(fv[c0:]), n, T, 8, P.k, P.KP, L.ptr(X), L.ptr(mask), L.ptr(vox), None, s), "dpd_patch_rows_fwd")
+        h1, h2, h3, y, _ = ops.decoder_fwd(X, mask, params, P.H)
+        dpred[:rows].copy_(G[c0:c0 + n, t0:t0 + T].reshape(rows, 3))
+        dy, g3, g2, g1, _ = ops.decoder_bwd_data(dpred, mask, y, h1, h2, h3, params, P.KP, False, small_grads=(None, None, d[5], d[6], d[7]),
+                                                 transposed=wT)
+        ops.decoder_bwd_weights(1, X, g1, rows_p, d[0], d[1], ws)
+        ops.decoder_bwd_weights(2, h1, g2, rows_p, d[2], d[3], ws)
+        ops.decoder_bwd_weights(3, h2, g3, rows_p, d[4], None, ws)
+        total.add_(part)
+    return total
+
+
+def decoder_grad_leg(a, model, S, Q, G, M, shape, lines):
+    P = model.params_
+    mod = DPDistField(model, max_rows=a.max_rows, backward="slots", decoder_grad=True)
+
+    def slot_form():
+        P.flat.grad = None
+        (G * mod(S, Q)).sum().backward()
+        return P.flat.grad
+
+    P.flat.requires_grad_(True)
+    try:
+        forms = {"slots": slot_form, "rows": lambda: rows_weight_grads(model, S, Q, G, a.max_rows)}
+        got, want = forms["slots"]().clone(), forms["rows"]()
+        torch.cuda.synchronize()
+        if not torch.equal(got, forms["slots"]()):
+            raise SystemExit("M = %d: the decoder gradients are not reproducible" % M)
+        for name in ("W1p", "b1", "W2", "b2", "W3", "b3", "W4", "b4"):
+            x, y = P.view(name, got), P.view(name, want)
+            if float((x - y).abs().max()) > 2e-4 * max(1.0, float(y.abs().max())):
+                raise SystemExit("M = %d: the two forms of d%s differ by %.3e" % (M, name, float((x - y).abs().max())))
+        forms["rows"]()
+        t = {"slots": [], "rows": []}
+        for _ in range(a.rounds):
+            for form in ("slots", "rows"):
+                t[form].append(timed(forms[form]))
+    finally:
+        P.flat.requires_grad_(False)
+        P.flat.grad = None
+    med = {form: float(np.median(v)) for form, v in t.items()}
+    shape["decoder_grad_slots_ms"], shape["decoder_grad_rows_ms"] = round(med["slots"], 4), round(med["rows"], 4)
+    lines.append("    decoder gradients  slots %9.3f [%9.3f .. %9.3f]   row entries %8.3f [%9.3f .. %9.3f]   ratio %6.2f"
+                 % (med["slots"], min(t["slots"]), max(t["slots"]), med["rows"], min(t["rows"]), max(t["rows"]), med["rows"] / med["slots"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clouds", type=int, default=8)
@@ -68,6 +136,7 @@ def main():
     ap.add_argument("--queries", type=int, nargs="+", default=[64, 1024, 10000])
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--max-rows", type=int, default=16384)
+    ap.add_argument("--decoder-grad", action="store_true", help="add the forward+backward leg with the decoder's gradients (see above)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "field_bench.txt"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -79,7 +148,8 @@ def main():
     S = torch.tensor(synth.s2_modelnet_shaped(C, a.points, 100)[0], device=dev)
     res = {"device": torch.cuda.get_device_name(0), "C": C, "W": a.points, "H": H, "m": 8, "k": 5, "max_rows": a.max_rows, "rounds": a.rounds,
            "shapes": {}}
-    lines = ["# tools/field_bench.py --clouds %d --points %d --width %d --rounds %d --max-rows %d" % (C, a.points, H, a.rounds, a.max_rows),
+    lines = ["# tools/field_bench.py --clouds %d --points %d --width %d --rounds %d --max-rows %d%s"
+             % (C, a.points, H, a.rounds, a.max_rows, " --decoder-grad" if a.decoder_grad else ""),
              "# device: %s; exact fp32; ms per call (in-stream device event pairs), median [min .. max] of %d alternating calls after 2 warm-up calls"
              % (res["device"], a.rounds), ""]
     for M in a.queries:
@@ -132,6 +202,8 @@ def main():
             else:
                 shape["field_fwd_bwd_%s_ms" % form] = None
                 lines.append("    forward+backward   rows  not supported (the rows backward takes whole clouds of at most %d queries)" % MAX_BWD_QUERIES)
+        if a.decoder_grad:
+            decoder_grad_leg(a, model, S, Q, G, M, shape, lines)
         lines.append("")
     text = "\n".join(lines)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
