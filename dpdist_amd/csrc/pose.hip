@@ -213,11 +213,18 @@ extern "C" size_t dpd_pose_refine_workspace_bytes(int B, int N, int out_features
 
 extern "C" int dpd_pose_refine(const dpd_pose_net* net, const float* src, const float* tmpl, int B, int N, int loops, float lim_rot_deg,
                                const float* drop_mask, void* ws, size_t ws_bytes, float* moved, float* T_out, float* pred_out, void* stream) {
+    return dpd_pose_refine_pool(net, src, tmpl, B, N, loops, lim_rot_deg, DPD_POOL_MAX, drop_mask, ws, ws_bytes, moved, T_out, pred_out, stream);
+}
+
+extern "C" int dpd_pose_refine_pool(const dpd_pose_net* net, const float* src, const float* tmpl, int B, int N, int loops, float lim_rot_deg, int pool,
+                                    const float* drop_mask, void* ws, size_t ws_bytes, float* moved, float* T_out, float* pred_out, void* stream) {
     using namespace dpd;
     if (!net || !src || !tmpl || !ws || !moved || !T_out) return DPD_E_NULL;
     if (int rc = check_point_layers(net)) return rc;
     if (int rc = check_head_layers(net, true)) return rc;
     if (B <= 0 || N <= 0 || loops <= 0) return DPD_E_DIM;
+    if (!pool_known(pool)) return DPD_E_UNSUPPORTED;
+    const bool avg = pool == DPD_POOL_AVG;                 // the shared MLP's epilogue only: the head and the pose chain do not look at the pool
     const int OUT = net->out_features;
     if (OUT != 1024) return DPD_E_UNSUPPORTED;             // the reference's width (models/ipcr_model.py:226); the head kernel's K is a template parameter
     if (((uintptr_t)ws & 15) != 0) return DPD_E_UNSUPPORTED;
@@ -234,7 +241,7 @@ extern "C" int dpd_pose_refine(const dpd_pose_net* net, const float* src, const 
     const float* Tcur = nullptr;
     for (int it = 0; it < loops; ++it) {
         if (it == 0) {
-            if (int rc = launch_pose_point<false>(cur, tmpl, B, 2 * B, N, pw, OUT, w.f, PointSave{}, PoseMove{}, s)) return rc;
+            if (int rc = launch_pose_point<false>(cur, tmpl, B, 2 * B, N, pw, OUT, w.f, PointSave{}, PoseMove{}, avg, s)) return rc;
             // the template never moves: its half of fc1's sum (W1[:, OUT:] f_tmpl + b1) once per call, every loop then contracts the source's
             // half only (4 MB of weights per loop instead of 8)
             if (int rc = launch_pose_fc(net, 0, FcIn{f_tmpl, nullptr, OUT, OUT}, /*wcol0*/ OUT, /*rowbias*/ nullptr, /*relu*/ false, /*mask*/ nullptr, w.tb, B, s)) return rc;
@@ -242,7 +249,7 @@ extern "C" int dpd_pose_refine(const dpd_pose_net* net, const float* src, const 
             float* nxt = w.cloud[(it - 1) & 1];
             float* Tn = w.T[(it - 1) & 1];
             const PoseMove mv{w.h3, net->Wh[3], net->bh[3], Tcur, nxt, Tn, pred_out ? pred_out + (size_t)(it - 1) * B * 7 : (float*)nullptr, lim_rad, 256};
-            if (int rc = launch_pose_point<false>(cur, nullptr, B, B, N, pw, OUT, w.f, PointSave{}, mv, s)) return rc;
+            if (int rc = launch_pose_point<false>(cur, nullptr, B, B, N, pw, OUT, w.f, PointSave{}, mv, avg, s)) return rc;
             cur = nxt;
             Tcur = Tn;
         }

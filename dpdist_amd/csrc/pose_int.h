@@ -21,7 +21,8 @@ __device__ __forceinline__ int mfma_row(int r, int l) { return (r & 3) + 8 * (r 
 
 // What the training evaluation keeps of the shared MLP's forward (pose_point.hip writes it, pose_point_bwd.hip reads it): the four hidden
 // activations and the TIE MASK of the max pool -- W = ceil(N / 64) words per (cloud, column), ties[cloud][w][column]; bit b of word w is set
-// iff point 64 w + b attains the column's maximum and that maximum is positive.
+// iff point 64 w + b attains the column's maximum and that maximum is positive.  Under the average pool the same buffer holds the GATE
+// words: bit b of word w is set iff point 64 w + b is a real point and its layer-5 pre-activation is > 0.
 struct PointSave {
     float* h[4];                    // [clouds * N, 64] x 3, [clouds * N, 128]
     unsigned long long* ties;       // [clouds, ceil(N / 64), OUT]
@@ -46,10 +47,12 @@ struct PoseMove {
 // ---- pose_point.hip ----
 int check_point_layers(const dpd_pose_net* net);           // DPD_E_NULL unless net and its five Wp / bp are there
 PointNetW point_net_of(const dpd_pose_net* net);
-// pose_point_kernel<TRAIN> over `clouds` clouds (cloud c < nA: ptsA[c], else ptsB[c - nA]) -> f [clouds, OUT]
+// pose_point_kernel<TRAIN, avg> over `clouds` clouds (cloud c < nA: ptsA[c], else ptsB[c - nA]) -> f [clouds, OUT]; avg: the average pool
+// (f = sum / N, PointSave::ties receives the GATE words) instead of the max pool
 template <bool TRAIN>
 int launch_pose_point(const float* ptsA, const float* ptsB, int nA, int clouds, int N, const PointNetW& pw, int OUT, float* f, const PointSave& sv,
-                      const PoseMove& mv, hipStream_t s);
+                      const PoseMove& mv, bool avg, hipStream_t s);
+inline bool pool_known(int pool) { return pool == DPD_POOL_MAX || pool == DPD_POOL_AVG; }      // enum dpd_pool; anything else: DPD_E_UNSUPPORTED
 
 // ---- pose_head.hip ----
 int check_head_layers(const dpd_pose_net* net, bool biases);      // DPD_E_NULL unless net and its four Wh (and, with `biases`, bh) are there

@@ -3,6 +3,8 @@
 //   <false>  the forward-only refinement (dpd_pose_refine in pose.hip, through launch_pose_point): loops 2..n move the cloud first (PoseMove)
 //   <true>   the training evaluation (dpd_pose_point_fwd_train, here): hidden activations and the max pool's tie masks stored for
 //            pose_point_bwd.hip
+// Second flag AVG: the average-pool encoder (models/ipcr_model.py:236-271, --pn_pool avg): the epilogue sums relu(layer 5) over the cloud's
+// points instead of taking their maximum, and the training form stores GATE words instead of tie words (see pose_point_kernel).
 // What the units of the pose network share: pose_int.h.  fp32 throughout (MFMA fp32 / FMA).
 #include "pose_int.h"
 #include "pose_math.h"
@@ -86,7 +88,14 @@ __device__ __forceinline__ void save_rows(float* __restrict__ dst, const float* 
         *reinterpret_cast<float4*>(dst + (size_t)r * W + 4 * c4) = *reinterpret_cast<const float4*>(src_lds + r * stride + 4 * c4);
     }
 }
-template <bool TRAIN>
+// AVG (models/ipcr_model.py:236-271, tf_util.avg_pool2d over the points): f = (sum over the cloud's real points of relu(layer 5)) / (float)N.
+// The sum has ONE order: inside a pass every lane adds the rows it holds, ascending (rows r & 3 + 8 (r >> 2) + 4 half of the first 32-row tile,
+// then of the second), the lower lane half's partial sum and the upper one's are added (lower + upper), and the pass sums are added to the
+// running sum passes ascending; the quotient is one IEEE division, not a product with a reciprocal.  The origin rows that pad a partial pass
+// are left out of the sum.  TRAIN stores, in the tie words' buffer and layout, the GATE words: bit b of word w is set iff point 64 w + b is a
+// real point and its layer-5 pre-activation is > 0 (the ReLU gate: every such point carries gradient df / N).  No running maximum, no stale
+// word.  TRAIN and !TRAIN run the same epilogue: the same feature bits.
+template <bool TRAIN, bool AVG>
 __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict__ ptsA, const float* __restrict__ ptsB, int nA, int N,
                                                          PointNetW net, int OUT, int row0, float* __restrict__ f, PointSave sv, PoseMove mv) {
     extern __shared__ __attribute__((aligned(16))) float lds[];      // (float4 reads; the alignment the one-unit build took from pose_bwd_cloud_kernel's declaration)
@@ -95,7 +104,7 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
     const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)lds;
     const float* pts = c < nA ? ptsA + (size_t)c * N * 3 : ptsB + (size_t)(c - nA) * N * 3;
     const float* W5s = net.W[4] + (size_t)slice * kSlice * 128;
-    float vmax = 0.f;                                          // column wv * 32 + (l & 31) of the slice, over this lane's rows; relu outputs are >= 0
+    float vmax = 0.f;                                          // column wv * 32 + (l & 31) of the slice, over this lane's rows; relu outputs are >= 0 (AVG: the column's running sum)
     float runmax = 0.f;                                        // TRAIN: the column's maximum over the passes so far (all of its points)
     unsigned alive = 0, stale = 0;                             // TRAIN: passes whose word stands / has to be zeroed (see above)
     const int NW = (N + kPP - 1) / kPP;
@@ -198,6 +207,30 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
         if (TRAIN && slice == 0) save_rows<TRAIN>(sv.h[3] + ((size_t)(row0 + c) * N + p0) * 128, lds + kHB, np, 128, kS128, t);
         // layer 5 (slice): waves 0, 1 on the first half of the slice, 2, 3 on the second; max over this lane's valid points
         mfma_layer<128, 2>(lds + kHB, lds + (wv < 2 ? kW5a : kW5b), lds[kBias + 320 + wv * 32 + (l & 31)], 0, (wv & 1) * 32, c0, c1);
+        if (AVG) {
+            float ps = 0.f;                                    // this lane's rows of the pass, ascending
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (mfma_row(r, l) < np) ps += fmaxf(c0[r], 0.f);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (32 + mfma_row(r, l) < np) ps += fmaxf(c1[r], 0.f);
+            vmax += sum_x32(ps);                               // lower lane half + upper (the other rows of the same column), in both; passes ascending
+            if (TRAIN) {
+                unsigned lo = 0, hi = 0;                       // rows 0..31 come from c0, rows 32..63 from c1
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = mfma_row(r, l);
+                    if (row < np && c0[r] > 0.f) lo |= 1u << row;
+                    if (32 + row < np && c1[r] > 0.f) hi |= 1u << row;
+                }
+                lo |= (unsigned)__shfl_xor((int)lo, 32, 64);
+                hi |= (unsigned)__shfl_xor((int)hi, 32, 64);
+                if ((l >> 5) == 0)
+                    sv.ties[((size_t)(row0 + c) * NW + p0 / kPP) * OUT + slice * kSlice + wv * 32 + (l & 31)] = ((unsigned long long)hi << 32) | lo;
+            }
+            continue;
+        }
         float pmax = 0.f;                                      // this pass alone
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -228,6 +261,10 @@ __global__ __launch_bounds__(256) void pose_point_kernel(const float* __restrict
             if ((l >> 5) == 0) sv.ties[((size_t)(row0 + c) * NW + w) * OUT + slice * kSlice + col] = ((unsigned long long)hi << 32) | lo;
         }
     }
+    if (AVG) {                                                 // (both lane halves hold the column's sum)
+        if ((l >> 5) == 0) f[(size_t)(row0 + c) * OUT + slice * kSlice + wv * 32 + (l & 31)] = vmax / (float)N;
+        return;
+    }
     if (TRAIN && (l >> 5) == 0) {
         while (stale) {
             const int w = __ffs((int)stale) - 1;
@@ -257,32 +294,47 @@ dpd::PointNetW dpd::point_net_of(const dpd_pose_net* net) {
     return pw;
 }
 
-template <bool TRAIN>
-int dpd::launch_pose_point(const float* ptsA, const float* ptsB, int nA, int clouds, int N, const PointNetW& pw, int OUT, float* f, const PointSave& sv,
-                           const PoseMove& mv, hipStream_t s) {
+namespace dpd {
+template <bool TRAIN, bool AVG>
+static int launch_pose_point_form(const float* ptsA, const float* ptsB, int nA, int clouds, int N, const PointNetW& pw, int OUT, float* f,
+                                  const PointSave& sv, const PoseMove& mv, hipStream_t s) {
     static LdsOptIn opt_in;                                  // of this instantiation's kernel
     const size_t lds = (size_t)kPointLds * sizeof(float);
-    if (int rc = ensure_dyn_lds(opt_in, (const void*)pose_point_kernel<TRAIN>, lds)) return rc;
-    DPD_LAUNCH(pose_point_kernel<TRAIN>, dim3((unsigned)clouds, (unsigned)(OUT / kSlice)), dim3(256), lds, s, ptsA, ptsB, nA, N, pw, OUT, 0, f, sv, mv);
+    if (int rc = ensure_dyn_lds(opt_in, (const void*)pose_point_kernel<TRAIN, AVG>, lds)) return rc;
+    DPD_LAUNCH((pose_point_kernel<TRAIN, AVG>), dim3((unsigned)clouds, (unsigned)(OUT / kSlice)), dim3(256), lds, s, ptsA, ptsB, nA, N, pw, OUT, 0, f, sv, mv);
     DPD_CHECK_LAUNCH();
     return 0;
 }
+}  // namespace dpd
+
+template <bool TRAIN>
+int dpd::launch_pose_point(const float* ptsA, const float* ptsB, int nA, int clouds, int N, const PointNetW& pw, int OUT, float* f, const PointSave& sv,
+                           const PoseMove& mv, bool avg, hipStream_t s) {
+    return avg ? launch_pose_point_form<TRAIN, true>(ptsA, ptsB, nA, clouds, N, pw, OUT, f, sv, mv, s)
+               : launch_pose_point_form<TRAIN, false>(ptsA, ptsB, nA, clouds, N, pw, OUT, f, sv, mv, s);
+}
 template int dpd::launch_pose_point<false>(const float*, const float*, int, int, int, const PointNetW&, int, float*, const PointSave&, const PoseMove&,
-                                           hipStream_t);
+                                           bool, hipStream_t);
 template int dpd::launch_pose_point<true>(const float*, const float*, int, int, int, const PointNetW&, int, float*, const PointSave&, const PoseMove&,
-                                          hipStream_t);
+                                          bool, hipStream_t);
 
 extern "C" int dpd_pose_point_tie_words(int N) { return N > 0 ? (N + dpd::kPP - 1) / dpd::kPP : 0; }
 
-extern "C" int dpd_pose_point_fwd_train(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, float* f,
-                                        float* h1, float* h2, float* h3, float* h4, unsigned long long* ties, void* stream) {
+extern "C" int dpd_pose_point_fwd_train_pool(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, int pool, float* f,
+                                             float* h1, float* h2, float* h3, float* h4, unsigned long long* words, void* stream) {
     using namespace dpd;
     if (int rc = check_point_layers(net)) return rc;
     if (net->out_features != 1024) return DPD_E_UNSUPPORTED;
-    if (!ptsA || (nB > 0 && !ptsB) || !f || !h1 || !h2 || !h3 || !h4 || !ties) return DPD_E_NULL;
+    if (!ptsA || (nB > 0 && !ptsB) || !f || !h1 || !h2 || !h3 || !h4 || !words) return DPD_E_NULL;
     if (nA <= 0 || nB < 0 || N <= 0) return DPD_E_DIM;
+    if (!pool_known(pool)) return DPD_E_UNSUPPORTED;
     if (N > kTrainMaxN) return DPD_E_UNSUPPORTED;          // the kernel keeps its pass sets in 32-bit words
     if ((((uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)h3 | (uintptr_t)h4) & 15) != 0) return DPD_E_UNSUPPORTED;
-    return launch_pose_point<true>(ptsA, ptsB, nA, nA + nB, N, point_net_of(net), net->out_features, f, PointSave{{h1, h2, h3, h4}, ties}, PoseMove{},
-                                   (hipStream_t)stream);
+    return launch_pose_point<true>(ptsA, ptsB, nA, nA + nB, N, point_net_of(net), net->out_features, f, PointSave{{h1, h2, h3, h4}, words}, PoseMove{},
+                                   pool == DPD_POOL_AVG, (hipStream_t)stream);
+}
+
+extern "C" int dpd_pose_point_fwd_train(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, float* f,
+                                        float* h1, float* h2, float* h3, float* h4, unsigned long long* ties, void* stream) {
+    return dpd_pose_point_fwd_train_pool(net, ptsA, ptsB, nA, nB, N, DPD_POOL_MAX, f, h1, h2, h3, h4, ties, stream);
 }

@@ -13,6 +13,9 @@
 //                           gradients per chunk
 //   pose_bwd_reduce_kernel  sums the clouds x chunks partials in (cloud, chunk) order
 // fp32 throughout (MFMA fp32 = an fmaf chain per element); every sum has a fixed order (bitwise reproducible).
+// The average pool (dpd_pose_point_bwd_pool with DPD_POOL_AVG) makes that gradient DENSE -- every point with an open ReLU gate carries df / N:
+// dW5 is then a real product (pose_avg_dw5_kernel, further down, with its coefficient and reduce kernels); the g4 role, the per-cloud kernel and
+// the reduce kernel above serve both pools.
 #include "pose_int.h"
 
 namespace dpd {
@@ -364,6 +367,118 @@ __global__ __launch_bounds__(256) void pose_bwd_reduce_kernel(const float* __res
     db1[k] = s;
 }
 
+// ---- the average pool (models/ipcr_model.py:236-271): f = sum over the points of relu(layer 5) / N, so EVERY point whose ReLU gate is open
+// carries the gradient coef[c, col] = df[c, col] / (float)N -- about half of all (point, column) entries, and dW5 is a real
+// [1024, C N] x [C N, 128] product:  g5[c, p, col] = gate ? coef[c, col] : 0,  dW5[col, :] = sum over (cloud, point) of g5 h4[point, :].
+//   pose_avg_coef_kernel    coef [C, OUT] (one IEEE division per entry) and bterm [C, OUT] = coef * popcount(the (cloud, column)'s gate words)
+//   pose_bwd_w5_dh4_kernel  its g4 role only, with coefg = coef (also at NW == 1): g4 = S W5 costs the same whatever S holds
+//   pose_avg_dw5_kernel     the product on v_mfma_f32_32x32x2_f32, partials per split of the (cloud, chunk) range
+//   pose_avg_reduce_kernel  dW5 = the partials added in ascending split order; db5[col] = bterm[:, col] added clouds ascending
+// Every sum has one order (below): bitwise reproducible, no atomics.
+constexpr int kAvgCols = 128;          // columns of dW5 per workgroup: four waves x 32
+constexpr int kAvgMaxSplit = 32;       // (OUT / kAvgCols = 8 column blocks) x 32 splits = 256 workgroups, one per CU
+
+inline int avg_splits(int chunks) { return chunks < kAvgMaxSplit ? chunks : kAvgMaxSplit; }      // every split owns at least one chunk
+
+__global__ __launch_bounds__(256) void pose_avg_coef_kernel(const float* __restrict__ df, const unsigned long long* __restrict__ gates, int C, int NW,
+                                                             int N, int OUT, float* __restrict__ coef, float* __restrict__ bterm) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= C * OUT) return;
+    const int c = i / OUT, col = i % OUT;
+    int cnt = 0;
+    for (int w = 0; w < NW; ++w) cnt += __popcll(gates[((size_t)c * NW + w) * OUT + col]);
+    const float cf = df[i] / (float)N;
+    coef[i] = cf;
+    bterm[i] = cf * (float)cnt;
+}
+
+// One 64-point chunk of h4 in flight: thread t holds float4 q of rows (t >> 5) + 8 q, columns 4 (t & 31) .. + 3, and its column's gate word and
+// coefficient.  Rows at or beyond the cloud's last point are ZERO (their gate bits are 0, but 0 x the next cloud's value must stay 0 and the
+// last cloud's chunk ends where h4 ends).
+struct AvgChunk {
+    float4 v[8];
+    unsigned long long gate;
+    float coef;
+};
+__device__ __forceinline__ void avg_chunk_load(AvgChunk& x, const float* __restrict__ h4, const unsigned long long* __restrict__ gates,
+                                               const float* __restrict__ coef, int ch, int NW, int N, int OUT, int col, int t) {
+    const int c = ch / NW, w = ch % NW, np = min(64, N - 64 * w);
+    const float* src = h4 + ((size_t)c * N + 64 * w) * 128;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int r = (t >> 5) + 8 * q;
+        x.v[q] = r < np ? *reinterpret_cast<const float4*>(src + (size_t)r * 128 + 4 * (t & 31)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    x.gate = gates[((size_t)c * NW + w) * OUT + col];
+    x.coef = coef[(size_t)c * OUT + col];
+}
+
+// Workgroup = (column block cb of 128 columns, split sp of the C NW (cloud, chunk)s: chunks [sp CH / S, (sp + 1) CH / S), ascending); wave = 32
+// columns x all 128 inputs = four 32x32 accumulators.  Per chunk the h4 rows [64, 128] are staged in LDS ONCE (float4 writes, 32 KiB) and shared
+// by the four waves; the A operand is not a matrix in memory: lane (i = l & 31, half = l >> 5) builds A[column i][k = half] of step j -- point
+// 2 j + half of the chunk -- from its column's gate word and coefficient (bit ? coef : 0), and reads B[k][input] = h4[point][32 n + i] as one
+// ds_read_b32 per product (the two lane halves read two rows: no bank conflict; 256 B of LDS per 64-cycle MFMA).  The next chunk's rows, gate
+// word and coefficient are requested before the 128 products of the current one and written to LDS after them.
+// Order of every dW5 element's sum: an fp32 fmaf chain over the points of a chunk ascending, chunks ascending inside the split (cloud-major),
+// then the splits ascending in pose_avg_reduce_kernel.
+__global__ __launch_bounds__(256) void pose_avg_dw5_kernel(const float* __restrict__ coef, const unsigned long long* __restrict__ gates,
+                                                            const float* __restrict__ h4, int C, int N, int OUT, int S, float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float sH[64 * 128];
+    const int ncb = OUT / kAvgCols;
+    const int cb = (int)blockIdx.x % ncb, sp = (int)blockIdx.x / ncb;
+    const int NW = (N + 63) / 64, CH = C * NW;
+    const int ch0 = (int)((long long)sp * CH / S), ch1 = (int)((long long)(sp + 1) * CH / S);
+    const int t = threadIdx.x, wv = t >> 6, l = t & 63, i = l & 31, h = l >> 5;
+    const int col = cb * kAvgCols + wv * 32 + i;
+    f32x16 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+    AvgChunk nx;
+    avg_chunk_load(nx, h4, gates, coef, ch0, NW, N, OUT, col, t);
+    for (int ch = ch0; ch < ch1; ++ch) {
+        __syncthreads();                                   // the previous chunk's products are done with sH
+#pragma unroll
+        for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(sH + ((t >> 5) + 8 * q) * 128 + 4 * (t & 31)) = nx.v[q];
+        const unsigned long long g = nx.gate >> h;         // bit 2 j: point 2 j + half
+        const unsigned glo = (unsigned)g, ghi = (unsigned)(g >> 32);
+        const float cf = nx.coef;
+        __syncthreads();
+        if (ch + 1 < ch1) avg_chunk_load(nx, h4, gates, coef, ch + 1, NW, N, OUT, col, t);
+        const float* bp = sH + h * 128 + i;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const unsigned bit = j < 16 ? (glo >> (2 * j)) & 1u : (ghi >> (2 * j - 32)) & 1u;
+            const float a = bit ? cf : 0.f;
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bp[j * 256 + 32 * n], acc[n], 0, 0, 0);
+        }
+    }
+    float* out = part + ((size_t)sp * OUT + cb * kAvgCols + wv * 32) * 128;
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[(size_t)mfma_row(r, l) * 128 + 32 * n + i] = acc[n][r];
+}
+
+// threads [0, OUT * 128): dW5 element = partials of the S splits, ascending; threads [OUT * 128, OUT * 128 + OUT): db5 = bterm over the clouds, ascending
+__global__ __launch_bounds__(256) void pose_avg_reduce_kernel(const float* __restrict__ part, int S, const float* __restrict__ bterm, int C, int OUT,
+                                                               float* __restrict__ dW5, float* __restrict__ db5) {
+    const int i = blockIdx.x * 256 + threadIdx.x, n = OUT * 128;
+    if (i < n) {
+        float s = part[i];
+        for (int sp = 1; sp < S; ++sp) s += part[(size_t)sp * n + i];
+        dW5[i] = s;
+        return;
+    }
+    const int col = i - n;
+    if (col >= OUT) return;
+    float s = bterm[col];
+    for (int c = 1; c < C; ++c) s += bterm[(size_t)c * OUT + col];
+    db5[col] = s;
+}
+
 }  // namespace dpd
 
 // partial weight gradients per (cloud, 64-point chunk) + g4 [clouds * chunks * 64, 128] (+ coef [clouds, OUT] when a cloud has several chunks)
@@ -375,36 +490,70 @@ extern "C" size_t dpd_pose_point_bwd_workspace_bytes_n(int clouds, int N) {
 
 extern "C" size_t dpd_pose_point_bwd_workspace_bytes(int clouds) { return dpd_pose_point_bwd_workspace_bytes_n(clouds, dpd::kPP); }      // N <= 64
 
+// average pool: the records and g4 as above, then coef [clouds, OUT], bterm [clouds, OUT] and the dW5 partials [splits, OUT, 128]
+extern "C" size_t dpd_pose_point_bwd_workspace_bytes_pool(int clouds, int N, int pool) {
+    if (pool == DPD_POOL_MAX) return dpd_pose_point_bwd_workspace_bytes_n(clouds, N);
+    if (pool != DPD_POOL_AVG || clouds <= 0 || N <= 0 || N > dpd::kTrainMaxN) return 0;
+    const size_t W = (size_t)dpd_pose_point_tie_words(N);
+    return ((size_t)clouds * W * (dpd::kPart + 64 * 128) + (size_t)clouds * 1024 * 2 + (size_t)dpd::avg_splits((int)(clouds * W)) * 1024 * 128) * sizeof(float);
+}
+
 extern "C" int dpd_pose_point_bwd(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, const float* df,
                                   const float* h1, const float* h2, const float* h3, const float* h4, const unsigned long long* ties,
                                   float* const* dW, float* const* db, void* ws, size_t ws_bytes, void* stream) {
+    return dpd_pose_point_bwd_pool(net, ptsA, ptsB, nA, nB, N, DPD_POOL_MAX, df, h1, h2, h3, h4, ties, dW, db, ws, ws_bytes, stream);
+}
+
+extern "C" int dpd_pose_point_bwd_pool(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, int pool, const float* df,
+                                       const float* h1, const float* h2, const float* h3, const float* h4, const unsigned long long* words,
+                                       float* const* dW, float* const* db, void* ws, size_t ws_bytes, void* stream) {
     using namespace dpd;
     if (int rc = check_point_layers(net)) return rc;
     if (net->out_features != 1024) return DPD_E_UNSUPPORTED;
-    if (!ptsA || (nB > 0 && !ptsB) || !df || !h1 || !h2 || !h3 || !h4 || !ties || !dW || !db || !ws) return DPD_E_NULL;
+    if (!ptsA || (nB > 0 && !ptsB) || !df || !h1 || !h2 || !h3 || !h4 || !words || !dW || !db || !ws) return DPD_E_NULL;
     for (int i = 0; i < 5; ++i)
         if (!dW[i] || !db[i]) return DPD_E_NULL;
     if (nA <= 0 || nB < 0 || N <= 0) return DPD_E_DIM;
+    if (!pool_known(pool)) return DPD_E_UNSUPPORTED;
     if (N > kTrainMaxN) return DPD_E_UNSUPPORTED;
+    const bool avg = pool == DPD_POOL_AVG;
+    if (avg && ((uintptr_t)h4 & 15) != 0) return DPD_E_UNSUPPORTED;      // pose_avg_dw5_kernel reads h4 in 16-byte pieces
     const int C = nA + nB, OUT = net->out_features, NW = dpd_pose_point_tie_words(N);
-    if (ws_bytes < dpd_pose_point_bwd_workspace_bytes_n(C, N)) return DPD_E_WORKSPACE;
+    if (ws_bytes < dpd_pose_point_bwd_workspace_bytes_pool(C, N, pool)) return DPD_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const PointNetW pw = point_net_of(net);
     PointSave sv{{const_cast<float*>(h1), const_cast<float*>(h2), const_cast<float*>(h3), const_cast<float*>(h4)},
-                 const_cast<unsigned long long*>(ties)};
+                 const_cast<unsigned long long*>(words)};
     const size_t lds = (size_t)kBwdLds * sizeof(float);
     static LdsOptIn cloud_opt_in;                          // of pose_bwd_cloud_kernel, launched here only
     if (int rc = ensure_dyn_lds(cloud_opt_in, (const void*)pose_bwd_cloud_kernel, lds)) return rc;
     float* g4g = (float*)ws + (size_t)C * NW * kPart;              // [C * N, 128]
-    float* coef = NW > 1 ? g4g + (size_t)C * NW * 64 * 128 : nullptr;      // [C, OUT]
+    float* coef = (NW > 1 || avg) ? g4g + (size_t)C * NW * 64 * 128 : nullptr;      // [C, OUT]
     const int tiles = NW > 1 ? 4 * ((N + 31) / 32) : 8;            // 32 points x 32 inputs each
-    if (coef) {
-        DPD_LAUNCH(pose_tie_coef_kernel, dim3((unsigned)((C * OUT + 255) / 256)), dim3(256), 0, s, df, ties, C, NW, OUT, coef);
+    if (avg) {
+        float* bterm = coef + (size_t)C * OUT;                     // [C, OUT]
+        float* part = bterm + (size_t)C * OUT;                     // [S, OUT, 128]
+        const int S = avg_splits(C * NW);
+        DPD_LAUNCH(pose_avg_coef_kernel, dim3((unsigned)((C * OUT + 255) / 256)), dim3(256), 0, s, df, words, C, NW, N, OUT, coef, bterm);
+        DPD_CHECK_LAUNCH();
+        // the g4 role alone (no dW5 / db5 blocks): S = the gate bits, coefg = coef also where a cloud has one chunk
+        DPD_LAUNCH(pose_bwd_w5_dh4_kernel, dim3((unsigned)(C * tiles)), dim3(512), 0, s, df, words, net->Wp[4], h4, C, N, OUT, g4g, dW[4], db[4], tiles,
+                   (const float*)coef);
+        DPD_CHECK_LAUNCH();
+        DPD_LAUNCH(pose_avg_dw5_kernel, dim3((unsigned)(OUT / kAvgCols * S)), dim3(256), 0, s, (const float*)coef, words, h4, C, N, OUT, S, part);
+        DPD_CHECK_LAUNCH();
+        DPD_LAUNCH(pose_avg_reduce_kernel, dim3((unsigned)((OUT * 128 + OUT + 255) / 256)), dim3(256), 0, s, (const float*)part, S, (const float*)bterm, C, OUT,
+                   dW[4], db[4]);
+        DPD_CHECK_LAUNCH();
+    } else {
+        if (coef) {
+            DPD_LAUNCH(pose_tie_coef_kernel, dim3((unsigned)((C * OUT + 255) / 256)), dim3(256), 0, s, df, words, C, NW, OUT, coef);
+            DPD_CHECK_LAUNCH();
+        }
+        DPD_LAUNCH(pose_bwd_w5_dh4_kernel, dim3((unsigned)(C * tiles + (OUT + 7) / 8)), dim3(512), 0, s, df, words, net->Wp[4], h4, C, N, OUT, g4g, dW[4],
+                   db[4], tiles, (const float*)coef);
         DPD_CHECK_LAUNCH();
     }
-    DPD_LAUNCH(pose_bwd_w5_dh4_kernel, dim3((unsigned)(C * tiles + (OUT + 7) / 8)), dim3(512), 0, s, df, ties, net->Wp[4], h4, C, N, OUT, g4g, dW[4], db[4],
-               tiles, (const float*)coef);
-    DPD_CHECK_LAUNCH();
     DPD_LAUNCH(pose_bwd_cloud_kernel, dim3((unsigned)(C * NW)), dim3(kBT), lds, s, ptsA, ptsB, nA, N, pw, (const float*)g4g, sv, (float*)ws);
     DPD_CHECK_LAUNCH();
     DPD_LAUNCH(pose_bwd_reduce_kernel, dim3((unsigned)((kPart + 255) / 256)), dim3(256), 0, s, (const float*)ws, C * NW, dW[3], db[3], dW[2], db[2], dW[1],

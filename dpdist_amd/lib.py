@@ -181,6 +181,8 @@ SIGNATURES = {
     "dpd_pose_refine_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dpd_pose_refine": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "dpd_pose_refine_pool": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
     "dpd_occlude": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dpd_pose_trace": (c_int, [c_void_p, c_int, c_int, c_float] + [c_void_p] * 7),
     "dpd_chamfer_sqrt_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6),
@@ -191,6 +193,10 @@ SIGNATURES = {
     "dpd_pose_point_fwd_train": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 7),
     "dpd_pose_point_bwd": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 +
                            [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
+    "dpd_pose_point_bwd_workspace_bytes_pool": (c_size_t, [c_int, c_int, c_int]),
+    "dpd_pose_point_fwd_train_pool": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 7),
+    "dpd_pose_point_bwd_pool": (c_int, [POINTER(PoseNetW), c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6 +
+                                [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "dpd_pose_head_bwd_workspace_bytes": (c_size_t, [c_int]),
     "dpd_pose_head_fwd_train": (c_int, [POINTER(PoseNetW), c_void_p, c_int] + [c_void_p] * 6),
     "dpd_pose_head_bwd": (c_int, [POINTER(PoseNetW), c_void_p, c_int] + [c_void_p] * 5 + [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p,
@@ -251,6 +257,7 @@ def load():
 
 
 DTYPES = {"f32": 0, "f32x3": 1, "bf16": 2, 0: 0, 1: 1, 2: 2}   # include/dpdist_capi.h: enum dpd_dtype
+POOLS = {"max": 0, "avg": 1}                                   # include/dpdist_capi.h: enum dpd_pool
 
 
 def check(rc, what):

@@ -67,8 +67,9 @@ def _has_widths(seq, widths):
 
 
 def native_point_supported(net):
-    """Whether `net`'s shared MLP is the one csrc/pose_point.hip implements (3-64-64-64-128-1024, with biases): all `PoseNet._pooled` needs."""
-    return isinstance(net, PoseNet) and _has_widths(net.point, POINT_WIDTHS)
+    """Whether `net`'s shared MLP is the one csrc/pose_point.hip implements (3-64-64-64-128-1024, with biases; max or average pool): all
+    `PoseNet._pooled` needs."""
+    return isinstance(net, PoseNet) and _has_widths(net.point, POINT_WIDTHS) and getattr(net, "pool", "max") in L.POOLS
 
 
 def native_refine_supported(net):
@@ -93,25 +94,33 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def _point_forward(w, ptsA, ptsB, nA, nB, N):
-    """dpd_pose_point_fwd_train on the nA clouds of ptsA, then the nB of ptsB (None, 0: one array): (pooled features, hidden activations, tie masks)."""
+def _split_pool(wb):
+    """The autograd nodes below take the weight tensors as their trailing arguments, optionally followed by the pool id (lib.POOLS; absent:
+    the max pool, so that the nodes are called as before the average pool existed): (weights, pool id, whether it was given)."""
+    given = len(wb) > 0 and isinstance(wb[-1], int)
+    return (wb[:-1], wb[-1], True) if given else (wb, L.POOLS["max"], False)
+
+
+def _point_forward(w, ptsA, ptsB, nA, nB, N, pool=0):
+    """dpd_pose_point_fwd_train_pool on the nA clouds of ptsA, then the nB of ptsB (None, 0: one array): (pooled features, hidden activations,
+    the max pool's tie words or the average pool's gate words)."""
     C, dev, lib = nA + nB, ptsA.device, L.load()
     f = torch.empty(C, w.out_features, device=dev, dtype=torch.float32)
     h = [torch.empty(C * N, k, device=dev, dtype=torch.float32) for _, k in POINT_WIDTHS[:4]]
     ties = torch.empty(C, lib.dpd_pose_point_tie_words(N), w.out_features, device=dev, dtype=torch.int64)
-    L.check(lib.dpd_pose_point_fwd_train(byref(w), L.ptr(ptsA), L.ptr(ptsB), nA, nB, N, L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
-                                         ties.data_ptr(), L.cur_stream()), "dpd_pose_point_fwd_train")
+    L.check(lib.dpd_pose_point_fwd_train_pool(byref(w), L.ptr(ptsA), L.ptr(ptsB), nA, nB, N, int(pool), L.ptr(f), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]),
+                                              L.ptr(h[3]), ties.data_ptr(), L.cur_stream()), "dpd_pose_point_fwd_train_pool")
     return f, h, ties
 
 
-def _point_backward(w, ptsA, ptsB, nA, nB, N, df, h, ties, grads):
-    """dpd_pose_point_bwd: from `df` = d loss / d pooled features, the shared MLP's ten weight gradients WRITTEN into `grads` (dW1, db1, .. dW5, db5)."""
+def _point_backward(w, ptsA, ptsB, nA, nB, N, df, h, ties, grads, pool=0):
+    """dpd_pose_point_bwd_pool: from `df` = d loss / d pooled features, the shared MLP's ten weight gradients WRITTEN into `grads` (dW1, db1, .. dW5, db5)."""
     lib = L.load()
-    nbytes = lib.dpd_pose_point_bwd_workspace_bytes_n(nA + nB, N)
+    nbytes = lib.dpd_pose_point_bwd_workspace_bytes_pool(nA + nB, N, int(pool))
     ws = torch.empty(nbytes // 4, device=ptsA.device, dtype=torch.float32)
-    L.check(lib.dpd_pose_point_bwd(byref(w), L.ptr(ptsA), L.ptr(ptsB), nA, nB, N, L.ptr(df), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]), L.ptr(h[3]),
-                                   ties.data_ptr(), _ptr_array(grads[0::2]), _ptr_array(grads[1::2]), L.ptr(ws), nbytes, L.cur_stream()),
-            "dpd_pose_point_bwd")
+    L.check(lib.dpd_pose_point_bwd_pool(byref(w), L.ptr(ptsA), L.ptr(ptsB), nA, nB, N, int(pool), L.ptr(df), L.ptr(h[0]), L.ptr(h[1]), L.ptr(h[2]),
+                                        L.ptr(h[3]), ties.data_ptr(), _ptr_array(grads[0::2]), _ptr_array(grads[1::2]), L.ptr(ws), nbytes,
+                                        L.cur_stream()), "dpd_pose_point_bwd_pool")
 
 
 class _PointFeaturesFn(torch.autograd.Function):
@@ -119,13 +128,15 @@ class _PointFeaturesFn(torch.autograd.Function):
     (include/dpdist_capi.h: dpd_pose_point_fwd_train / dpd_pose_point_bwd; csrc/pose_point.hip, pose_point_bwd.hip): one launch forward, three backward (four above
     64 points), instead of ~16 forward and ~45 backward launches of torch / hipBLASLt kernels at batch 16.  The clouds carry no gradient (the
     refined source of a registration step is a constant of the step, iterative_PCRNet_ours.py:442-470).  Same mathematics as `point(...).amax(1)` -- gradient of
-    the max pool shared evenly among ties like tf.reduce_max -- in another fp32 summation order."""
+    the max pool shared evenly among ties like tf.reduce_max -- in another fp32 summation order.  `wb`: the ten weight tensors, optionally followed
+    by the pool id (lib.POOLS["avg"]: `point(...).mean(1)`, models/ipcr_model.py:236-271; four launches more backward: the dense dW5 product)."""
 
     @staticmethod
     def forward(ctx, clouds, *wb):
+        wb, ctx.pool, ctx.pool_given = _split_pool(wb)
         C, N, _ = clouds.shape
         L.req(clouds, name="clouds", shape=(C, N, 3))
-        f, h, ties = _point_forward(_pose_net_struct(wb), clouds, None, C, 0, N)
+        f, h, ties = _point_forward(_pose_net_struct(wb), clouds, None, C, 0, N, ctx.pool)
         ctx.save_for_backward(clouds, ties, *h, *wb)
         return f
 
@@ -135,8 +146,8 @@ class _PointFeaturesFn(torch.autograd.Function):
         clouds, ties, h, wb = sv[0], sv[1], sv[2:6], sv[6:]
         C, N, _ = clouds.shape
         grads = [torch.empty_like(t) for t in wb]
-        _point_backward(_pose_net_struct(wb), clouds, None, C, 0, N, df.contiguous(), h, ties, grads)
-        return (None,) + tuple(grads)
+        _point_backward(_pose_net_struct(wb), clouds, None, C, 0, N, df.contiguous(), h, ties, grads, ctx.pool)
+        return (None,) + tuple(grads) + ((None,) if ctx.pool_given else ())
 
 
 class _PoseNetRawFn(torch.autograd.Function):
@@ -144,16 +155,18 @@ class _PoseNetRawFn(torch.autograd.Function):
     273-284) -- as ONE autograd node on the library: five launches forward (dpd_pose_point_fwd_train, dpd_pose_head_fwd_train), eight backward
     (dpd_pose_head_bwd, dpd_pose_point_bwd; nine above 64 points), gradients w.r.t. the 18 weight tensors only.  `mask` [B,256]: the dropout mask
     (0 or 1 / keep) drawn by the caller, or None (evaluation mode).  `sink`: None, or {id(parameter): tensor of its shape} -- the backward then WRITES the
-    gradient of that parameter there (views of the optimizer's flat gradient buffer: no gather copy afterwards) and returns it."""
+    gradient of that parameter there (views of the optimizer's flat gradient buffer: no gather copy afterwards) and returns it.  `wb`: the 18 weight
+    tensors, optionally followed by the pool id (lib.POOLS; absent: the max pool)."""
 
     @staticmethod
     def forward(ctx, source, template, mask, sink, *wb):
+        wb, ctx.pool, ctx.pool_given = _split_pool(wb)
         B, N, _ = source.shape
         L.req(source, name="source", shape=(B, N, 3)), L.req(template, name="template", shape=(B, N, 3))
         if mask is not None:
             L.req(mask, name="mask", shape=(B, 256))
         w = _pose_net_struct(wb)
-        f, h, ties = _point_forward(w, source, template, B, B, N)
+        f, h, ties = _point_forward(w, source, template, B, B, N, ctx.pool)
         a1, a2, a3, pred = [torch.empty(B, k, device=source.device, dtype=torch.float32) for k in (1024, 512, 256, 7)]
         L.check(L.load().dpd_pose_head_fwd_train(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(pred), L.cur_stream()),
                 "dpd_pose_head_fwd_train")
@@ -181,8 +194,8 @@ class _PoseNetRawFn(torch.autograd.Function):
         ws = torch.empty(nb // 4, device=source.device, dtype=torch.float32)
         L.check(lib.dpd_pose_head_bwd(byref(w), L.ptr(f), B, L.ptr(mask), L.ptr(a1), L.ptr(a2), L.ptr(a3), L.ptr(dpred), _ptr_array(grads[10::2]),
                                       _ptr_array(grads[11::2]), L.ptr(df), L.ptr(ws), nb, L.cur_stream()), "dpd_pose_head_bwd")
-        _point_backward(w, source, template, B, B, N, df, h, ties, grads[:10])
-        return (None, None, None, None) + tuple(grads)
+        _point_backward(w, source, template, B, B, N, df, h, ties, grads[:10], ctx.pool)
+        return (None, None, None, None) + tuple(grads) + ((None,) if ctx.pool_given else ())
 
 
 def _dropout_masks(net, count, B, device):
@@ -201,8 +214,13 @@ class PoseNet(nn.Module):
     grad_sink = None         # {id(parameter): where _PoseNetRawFn's backward writes that gradient}, for the span of one `_evaluate_grad`
     native_train = True      # the training evaluation on the library (_PoseNetRawFn / _PointFeaturesFn) when the network and the inputs allow it
 
-    def __init__(self, out_features=1024, lim_rot=45.0, keep_prob=0.7):
+    def __init__(self, out_features=1024, lim_rot=45.0, keep_prob=0.7, pool="max"):
+        """pool: the reference's --pn_pool: "max" (ipcr_model.pointnet, :198-233) or "avg" (pointnet_avg, :236-271: the mean of the last shared
+        layer's ReLU outputs over the points; the same variables, so `load_tf_state_dict` serves both)."""
         super().__init__()
+        if pool not in L.POOLS:
+            raise ValueError("pool must be 'max' or 'avg', got %r" % (pool,))
+        self.pool = pool
         dims = [3, 64, 64, 64, 128, out_features]
         self.point = nn.Sequential(*[m for i in range(5) for m in (nn.Linear(dims[i], dims[i + 1]), nn.ReLU())])
         self.head = nn.Sequential(nn.Linear(2 * out_features, 1024), nn.ReLU(), nn.Linear(1024, 512), nn.ReLU(),
@@ -241,11 +259,15 @@ class PoseNet(nn.Module):
         return wb if any(t.requires_grad for t in wb) else None
 
     def _pooled(self, clouds):
-        """shared MLP + max pool over the points of every cloud: [C, N, 3] -> [C, out_features]"""
+        """shared MLP + max (or average) pool over the points of every cloud: [C, N, 3] -> [C, out_features]"""
         wb = self._library_weights(clouds, head=False)
         if wb is not None:
-            return _PointFeaturesFn.apply(clouds.contiguous(), *wb)
-        return self.point(clouds).amax(1)
+            return _PointFeaturesFn.apply(clouds.contiguous(), *wb, *self._pool_arg())
+        return self.point(clouds).mean(1) if self.pool == "avg" else self.point(clouds).amax(1)
+
+    def _pool_arg(self):
+        """the trailing pool argument of the library's nodes: none for the max pool (the nodes' call of before), the id for the average pool"""
+        return () if self.pool == "max" else (L.POOLS[self.pool],)
 
     def features(self, source, template):
         """ipcr_model.pointnet (:198-233): (source_global_feature, template_global_feature), each [B, out_features]."""
@@ -264,7 +286,7 @@ class PoseNet(nn.Module):
             if mask is None or not self.training or mask.shape != (B, 256) or mask.device != source.device:
                 mask = _dropout_masks(self, 1, B, source.device)
                 mask = None if mask is None else mask[0]
-            return _PoseNetRawFn.apply(source.contiguous(), template.contiguous(), mask, self.grad_sink, *wb)
+            return _PoseNetRawFn.apply(source.contiguous(), template.contiguous(), mask, self.grad_sink, *wb, *self._pool_arg())
         return self.head(torch.cat(self.features(source, template), 1))
 
     def forward(self, source, template):
@@ -434,7 +456,7 @@ def pose_apply(pred, source, T=None, lim_rot=45.0, mode=0):
 
 def pose_refine_native(net, source, template, loops, drop_mask=None, want_pred=False):
     """`loops` forward-only refinements (iterative_PCRNet_ours.py:414-441) with the pose network, quat_normalize, the cloud move and the T
-    composition all on the library (include/dpdist_capi.h: dpd_pose_refine, four launches per loop + one per call): (moved source, T[, raw outputs
+    composition all on the library (include/dpdist_capi.h: dpd_pose_refine_pool with the network's pool, four launches per loop + one per call): (moved source, T[, raw outputs
     [loops,B,7]]).  drop_mask [loops,B,256] (0 or 1/keep) or None; the caller draws it (IterativeRegistration.refine does, in train mode)."""
     B, N, _ = source.shape
     L.req(source, name="source", shape=(B, N, 3)), L.req(template, name="template", shape=(B, N, 3))
@@ -446,8 +468,9 @@ def pose_refine_native(net, source, template, loops, drop_mask=None, want_pred=F
         L.req(drop_mask, name="drop_mask", shape=(loops, B, 256))
     moved, T = torch.empty_like(source), torch.empty(B, 4, 4, device=source.device, dtype=torch.float32)
     pred = torch.empty(loops, B, 7, device=source.device, dtype=torch.float32) if want_pred else None
-    L.check(lib.dpd_pose_refine(byref(w), L.ptr(source), L.ptr(template), B, N, int(loops), float(net.lim_rot or 0.0), L.ptr(drop_mask),
-                                L.ptr(ws), nbytes, L.ptr(moved), L.ptr(T), L.ptr(pred), L.cur_stream()), "dpd_pose_refine")
+    L.check(lib.dpd_pose_refine_pool(byref(w), L.ptr(source), L.ptr(template), B, N, int(loops), float(net.lim_rot or 0.0),
+                                     L.POOLS[getattr(net, "pool", "max")], L.ptr(drop_mask), L.ptr(ws), nbytes, L.ptr(moved), L.ptr(T), L.ptr(pred),
+                                     L.cur_stream()), "dpd_pose_refine_pool")
     return (moved, T, pred) if want_pred else (moved, T)
 
 

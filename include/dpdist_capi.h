@@ -957,6 +957,18 @@ size_t dpd_pose_refine_workspace_bytes(int B, int N, int out_features);
 int dpd_pose_refine(const dpd_pose_net* net, const float* src, const float* tmpl, int B, int N, int loops, float lim_rot_deg,
                     const float* drop_mask, void* ws, size_t ws_bytes, float* moved, float* T_out, float* pred_out, void* stream);
 
+/* The pool of the pose network's shared MLP (the reference's --pn_pool max|avg).  DPD_POOL_AVG is models/ipcr_model.py:236-271 (pointnet_avg):
+ * the same five layers and head, tf_util.avg_pool2d over the points in place of the max pool -- per (cloud, column) the feature is
+ *   f = (sum over the cloud's N points of relu(layer 5)) / (float)N,
+ * the sum taken in one fixed order (per 64-point pass: each lane adds the rows the 32x32 MFMA gave it, ascending; the lower lane half's sum
+ * + the upper one's; then the passes ascending; the origin rows that pad a partial pass are left out) and the quotient as ONE IEEE fp32
+ * division (not a product with a reciprocal).  Any other `pool` value: DPD_E_UNSUPPORTED, before any launch.
+ * dpd_pose_refine_pool is dpd_pose_refine with that pool (workspace: dpd_pose_refine_workspace_bytes; the same checks); with DPD_POOL_MAX it
+ * IS dpd_pose_refine -- the same launches, the same bits.  Its features have the bits of dpd_pose_point_fwd_train_pool's. */
+enum dpd_pool { DPD_POOL_MAX = 0, DPD_POOL_AVG = 1 };
+int dpd_pose_refine_pool(const dpd_pose_net* net, const float* src, const float* tmpl, int B, int N, int loops, float lim_rot_deg, int pool,
+                         const float* drop_mask, void* ws, size_t ws_bytes, float* moved, float* T_out, float* pred_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The registration experiment's test protocol (pcrnet-registration/results_itrPCRNet_no_stop.py; csrc/regtest.hip): the occlusion of
  * the source clouds, the per-iteration error tables of the no-stop loop and the square-rooted Chamfer baseline.  None of the four
@@ -1024,6 +1036,27 @@ int dpd_pose_point_fwd_train(const dpd_pose_net* net, const float* ptsA, const f
 int dpd_pose_point_bwd(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, const float* df, const float* h1,
                        const float* h2, const float* h3, const float* h4, const unsigned long long* ties, float* const* dW, float* const* db,
                        void* ws, size_t ws_bytes, void* stream);
+/* The same two entries with the pool as an argument (enum dpd_pool above); with DPD_POOL_MAX they ARE the entries above (which call them):
+ * the same launches, the same bits, and dpd_pose_point_bwd_workspace_bytes_pool(clouds, N, DPD_POOL_MAX) ==
+ * dpd_pose_point_bwd_workspace_bytes_n(clouds, N).  With DPD_POOL_AVG:
+ *   forward: f = sum / (float)N as stated at enum dpd_pool; `words` (the tie words' buffer and layout, [nA+nB, W, out_features]) receives the
+ *     GATE words: bit b of word w set <=> point 64 w + b is a real point (< N) and its layer-5 pre-activation is > 0.
+ *   backward: coef[c, col] = df[c, col] / (float)N (one IEEE division), g5[c, p, col] = gate bit ? coef[c, col] : 0;
+ *     dW5[col, :] = sum over (cloud, point) of g5 h4[point, :] on the fp32 matrix cores: an fmaf chain over the points of a 64-point chunk
+ *       ascending, the chunks of a split ascending (cloud-major), then the splits' partials ascending (the (cloud, chunk) range is cut into
+ *       min(clouds W, 32) contiguous splits);
+ *     db5[col] = sum over the clouds ascending of coef[c, col] * (float)popcount(the gate words of (c, col));
+ *     the gradient of layer 4's output and dW1..dW4, db1..db4 through the kernels of the max pool (they do not look at the pool).
+ *     ws: dpd_pose_point_bwd_workspace_bytes_pool(nA + nB, N, DPD_POOL_AVG) bytes -- the max pool's records, then coef, coef * popcount
+ *     [clouds, out_features] each and the split partials [splits, out_features, 128]; h4 16-byte aligned.
+ * Refusals before any launch: pool not in enum dpd_pool: DPD_E_UNSUPPORTED (the workspace entry returns 0); N > 2048, out_features != 1024:
+ * DPD_E_UNSUPPORTED; the NULL / dimension / workspace checks of the entries above.  Deterministic (no atomics). */
+size_t dpd_pose_point_bwd_workspace_bytes_pool(int clouds, int N, int pool);
+int dpd_pose_point_fwd_train_pool(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, int pool, float* f, float* h1,
+                                  float* h2, float* h3, float* h4, unsigned long long* words, void* stream);
+int dpd_pose_point_bwd_pool(const dpd_pose_net* net, const float* ptsA, const float* ptsB, int nA, int nB, int N, int pool, const float* df,
+                            const float* h1, const float* h2, const float* h3, const float* h4, const unsigned long long* words, float* const* dW,
+                            float* const* db, void* ws, size_t ws_bytes, void* stream);
 
 /* The head of the same training evaluation (models/ipcr_model.py:273-284: fc 2 x out_features -> 1024 -> 512 -> 256, ReLU each, dropout on the
  * last, -> 7) and its autodiff.  f [2B, out_features] = the pooled features (rows < B: first cloud set, rows >= B: second; the head reads

@@ -6,6 +6,7 @@ network with DPDist as the loss at the reference's workload (batch 16, 64 points
 
     python tools/registration_demo.py [--dp_steps 6000] [--reg_steps 6000] [--batch 16] [--loss ours|chamfer|emd|both|all] [--gpus N] [--num_point 64]
                                       [--test_iterations N] [--add_occlusions F] [--noise] [--centroid_sub] [--chamfer_form squared|sqrt] [--log_dir DIR]
+                                      [--pn_pool max|avg]
 
 The held-out pairs go through the reference's test protocol (results_itrPCRNet_no_stop.py; dpdist_amd/regtest.py): the per-iteration
 translation / rotation / convergence tables and the nested success buckets, with the source optionally occluded (--add_occlusions, the
@@ -13,6 +14,9 @@ fraction of points cut out around a random point), perturbed (--noise) or centre
 the test (default --loops, which makes the table's last row the transform `evaluate` reports).  --chamfer_form sqrt: the Chamfer leg
 trains with PCRNet's square-rooted form (utils/tf_util_loss.py:35-39) instead of the AUE task's squared one.  --log_dir: every leg's
 log_data.npz and test.txt (regtest.write_results) under DIR/<leg>.
+
+--pn_pool: the pool of the pose network's shared MLP (the reference's flag of the same name: max = ipcr_model.pointnet, avg = pointnet_avg,
+models/ipcr_model.py:236-271); both run on the library.
 
 --num_point: points per registration cloud (the reference's --num_point: 256 / 512 / 1024 / 2048, default 512, iterative_PCRNet_ours.py:40;
 this demo's default stays 64).  DPDist itself is trained on 64-point chair clouds either way.
@@ -55,6 +59,7 @@ def main():
     ap.add_argument("--noise", action="store_true", help="perturb the held-out sources (helper.add_noise)")
     ap.add_argument("--centroid_sub", action="store_true", help="centre the held-out sources before the test")
     ap.add_argument("--chamfer_form", default="squared", choices=["squared", "sqrt"], help="sqrt = PCRNet's --loss_type chamf")
+    ap.add_argument("--pn_pool", default="max", choices=["max", "avg"], help="pool of the pose network's shared MLP (the reference's flag)")
     ap.add_argument("--log_dir", default="", help="write every leg's log_data.npz and test.txt under this directory")
     a = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
@@ -98,7 +103,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     say = print if rank == 0 else (lambda *x, **k: None)
     cu = lambda x: torch.tensor(x, device=dev)   # noqa: E731
-    out = {"n_gpus": world, "workload": {"batch_per_gpu": a.batch, "global_batch": a.batch * world, "num_point": a.num_point, "loops": a.loops, "lim_rot": 45.0, "poses": "U(-45,45)^3 deg, U(-.01,.01)^3",
+    out = {"n_gpus": world, "workload": {"batch_per_gpu": a.batch, "global_batch": a.batch * world, "num_point": a.num_point, "pn_pool": a.pn_pool, "loops": a.loops, "lim_rot": 45.0, "poses": "U(-45,45)^3 deg, U(-.01,.01)^3",
                         "shapes": "synthetic box-union chairs"}}
     test_iters = a.test_iterations or a.loops
     out["test"] = {"iterations": test_iters, "add_occlusions": a.add_occlusions, "noise": a.noise, "centroid_sub": a.centroid_sub,
@@ -183,7 +188,7 @@ def main():
     baselines = {"chamfer": lambda moved, tmpl: chamfer(moved, tmpl), "emd": lambda moved, tmpl: earth_mover(moved, tmpl)}
     for name in {"both": ["ours", "chamfer"], "all": ["ours", "chamfer", "emd"]}.get(a.loss, [a.loss]):
         torch.manual_seed(0)                                  # the same pose network on every rank (replicated variables)
-        net = PoseNet().to(dev)
+        net = PoseNet(pool=a.pn_pool).to(dev)
         torch.manual_seed(1000 + rank)                       # ... but its own dropout masks
         rng = np.random.default_rng(1000 * rank)             # ... and its own pairs
         loss_fn = dp_loss if name == "ours" else baselines[name]

@@ -12,7 +12,12 @@ forward/backward + TF-form Adam, pcrnet-registration/iterative_PCRNet_ours.py:41
 Inputs are resident on the GPU before the clock starts (pair generation is the data loader's business, not this path's).  Also prints
 what one DPDist forward+backward costs on its own (the as-loss engine, same shape), i.e. the share of the step that IS the hot path.
 
-    python tools/registration_step_bench.py [--batch 16] [--steps 300] [--dtype f32|f32x3|bf16] [--loops 8] [--num_point 64]
+    python tools/registration_step_bench.py [--batch 16] [--steps 300] [--dtype f32|f32x3|bf16] [--loops 8] [--num_point 64] [--pn_pool max|avg]
+
+--pn_pool avg (the reference's flag) times the average-pool pose encoder (models/ipcr_model.py:236-271).  --torch_train keeps the training
+evaluation in torch as well (PoseNet.native_train = False): with --forms eager_fused,graph_fused that is the torch form of the whole pose
+network, the yardstick of the library's forms.  Every form also reports the pose network's training evaluation split into forward and
+backward by in-stream events (`pose_fwd_ms`, `pose_bwd_ms`) and, under the average pool, the dense dW5 kernel alone (`avg_dw5_kernel_us`).
 
 --num_point other than 64 (the reference registers at 256 .. 2048 points, default 512) adds, per form, what the pose network's training
 evaluation costs on its own (`train_eval_ms`: PoseNet.raw forward + backward, GPU time), whether it ran as the library's node, and the
@@ -37,6 +42,8 @@ def main():
     ap.add_argument("--dtype", default="f32")
     ap.add_argument("--num_point", type=int, default=64)
     ap.add_argument("--forms", default="eager_torch,eager_fused,eager_native,graph_fused,graph")
+    ap.add_argument("--pn_pool", default="max", choices=["max", "avg"], help="pool of the pose network's shared MLP (the reference's flag)")
+    ap.add_argument("--torch_train", action="store_true", help="the training evaluation in torch too (PoseNet.native_train = False)")
     ap.add_argument("--train-only", action="store_true", help="profiler runs: exactly 8 + 3 * steps training steps per form, nothing else")
     a = ap.parse_args()
     from dpdist_amd import synth
@@ -45,14 +52,16 @@ def main():
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     pool = [tuple(torch.tensor(x, device=dev) for x in synth.registration_pairs(a.batch, a.num_point, rng=rng)[:2]) for _ in range(32)]
-    out = {"workload": {"batch": a.batch, "num_point": a.num_point, "loops": a.loops, "dpdist_dtype": a.dtype}}
+    out = {"workload": {"batch": a.batch, "num_point": a.num_point, "loops": a.loops, "dpdist_dtype": a.dtype, "pn_pool": a.pn_pool,
+                        "torch_train": a.torch_train}}
 
     def harness(graph, fused, native=True):
         torch.manual_seed(0)
         model = DPDistModel(device=dev)
         model.load_tf_state_dict(synth.make_weights("wide"))
         model.params_.compute_dtype = a.dtype
-        net = PoseNet().to(dev)
+        net = PoseNet(pool=a.pn_pool).to(dev)
+        net.native_train = not a.torch_train
         torch.manual_seed(1000)
         return model, IterativeRegistration(net, DPDistLoss(model), lr=1e-4, max_loops=a.loops, distributed=False, graph=graph, fused_pose=fused,
                                             native_refine=native)
@@ -73,12 +82,25 @@ def main():
         params = [p for p in net.parameters()]
         up = torch.ones(a.batch, 7, device=dev)
 
-        def one():
+        def one(marks=None):
+            if marks:
+                marks[0].record()
             pred = net.raw(src, tmpl)
+            if marks:
+                marks[1].record()
             torch.autograd.grad(pred, params, grad_outputs=up)
+            if marks:
+                marks[2].record()
             return pred
         for _ in range(5):
             pred = one()
+        fwd_ms, bwd_ms = [], []
+        for _ in range(20):                      # forward | backward by in-stream events, one evaluation at a time; the median of 20
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            one(marks)
+            torch.cuda.synchronize()
+            fwd_ms.append(marks[0].elapsed_time(marks[1]))
+            bwd_ms.append(marks[1].elapsed_time(marks[2]))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
@@ -89,9 +111,17 @@ def main():
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
             reg._train_step_eager(src, tmpl)
             torch.cuda.synchronize()
-        launches = sum(1 for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA)
-        return {"train_eval_ms": round(e0.elapsed_time(e1) / 50, 4), "train_eval_on_library": type(pred.grad_fn).__name__ == "_PoseNetRawFnBackward",
-                "launches_per_step": launches}
+        kernels = [ev for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA]
+        res = {"train_eval_ms": round(e0.elapsed_time(e1) / 50, 4), "train_eval_on_library": type(pred.grad_fn).__name__ == "_PoseNetRawFnBackward",
+               "pose_fwd_ms": round(float(np.median(fwd_ms)), 4), "pose_bwd_ms": round(float(np.median(bwd_ms)), 4), "launches_per_step": len(kernels)}
+        with profile(activities=[ProfilerActivity.CUDA]) as prof5:          # the dense dW5 kernel alone: ten evaluations, profiled apart
+            for _ in range(10):
+                one()
+            torch.cuda.synchronize()
+        dw5 = [ev.device_time for ev in prof5.events() if ev.device_type == torch.autograd.DeviceType.CUDA and "pose_avg_dw5_kernel" in ev.name]
+        if dw5:
+            res["avg_dw5_kernel_us"] = round(float(np.mean(dw5)), 2)
+        return res
 
     for form in a.forms.split(","):
         graph, fused, native = form.startswith("graph"), form != "eager_torch", form in ("eager_native", "graph")
@@ -121,7 +151,7 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             out[form]["replay_gpu_ms"] = round(e0.elapsed_time(e1) / 100, 4)
-        if a.num_point != 64:
+        if a.num_point != 64 or a.pn_pool != "max" or a.torch_train:
             out[form].update(train_eval_cost(reg))
         reg.close()
         print(form, json.dumps(out[form]), flush=True)
