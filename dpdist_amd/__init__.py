@@ -31,4 +31,7 @@ def __getattr__(name):
     if name in ("emd_matrix", "EMDMatrix", "emd_pairs", "EMDPairs"):
         from . import emd
         return getattr(emd, name)
+    if name in ("farthest_point_order", "farthest_point_sample"):
+        from . import sampling
+        return getattr(sampling, name)
     raise AttributeError(name)

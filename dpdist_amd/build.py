@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdpdist_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_x3.hip", "gemm_p8.hip", "mfv3d.hip", "mfv3d_bwd.hip", "patch_rows.hip", "decoder.hip", "decoder_out.hip", "decoder_bwd.hip", "decoder_live.hip", "cross_bwd.hip", "field_bwd.hip", "field_train.hip", "loss_adam.hip", "chamfer.hip", "chamfer_matrix.hip", "chamfer_pairs.hip", "nn_dist.hip", "emd.hip", "emd_matrix.hip", "emd_pairs.hip", "asloss.hip", "pose.hip", "pose_point.hip", "pose_point_bwd.hip", "pose_head.hip", "regtest.hip", "host_util.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_x3.hip", "gemm_p8.hip", "mfv3d.hip", "mfv3d_bwd.hip", "patch_rows.hip", "decoder.hip", "decoder_out.hip", "decoder_bwd.hip", "decoder_live.hip", "cross_bwd.hip", "field_bwd.hip", "field_train.hip", "loss_adam.hip", "chamfer.hip", "chamfer_matrix.hip", "chamfer_pairs.hip", "nn_dist.hip", "fps.hip", "emd.hip", "emd_matrix.hip", "emd_pairs.hip", "asloss.hip", "pose.hip", "pose_point.hip", "pose_point_bwd.hip", "pose_head.hip", "regtest.hip", "host_util.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
 

@@ -4,9 +4,17 @@
     nn_distance                 thin wrapper over dpd_nn_dist (csrc/nn_dist.hip); no torch fallback
     generate_distance_dataset   restates dataset_sample_with_gt.py:60-139 (the reference's label generator) on that kernel
     ModelNetDistanceDataset     restates modelnet_dataset.py:30-187 (the reference's reader) with SyntheticDistanceDataset's interface
+    resample_tree               writes a tree whose shape files are in farthest-point order (csrc/fps.hip through dpdist_amd/sampling.py)
 
     python -m dpdist_amd.dataset --root data/modelnet40_normal_resampled --only_chair      # writes the label files
     python -m dpdist_amd.train --data_dir data/modelnet40_normal_resampled                 # trains on them
+    python -m dpdist_amd.dataset --resample_from data/my_shapes --root data/my_resampled [--fps_points 10000]   # resample, then label
+
+THE ROW-ORDER CONTRACT.  Generator and readers take "the first npoints" rows of a shape file (modelnet_dataset.py:121-122,136;
+dataset_sample_with_gt.py:79-82), which is a well-spread 64- or 128-point cloud only because modelnet40_normal_resampled was written in
+FARTHEST-POINT ORDER: a prefix of such a file is itself a farthest-point sample.  A tree with any other row order (mesh samples, scans)
+gives a clustered or arbitrary subset, silently.  `--resample_from SRC` (resample_tree) writes --root from SRC with every file in that
+order, from its row 0, before the labels are generated; the text of each row is carried over unchanged.
 
 Files, next to each raw `<root>/<shape>/<id>.txt` (comma separated, `%.6f`):
     <id>_dist_c_scaled.txt            [P,3]    the cloud scaled by 0.8
@@ -197,6 +205,82 @@ def generate_distance_dataset(root, split_files=("modelnet40_test.txt", "modelne
 
 
 # --------------------------------------------------------------------------------------------------------------
+# resampler: any tree -> a tree whose files are in farthest-point order
+# --------------------------------------------------------------------------------------------------------------
+def _hip_fps_orders(points_list, K):
+    """the default order_fn of resample_tree: one ragged launch of dpd_fps_order (dpdist_amd/sampling.py) from row 0 of every cloud"""
+    import torch
+    from .sampling import farthest_point_order
+    counts = [len(p) for p in points_list]
+    pts = np.zeros((len(points_list), max(counts), 3), np.float32)
+    for c, p in enumerate(points_list):
+        pts[c, :len(p)] = p
+    order = farthest_point_order(torch.from_numpy(pts).cuda(), K, counts=counts).cpu().numpy()
+    return [order[c, :min(K, n)] for c, n in enumerate(counts)]
+
+
+def _read_rows(path):
+    """the non-empty text lines of a shape file and the float32 parse of their first three columns (the values np.loadtxt(...).astype(
+    np.float32) gives the generator above)"""
+    lines = _lines(path)
+    if not lines:
+        raise ValueError("%s holds no rows" % path)
+    xyz = np.array([ln.split(",")[0:3] for ln in lines], dtype=np.float64).astype(np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("%s: every row must start with x,y,z" % path)
+    if not np.isfinite(xyz).all():
+        raise ValueError("%s holds a coordinate that is not finite" % path)
+    return lines, xyz
+
+
+def resample_tree(src_root, dst_root, num_points=10 ** 4, class_choice=None, overwrite=False, batch=16, order_fn=None):
+    """Write every `<shape>/<id>.txt` that the split files of `src_root` name (after the category filter) to the same relative path under
+    `dst_root`, holding the first min(num_points, n) rows of the file's FARTHEST-POINT ORDER from row 0 -- the order the readers' "first
+    npoints" presumes.  Rows are `x,y,z[,...]`, any count, any order; the text lines themselves are moved, so every value (normals
+    included) stays byte for byte, and the order is computed on the float32 parse of the first three columns.  The list files are copied.
+    `batch` shapes share a launch as one ragged batch.  A shape whose destination exists is skipped unless `overwrite`.
+    order_fn(points_list, K) -> one index sequence per cloud, at least min(K, n) long; default: the HIP op (no torch fallback).
+    Returns the destination paths written."""
+    import shutil
+    if num_points < 1 or batch < 1:
+        raise ValueError("num_points and batch must be at least 1")
+    if os.path.abspath(src_root) == os.path.abspath(dst_root):
+        raise ValueError("resample_tree writes a new tree: dst_root must differ from src_root")
+    order_fn = order_fn or _hip_fps_orders
+    os.makedirs(dst_root, exist_ok=True)
+    todo, seen = [], set()
+    for name in [NAMES_FILE] + sorted(SPLIT_FILES.values()):
+        src = os.path.join(src_root, name)
+        if not os.path.exists(src):
+            continue
+        if name != NAMES_FILE:
+            for _, shape, raw in split_items(src_root, name, class_choice):
+                rel = os.path.join(shape, os.path.basename(raw))
+                dst = os.path.join(dst_root, rel)
+                if rel not in seen and (overwrite or not os.path.exists(dst)):
+                    todo.append((raw, dst))
+                seen.add(rel)
+        if overwrite or not os.path.exists(os.path.join(dst_root, name)):
+            shutil.copyfile(src, os.path.join(dst_root, name))
+    if not seen:
+        raise ValueError("no shape of %s in the split files of %s" % (class_choice, src_root))
+    done = []
+    for g in range(0, len(todo), batch):
+        rows = [_read_rows(raw) for raw, _ in todo[g:g + batch]]
+        K = min(num_points, max(len(xyz) for _, xyz in rows))
+        orders = order_fn([xyz for _, xyz in rows], K)
+        for (raw, dst), (lines, xyz), order in zip(todo[g:g + batch], rows, orders):
+            keep = [int(j) for j in list(order)[:min(num_points, len(lines))]]
+            if len(keep) != min(num_points, len(lines)) or len(set(keep)) != len(keep) or min(keep) < 0 or max(keep) >= len(lines):
+                raise RuntimeError("order_fn returned no valid order for %s" % raw)
+            os.makedirs(os.path.dirname(dst), exist_ok=True)
+            with open(dst, "w") as f:
+                f.write("".join(lines[j] + "\n" for j in keep))
+            done.append(dst)
+    return done
+
+
+# --------------------------------------------------------------------------------------------------------------
 # reader
 # --------------------------------------------------------------------------------------------------------------
 def neg_u_order(seed, split, index, size):
@@ -266,7 +350,13 @@ def main(argv=None):
     p.add_argument("--candidates", type=int, default=50000)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--overwrite", action="store_true")
+    p.add_argument("--resample_from", default=None, help="first write --root from this tree, every shape file in farthest-point order")
+    p.add_argument("--fps_points", type=int, default=10 ** 4, help="rows kept per shape by --resample_from")
     F = p.parse_args(argv)
+    if F.resample_from:
+        wrote = resample_tree(F.resample_from, F.root, num_points=F.fps_points, class_choice=["chair"] if F.only_chair else None,
+                              overwrite=F.overwrite)
+        print("resampled %d shapes into %s" % (len(wrote), F.root))
     done = generate_distance_dataset(F.root, class_choice=["chair"] if F.only_chair else None, num_neg_points=F.num_neg_points,
                                      candidates=F.candidates, seed=F.seed, overwrite=F.overwrite, verbose=True)
     print("label files written for %d shapes" % len(done))

@@ -163,6 +163,11 @@ SIGNATURES = {
     "dpd_chamfer_matrix_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4),
     "dpd_chamfer_matrix_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     "dpd_nn_dist": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # farthest-point sampling (dpdist_amd/sampling.py): pts, counts, start, S, W, K, order, radius, ws, ws_bytes, stream
+    "dpd_fps_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dpd_fps_order": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dpd_fps_gather_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dpd_fps_gather_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dpd_emd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dpd_emd_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float] + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "dpd_emd_match_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),

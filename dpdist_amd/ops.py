@@ -352,3 +352,42 @@ def gemm_f32(A, B, transA=False, transB=False, bias=None, gate=None, epilogue=0,
 
 def set_gemm_plan(op, tile, split_k=1):
     L.check(L.load().dpd_set_gemm_plan(op, tile, split_k), "dpd_set_gemm_plan")
+
+
+def fps_order(pts, K, counts=None, start=None, want_radius=False):
+    """pts [S,W,3], counts / start [S] int32 on the device or None -> order [S,K] int32 (and radius [S,K]): dpd_fps_order"""
+    L.req(pts, name="clouds")
+    S, W, _ = pts.shape
+    for t, name in ((counts, "counts"), (start, "start")):
+        if t is not None:
+            L.req(t, torch.int32, name, shape=(S,))
+    lib = L.load()
+    order = torch.empty(S, K, device=pts.device, dtype=torch.int32)
+    radius = torch.empty(S, K, device=pts.device, dtype=torch.float32) if want_radius else None
+    need = lib.dpd_fps_workspace_bytes(S, W)
+    ws = torch.empty(need // 4, device=pts.device, dtype=torch.float32) if need else None
+    L.check(lib.dpd_fps_order(L.ptr(pts), L.ptr(counts), L.ptr(start), S, W, K, L.ptr(order), L.ptr(radius), L.ptr(ws), need, L.cur_stream()),
+            "dpd_fps_order")
+    return order, radius
+
+
+def fps_gather_fwd(src, order):
+    """src [S,W,D], order [S,K] int32 -> out [S,K,D] = src[c, order[c,k]], +0.0 rows where order is -1: dpd_fps_gather_fwd"""
+    L.req(src, name="src")
+    S, W, D = src.shape
+    L.req(order, torch.int32, "order")
+    K = order.shape[1]
+    L.req(order, torch.int32, "order", shape=(S, K))
+    out = torch.empty(S, K, D, device=src.device, dtype=torch.float32)
+    L.check(L.load().dpd_fps_gather_fwd(L.ptr(src), L.ptr(order), S, W, D, K, L.ptr(out), L.cur_stream()), "dpd_fps_gather_fwd")
+    return out
+
+
+def fps_gather_bwd(dout, order, W):
+    """dout [S,K,D], order [S,K] (distinct valid entries) -> dsrc [S,W,D], fully written: dpd_fps_gather_bwd"""
+    L.req(dout, name="dout")
+    S, K, D = dout.shape
+    L.req(order, torch.int32, "order", shape=(S, K))
+    dsrc = torch.empty(S, W, D, device=dout.device, dtype=torch.float32)
+    L.check(L.load().dpd_fps_gather_bwd(L.ptr(dout), L.ptr(order), S, W, D, K, L.ptr(dsrc), L.cur_stream()), "dpd_fps_gather_bwd")
+    return dsrc

@@ -816,6 +816,50 @@ int dpd_chamfer_matrix_bwd(const float* S, const int32_t* countsS, int Cs, int N
 int dpd_nn_dist(const float* ref, const float* qry, int S, int P, int M, float* dist, int32_t* arg, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Farthest-point sampling: the row order the reference's readers presume when they take "the first npoints" rows of a shape file
+ * (modelnet_dataset.py:121-122,136; modelnet40_normal_resampled was written in this order), and the gather of a sample
+ * (csrc/fps.hip; dpdist_amd/sampling.py: farthest_point_order, farthest_point_sample; dpdist_amd/dataset.py: resample_tree).
+ * This comment is the definition.  For one cloud of n points p_0 .. p_{n-1} (fp32), start index s and K outputs:
+ *   dmin_j = +inf, taken_j = false for all j;  cur = s
+ *   for k = 0 .. min(K, n) - 1:
+ *     order[k]  = cur
+ *     radius[k] = (k == 0) ? +inf : sqrtf(dmin_cur)            the distance of the chosen point to all earlier ones
+ *     taken_cur = true
+ *     d_j    = (dx*dx + dy*dy) + dz*dz, d? = p_j? - p_cur?     fp32, in this order and not fused: the form of dpd_nn_dist
+ *     dmin_j = d_j < dmin_j ? d_j : dmin_j
+ *     cur    = the j with taken_j == false of largest dmin_j; among equals the LOWEST j
+ *   order[k] = -1, radius[k] = 0   for min(K, n) <= k < K
+ * The valid part of `order` is a prefix of a permutation of 0 .. n-1: a chosen point is excluded, not merely at distance 0, so duplicate
+ * points never repeat an index.  The order for K is a prefix of the order for any K' > K, and radius[1:] is non-increasing.  A maximum
+ * does not depend on the visiting order once ties go to the lowest index, so the result is defined bit for bit whatever the tiling (every
+ * merge across lanes, waves and rounds compares (dmin, index)).  Inputs must be finite (the result for a cloud with a NaN or infinite
+ * coordinate is unspecified, but every index written stays below n).
+ * dpd_fps_order: pts [S,W,3]; counts [S] (int32, DEVICE memory, the rules of the RAGGED block: never read by the host, clamped into
+ * [1, W] by the kernel, the padding is never read; NULL = every cloud has W points); start [S] (int32, device memory, clamped into
+ * [0, n_c - 1] by the kernel; NULL = 0); order [S,K] int32; radius [S,K] fp32 or NULL.  One workgroup of DPD_FPS_THREADS threads per cloud,
+ * S clouds in one launch; clouds of W <= DPD_FPS_RESIDENT_POINTS are held in registers, wider ones (up to DPD_FPS_MAX_POINTS) are
+ * re-read from global memory every iteration -- the same bits either way.  Two calls give the same bits; a cloud's result does not depend
+ * on W, the padding or the other clouds.  ws: dpd_fps_workspace_bytes(S, W) bytes of device scratch, 4-byte aligned: 0 for
+ * W <= DPD_FPS_RESIDENT_POINTS (ws may then be NULL), S * W floats beyond (the wide form's dmin; needs no initialisation); 0 as well for
+ * a shape the entry refuses.
+ * dpd_fps_gather_fwd: out[c,k,:] = src[c, order[c,k], :] for rows of D floats (3: points; 6: points with normals), +0.0 where order is -1.
+ * dpd_fps_gather_bwd: its adjoint; dsrc [S,W,D] is fully written by one launch: row order[c,k] receives dout[c,k,:], every other row
+ * +0.0.  No atomics: the valid entries of a row of `order` must be DISTINCT (an FPS order is; with repeats the row's value is one of the
+ * candidates' and unspecified which).
+ * Refusals, before anything is launched and with the outputs untouched: DPD_E_NULL for a missing pts / src / dout, order, out or dsrc;
+ * DPD_E_DIM for S, W, K, D < 1 or K > W; DPD_E_UNSUPPORTED for S > DPD_FPS_MAX_CLOUDS, W > DPD_FPS_MAX_POINTS, W * D >= 2^31 or a
+ * workspace smaller than dpd_fps_workspace_bytes.  No allocation, stream-ordered.                                                      */
+#define DPD_FPS_THREADS 1024
+#define DPD_FPS_RESIDENT_POINTS 16384
+#define DPD_FPS_MAX_POINTS (1 << 20)
+#define DPD_FPS_MAX_CLOUDS 65535
+size_t dpd_fps_workspace_bytes(int S, int W);
+int dpd_fps_order(const float* pts, const int32_t* counts, const int32_t* start, int S, int W, int K, int32_t* order, float* radius,
+                  void* ws, size_t ws_bytes, void* stream);
+int dpd_fps_gather_fwd(const float* src, const int32_t* order, int S, int W, int D, int K, float* out, void* stream);
+int dpd_fps_gather_bwd(const float* dout, const int32_t* order, int S, int W, int D, int K, float* dsrc, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Earth Mover's distance by approximate matching (Fan et al.), the EMD loss of the registration baselines
  * (utils/tf_util_loss.py:42-47 earth_mover; csrc/emd.hip).  This comment is the definition.
  * For each pair b, xyz1 [B,n,3] has n points and xyz2 [B,m,3] has m.  All arithmetic is fp32; d2(k,l) = (dx*dx + dy*dy) + dz*dz.
