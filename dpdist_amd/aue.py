@@ -16,42 +16,12 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import lib as L
-
-
-class _ChamferFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pc, rec):
-        L.req(pc, name="pc"), L.req(rec, name="rec_pc")
-        B, N, _ = pc.shape
-        M = rec.shape[1]
-        dev = pc.device
-        min_a = torch.empty(B, N, device=dev)
-        min_b = torch.empty(B, M, device=dev)
-        arg_a = torch.empty(B, N, device=dev, dtype=torch.int32)
-        arg_b = torch.empty(B, M, device=dev, dtype=torch.int32)
-        loss = torch.empty(1, device=dev)
-        L.check(L.load().dpd_chamfer_fwd(L.ptr(pc), L.ptr(rec), B, N, M, L.ptr(min_a), L.ptr(arg_a), L.ptr(min_b), L.ptr(arg_b),
-                                         L.ptr(loss), L.cur_stream()), "dpd_chamfer_fwd")
-        ctx.save_for_backward(pc, rec, arg_a, arg_b)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        pc, rec, arg_a, arg_b = ctx.saved_tensors
-        B, N, _ = pc.shape
-        M = rec.shape[1]
-        da = torch.empty_like(pc) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(rec) if ctx.needs_input_grad[1] else None
-        L.check(L.load().dpd_chamfer_bwd(L.ptr(pc), L.ptr(rec), B, N, M, L.ptr(arg_a), L.ptr(arg_b), 1.0, L.ptr(da), L.ptr(db),
-                                         L.cur_stream()), "dpd_chamfer_bwd")
-        # the upstream gradient stays on the device (no host sync, any scalar-shaped g)
-        return (None if da is None else da.mul_(g)), (None if db is None else db.mul_(g))
+from .baselines import _chamfer_paired
 
 
 def chamfer_dist(pc, rec_pc):
     """chmafer_dist(pc, rec_pc) of train_multi_gpu_pc_compare_dist.py:912-916 on the HIP kernels (squared distances)."""
-    return _ChamferFn.apply(pc.contiguous(), rec_pc.contiguous())
+    return _chamfer_paired(pc, rec_pc, "squared")
 
 
 class PointNetAE(nn.Module):

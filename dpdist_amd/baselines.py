@@ -39,6 +39,43 @@ def _form(form):
     return FORMS[form]
 
 
+class _ChamferPairedFn(torch.autograd.Function):
+    """the batch-mean Chamfer loss of two full sets a [B,N,3], b [B,M,3] (dpd_chamfer_fwd / _bwd, or dpd_chamfer_sqrt_fwd / _bwd for the
+    sqrt form) as one autograd node: the public names are aue.chamfer_dist and regtest.chamfer_sqrt"""
+
+    @staticmethod
+    def forward(ctx, a, b, form):
+        for t, name in ((a, "a"), (b, "b")):
+            L.req(t, name=name)
+            if t.dim() != 3 or t.shape[2] != 3:
+                raise RuntimeError("%s must be [B,N,3], got %s" % (name, tuple(t.shape)))
+        if a.shape[0] != b.shape[0]:
+            raise RuntimeError("a and b must hold the same number of clouds, got %d and %d" % (a.shape[0], b.shape[0]))
+        ctx.entries = (("dpd_chamfer_fwd", "dpd_chamfer_bwd"), ("dpd_chamfer_sqrt_fwd", "dpd_chamfer_sqrt_bwd"))[_form(form)]
+        B, N, M, dev = a.shape[0], a.shape[1], b.shape[1], a.device
+        min_a, min_b = torch.empty(B, N, device=dev), torch.empty(B, M, device=dev)
+        arg_a, arg_b = torch.empty(B, N, device=dev, dtype=torch.int32), torch.empty(B, M, device=dev, dtype=torch.int32)
+        loss = torch.empty(1, device=dev)
+        L.check(getattr(L.load(), ctx.entries[0])(L.ptr(a), L.ptr(b), B, N, M, L.ptr(min_a), L.ptr(arg_a), L.ptr(min_b), L.ptr(arg_b),
+                                                  L.ptr(loss), L.cur_stream()), ctx.entries[0])
+        ctx.save_for_backward(a, b, arg_a, arg_b)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, arg_a, arg_b = ctx.saved_tensors
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        L.check(getattr(L.load(), ctx.entries[1])(L.ptr(a), L.ptr(b), a.shape[0], a.shape[1], b.shape[1], L.ptr(arg_a), L.ptr(arg_b), 1.0,
+                                                  L.ptr(da), L.ptr(db), L.cur_stream()), ctx.entries[1])
+        # the upstream gradient stays on the device (no host sync, any scalar-shaped g)
+        return (None if da is None else da.mul_(g)), (None if db is None else db.mul_(g)), None
+
+
+def _chamfer_paired(a, b, form):
+    return _ChamferPairedFn.apply(a.contiguous(), b.contiguous(), form)
+
+
 def _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS, pairs=False):
     """every argument check, before anything is launched -> (A, B, cA, cB): contiguous fp32 sets and int32 device counts (None: a full
     set; B and cB are None for a set against itself); cap: the most points per cloud the caller's entries take; pairs: the sets are

@@ -78,14 +78,14 @@ __global__ __launch_bounds__(256) void chamfer_matrix_fwd_kernel(const float* __
     const long long units = (long long)Cs * groups;
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {   // 64-bit: the last stride may pass 2^31
         const int i = (int)(u / groups), g = (int)(u % groups);
-        const int ns = cm_count(countsS, i, Ns);
+        const int ns = ragged_count(countsS, i, Ns);
         __syncthreads();
         cm_stage(s_y, S + (size_t)i * Ns * 3, ns);
         __syncthreads();
         const long long run_end = (long long)(g + 1) * per;
         const int j1 = run_end < Cq ? (int)run_end : Cq;
         for (int j = g * per; j < j1; ++j) {
-            const int nq = cm_count(countsQ, j, Nq);
+            const int nq = ragged_count(countsQ, j, Nq);
             const float* q = Q + (size_t)j * Nq * 3;
             float ssq = 0.f, srt = 0.f, mx = 0.f;
             for (int base = 0; base < nq; base += kCmPass) {
@@ -135,14 +135,14 @@ __global__ __launch_bounds__(256) void chamfer_matrix_dq_kernel(const float* __r
     const int base = blockIdx.y * (256 * R);
     const int first = base + threadIdx.x;
     for (long long j = blockIdx.x; j < Cq; j += gridDim.x) {   // 64-bit: the last stride may pass 2^31
-        const int nq = cm_count(countsQ, (int)j, Nq);
+        const int nq = ragged_count(countsQ, (int)j, Nq);
         const float* q = Q + (size_t)j * Nq * 3;
         float* dq = dQ + (size_t)j * Nq * 3;
         const int live = base < nq ? cm_live(base, nq, R) : 0;
         float acc[R][3] = {};
         if (base < nq) {                                     // workgroup-uniform: a chunk of padding only writes zeros
             for (int i = 0; i < Cs; ++i) {
-                const int ns = cm_count(countsS, i, Ns);
+                const int ns = ragged_count(countsS, i, Ns);
                 __syncthreads();
                 cm_stage(s_y, S + (size_t)i * Ns * 3, ns);
                 __syncthreads();
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kCmSurfThreads) void chamfer_matrix_ds_kernel(const
     int* s_arg = reinterpret_cast<int*>(s_y + ((Ns * 3 + 3) & ~3));
     const int t = threadIdx.x;
     for (long long i = blockIdx.x; i < Cs; i += gridDim.x) {   // 64-bit: the last stride may pass 2^31
-        const int ns = cm_count(countsS, (int)i, Ns);
+        const int ns = ragged_count(countsS, (int)i, Ns);
         __syncthreads();
         cm_stage(s_y, S + (size_t)i * Ns * 3, ns);
         __syncthreads();
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kCmSurfThreads) void chamfer_matrix_ds_kernel(const
             for (int c = 0; c < 3; ++c) own[k][c] = p < ns ? s_y[p * 3 + c] : 0.f;
         }
         for (int j = 0; j < Cq; ++j) {
-            const int nq = cm_count(countsQ, j, Nq);
+            const int nq = ragged_count(countsQ, j, Nq);
             const float* q = Q + (size_t)j * Nq * 3;
             const float w = W[(size_t)i * Cq + j] / (float)nq;
             for (int base = 0; base < nq; base += kCmSurfThreads) {

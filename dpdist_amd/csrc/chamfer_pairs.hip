@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void chamfer_pairs_scan_kernel(const float* __
         const int r = (int)(u % per);
         const bool dir = r >= chunks_ab;           // 0: AB (surface A, queries B), 1: BA
         const int chunk = dir ? r - chunks_ab : r;
-        const int na = cm_count(countsA, (int)b, Wa), nb = cm_count(countsB, (int)b, Wb);
+        const int na = ragged_count(countsA, (int)b, Wa), nb = ragged_count(countsB, (int)b, Wb);
         const int ns = dir ? nb : na, nq = dir ? na : nb, Wq = dir ? Wa : Wb;
         if (chunk * 256 >= nq) continue;           // a chunk of padding (workgroup-uniform, ahead of every barrier)
         const float* a = A + (size_t)b * Wa * 3;
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void chamfer_pairs_finish_kernel(const int32_t
     for (long long u = blockIdx.x; u < 2 * P; u += gridDim.x) {
         const bool dir = u >= P;
         const long long b = dir ? u - P : u;
-        const int nq = dir ? cm_count(countsA, (int)b, Wa) : cm_count(countsB, (int)b, Wb);
+        const int nq = dir ? ragged_count(countsA, (int)b, Wa) : ragged_count(countsB, (int)b, Wb);
         const float* mn = dir ? min_ba + (size_t)b * Wa : min_ab + (size_t)b * Wb;
         float ssq = 0.f, srt = 0.f, mx = 0.f;
         for (int n = threadIdx.x; n < nq; n += 256) {
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void chamfer_pairs_grad_kernel(const float* __
         const int r = (int)(u % per);
         const bool set = r >= chunks_a;
         const int chunk = set ? r - chunks_a : r;
-        const int na = cm_count(countsA, (int)b, Wa), nb = cm_count(countsB, (int)b, Wb);
+        const int na = ragged_count(countsA, (int)b, Wa), nb = ragged_count(countsB, (int)b, Wb);
         const int nx = set ? nb : na, ny = set ? na : nb, Wx = set ? Wb : Wa, Wy = set ? Wa : Wb;
         const float* x = (set ? B : A) + (size_t)b * Wx * 3;
         const float* y = (set ? A : B) + (size_t)b * Wy * 3;

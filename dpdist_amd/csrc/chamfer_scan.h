@@ -1,5 +1,6 @@
-// The nearest-neighbour scan of the Chamfer losses, shared by chamfer.hip (squared form, AUE task) and regtest.hip (square-rooted form,
-// PCRNet's baseline): both store the same minima and indices, bit for bit, because both run this one body.
+// The nearest-neighbour scan of the paired Chamfer losses of chamfer.hip (squared form, AUE task; square-rooted form, PCRNet's baseline):
+// both forms store the same minima and indices because both launch the one min kernel around this body.  Below it, what the counted
+// kernels of chamfer_matrix.hip and chamfer_pairs.hip share.  The count clamp of a ragged set is ragged_count (common.h).
 #pragma once
 #include "common.h"
 
@@ -43,12 +44,6 @@ __device__ __forceinline__ void chamfer_min_scan(const float* __restrict__ a, co
 // same bits from either.
 constexpr int kCmMaxPoints = 4096;     // the cap of every Chamfer entry: the surface cloud lives in LDS
 constexpr int kCmMaxGrid = 1 << 20;    // workgroups per launch; the kernels stride over their units beyond it
-
-__device__ __forceinline__ int cm_count(const int32_t* __restrict__ counts, int c, int width) {
-    if (!counts) return width;
-    const int n = counts[c];
-    return n < 1 ? 1 : (n > width ? width : n);
-}
 
 __device__ __forceinline__ void cm_stage(float* __restrict__ s_y, const float* __restrict__ y, int ny) {
     for (int e = threadIdx.x; e < ny * 3; e += blockDim.x) s_y[e] = y[e];

@@ -107,6 +107,14 @@ inline GridAxis make_axis(int m) {
     return a;
 }
 
+// the count of cloud c of a ragged set (include/dpdist_capi.h, RAGGED block): clamped into [1, width]; counts = NULL: the set is full.
+// The one clamp of the baselines (chamfer_*, emd_*, fps.hip).
+__device__ __forceinline__ int ragged_count(const int32_t* __restrict__ counts, int c, int width) {
+    if (!counts) return width;
+    const int n = counts[c];
+    return n < 1 ? 1 : (n > width ? width : n);
+}
+
 // bijective XCD-aware remap of a 1-D block id: each XCD gets a contiguous chunk of logical ids.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     const int q = nblk / kNumXCD, r = nblk % kNumXCD;

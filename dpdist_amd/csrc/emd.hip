@@ -22,36 +22,60 @@
 // every output element has one writer per launch: two runs give identical bits.
 // exp goes through v_exp_f32 (base 2) with log2(e) folded into the level on the host; 1 / sqrt through v_rsq_f32.
 // The scan of a wave and the finish of an owner are written once, in emd_int.h: the all-pairs kernel of emd_matrix.hip calls them too;
-// so is what a workgroup does for one owner tile of one pair (emd_row_tile, emd_col_tile), which the counted kernels of emd_pairs.hip share.
+// so is what a workgroup does for one owner tile of one pair (emd_row_tile, emd_col_tile).  The pass kernels and their launch schedule
+// (emd_passes) below are the only ones: the per-pass form of the ragged pairs (emd_pairs.hip) runs them with counts.
 #include "emd_int.h"
 
 namespace dpd {
 
+// The pass kernels serve "pair b of two sets with optional counts and padded strides": A [P,Wa,3], B [P,Wb,3]; the vectors, grad1 / grad2
+// and match are rows of the padded widths.  dpd_emd_fwd: counts = NULL, Wa = n, Wb = m; the per-pass form of emd_pairs.hip: match = NULL,
+// gs = 1.  Grid (min(P, kEmdMaxGrid), owner tiles of the padded width); a tile wholly beyond its pair's count leaves before a barrier.
+
+// the five vectors of pair b: rows of the padded widths
+__device__ __forceinline__ EmdVec emd_vec(const EmdWs& ws, long long b, int Wa, int Wb) {
+    const size_t ba = (size_t)b * Wa, bb = (size_t)b * Wb;
+    return EmdVec{ws.remainL + ba, ws.ratioL + ba, ws.costk + ba, ws.remainR + bb, ws.ratioR + bb};
+}
+
 // Row pass.  W: step 3 of the level whose base-2 exponent scale is lw (match += w, remainL -= sum w, cost and grad1);
 // R: step 1 of the level with scale lr (ratioL).  first: no level has run yet (remainL / remainR are their initial constants, the
-// accumulators are written, not added to); gs is 1 except in the last launch, where grad1 leaves scaled.
-template <bool W, bool R>
-__global__ __launch_bounds__(kEmdThreads) void emd_row_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n, int m,
-                                                              float lw, float lr, int first, EmdWs ws, float* __restrict__ grad1,
+// accumulators are written, not added to); gs is 1 except in the last launch of the dense entry, where grad1 leaves scaled.
+// match [P,Wb,Wa] is an argument of the M instances only (the branch on it sits in the scan's inner loop, so the training paths run the
+// instances without it); its row stride is the pair's n, so it goes with counts = NULL only (emd_passes refuses the combination).
+template <bool W, bool R, bool M>
+__global__ __launch_bounds__(kEmdThreads) void emd_row_kernel(const float* __restrict__ A, const int32_t* __restrict__ countsA, int Wa,
+                                                              const float* __restrict__ B, const int32_t* __restrict__ countsB, int Wb,
+                                                              long long P, float lw, float lr, int first, EmdWs ws, float* __restrict__ grad1,
                                                               float* __restrict__ match, float gs) {
     __shared__ float4 s2[kEmdMax];                       // {x2, y2, z2, remainR[l]}
     __shared__ float sR[W ? kEmdMax : 1];                // ratioR[l]
     __shared__ float red[kEmdWaves][6][kWave];
-    const size_t b = blockIdx.x, bn = b * n, bm = b * m;
-    const EmdVec v{ws.remainL + bn, ws.ratioL + bn, ws.costk + bn, ws.remainR + bm, ws.ratioR + bm};
-    emd_row_tile<W, R>(s2, sR, red, xyz1 + bn * 3, xyz2 + bm * 3, n, m, blockIdx.y, lw, lr, first, v, grad1 ? grad1 + bn * 3 : nullptr,
-                       match ? match + bm * n : nullptr, gs);
+    const int tile = blockIdx.y;
+    for (long long b = blockIdx.x; b < P; b += gridDim.x) {
+        const int n = ragged_count(countsA, (int)b, Wa), m = ragged_count(countsB, (int)b, Wb);
+        if (tile * kWave >= n) continue;                 // a tile of padding: nothing to own
+        __syncthreads();                                 // the pair before this one is done with the LDS
+        emd_row_tile<W, R>(s2, sR, red, A + (size_t)b * Wa * 3, B + (size_t)b * Wb * 3, n, m, tile, lw, lr, first, emd_vec(ws, b, Wa, Wb),
+                           grad1 ? grad1 + (size_t)b * Wa * 3 : nullptr, M ? match + (size_t)b * Wb * Wa : nullptr, gs);
+    }
 }
 
-// Column pass: step 2 of the level with base-2 exponent scale lv, and grad2's share of that level.
+// Column pass: step 2 of the level with base-2 exponent scale lv, and grad2's share of that level (G; grad2 is read only then).
 template <bool G>
-__global__ __launch_bounds__(kEmdThreads) void emd_col_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n, int m,
-                                                              float lv, int first, EmdWs ws, float* __restrict__ grad2, float gs) {
+__global__ __launch_bounds__(kEmdThreads) void emd_col_kernel(const float* __restrict__ A, const int32_t* __restrict__ countsA, int Wa,
+                                                              const float* __restrict__ B, const int32_t* __restrict__ countsB, int Wb,
+                                                              long long P, float lv, int first, EmdWs ws, float* __restrict__ grad2, float gs) {
     __shared__ float4 s1[kEmdMax];                       // {x1, y1, z1, ratioL[k]}
     __shared__ float red[kEmdWaves][4][kWave];
-    const size_t b = blockIdx.x, bn = b * n, bm = b * m;
-    const EmdVec v{ws.remainL + bn, ws.ratioL + bn, ws.costk + bn, ws.remainR + bm, ws.ratioR + bm};
-    emd_col_tile<G>(s1, red, xyz1 + bn * 3, xyz2 + bm * 3, n, m, blockIdx.y, lv, first, v, G ? grad2 + bm * 3 : nullptr, gs);
+    const int tile = blockIdx.y;
+    for (long long b = blockIdx.x; b < P; b += gridDim.x) {
+        const int n = ragged_count(countsA, (int)b, Wa), m = ragged_count(countsB, (int)b, Wb);
+        if (tile * kWave >= m) continue;
+        __syncthreads();
+        emd_col_tile<G>(s1, red, A + (size_t)b * Wa * 3, B + (size_t)b * Wb * 3, n, m, tile, lv, first, emd_vec(ws, b, Wa, Wb),
+                        G ? grad2 + (size_t)b * Wb * 3 : nullptr, gs);
+    }
 }
 
 // cost[b] = sum_k costk[b][k] and loss = mean_b cost[b] / n, one workgroup, fixed order
@@ -120,10 +144,35 @@ static int emd_check(const void* xyz1, const void* xyz2, int B, int n, int m, co
     return 0;
 }
 
-static EmdWs emd_carve(void* ws, int B, int n, int m) {
-    float* f = (float*)ws;
-    const size_t bn = (size_t)B * n, bm = (size_t)B * m;
-    return EmdWs{f, f + bn, f + 2 * bn, f + 3 * bn, f + 3 * bn + bm};
+// The launch schedule of the matching (contract in emd_int.h; emd_pairs.hip calls it too): row<ratio> | (col, row) x 10, 21 launches on s
+int emd_passes(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, const EmdWs& w, float* g1,
+               float* g2, float* match, float gs, hipStream_t s) {
+    if (match && (countsA || countsB)) return DPD_E_UNSUPPORTED;       // match's row stride is the pair's n: full sets only
+    const int px = P < kEmdMaxGrid ? P : kEmdMaxGrid;
+    const dim3 grow(px, (Wa + kWave - 1) / kWave), gcol(px, (Wb + kWave - 1) / kWave), blk(kEmdThreads);
+    const long long PP = P;
+    const EmdLevels levels = emd_levels();
+    const float* lv = levels.v;
+#define EMD_ROW(W, R, M, lw, lr, first, g) \
+    DPD_LAUNCH((emd_row_kernel<W, R, M>), grow, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, lw, lr, first, w, g1, match, g)
+#define EMD_COL(G, lv, first, g) DPD_LAUNCH((emd_col_kernel<G>), gcol, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, lv, first, w, g2, g)
+    EMD_ROW(false, true, false, 0.f, lv[0], 1, 1.f);
+    DPD_CHECK_LAUNCH();
+    for (int i = 0; i < kEmdLevels; ++i) {
+        const int first = i == 0;
+        const bool last = i == kEmdLevels - 1;
+        if (g2) EMD_COL(true, lv[i], first, last ? gs : 1.f);
+        else EMD_COL(false, lv[i], first, 1.f);
+        DPD_CHECK_LAUNCH();
+        if (!last && match) EMD_ROW(true, true, true, lv[i], lv[i + 1], first, 1.f);
+        else if (!last) EMD_ROW(true, true, false, lv[i], lv[i + 1], first, 1.f);
+        else if (match) EMD_ROW(true, false, true, lv[i], 0.f, first, gs);
+        else EMD_ROW(true, false, false, lv[i], 0.f, first, gs);
+        DPD_CHECK_LAUNCH();
+    }
+#undef EMD_ROW
+#undef EMD_COL
+    return 0;
 }
 
 }  // namespace dpd
@@ -139,26 +188,7 @@ extern "C" int dpd_emd_fwd(const float* xyz1, const float* xyz2, int B, int n, i
     if (const int rc = emd_check(xyz1, xyz2, B, n, m, cost, loss, ws, ws_bytes)) return rc;
     const EmdWs w = emd_carve(ws, B, n, m);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grow(B, (n + kWave - 1) / kWave), gcol(B, (m + kWave - 1) / kWave), blk(kEmdThreads);
-    const float gs = gscale / ((float)B * (float)n);
-    const EmdLevels levels = emd_levels();
-    const float* lv = levels.v;
-    DPD_LAUNCH((emd_row_kernel<false, true>), grow, blk, 0, s, xyz1, xyz2, n, m, 0.f, lv[0], 1, w, grad1, match, 1.f);
-    DPD_CHECK_LAUNCH();
-    for (int i = 0; i < kEmdLevels; ++i) {
-        const int first = i == 0;
-        const bool last = i == kEmdLevels - 1;
-        if (grad2)
-            DPD_LAUNCH((emd_col_kernel<true>), gcol, blk, 0, s, xyz1, xyz2, n, m, lv[i], first, w, grad2, last ? gs : 1.f);
-        else
-            DPD_LAUNCH((emd_col_kernel<false>), gcol, blk, 0, s, xyz1, xyz2, n, m, lv[i], first, w, grad2, 1.f);
-        DPD_CHECK_LAUNCH();
-        if (!last)
-            DPD_LAUNCH((emd_row_kernel<true, true>), grow, blk, 0, s, xyz1, xyz2, n, m, lv[i], lv[i + 1], first, w, grad1, match, 1.f);
-        else
-            DPD_LAUNCH((emd_row_kernel<true, false>), grow, blk, 0, s, xyz1, xyz2, n, m, lv[i], 0.f, first, w, grad1, match, gs);
-        DPD_CHECK_LAUNCH();
-    }
+    if (const int rc = emd_passes(xyz1, nullptr, n, xyz2, nullptr, m, B, w, grad1, grad2, match, gscale / ((float)B * (float)n), s)) return rc;
     DPD_LAUNCH(emd_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)w.costk, B, n, cost, loss);
     DPD_CHECK_LAUNCH();
     return 0;

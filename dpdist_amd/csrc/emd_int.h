@@ -122,24 +122,24 @@ __device__ __forceinline__ void emd_col_finish(const float (&t)[4], int first, f
     }
 }
 
-// the count of cloud c of a ragged set (include/dpdist_capi.h, RAGGED block): clamped into [1, width]; counts = NULL: the set is full
-__device__ __forceinline__ int em_count(const int32_t* __restrict__ counts, int c, int width) {
-    if (!counts) return width;
-    const int n = counts[c];
-    return n < 1 ? 1 : (n > width ? width : n);
-}
+// ---- a pass as a launch: what one 256-thread workgroup does for one owner tile (64 points) of ONE pair.  The pass kernels of emd.hip
+// call these with the pair's own n, m and rows of the padded widths (a dense batch: n = Wa, m = Wb for every pair).
 
-// ---- a pass as a launch: what one 256-thread workgroup does for one owner tile (64 points) of ONE pair.  The paired kernels of emd.hip
-// call these with the pair's slices of a dense batch, the counted kernels of emd_pairs.hip with the pair's own n, m and padded strides.
-
-struct EmdWs {            // the vectors of a batch, carved from the caller's workspace, floats
-    float* remainL;       // [B,n]
-    float* ratioL;        // [B,n]
-    float* costk;         // [B,n]  sum_l match[l][k] sqrt(d^2)
-    float* remainR;       // [B,m]
-    float* ratioR;        // [B,m]
+struct EmdWs {            // the vectors of P pairs of padded widths Wa, Wb, carved from the caller's workspace, floats
+    float* remainL;       // [P,Wa]
+    float* ratioL;        // [P,Wa]
+    float* costk;         // [P,Wa]  sum_l match[l][k] sqrt(d^2)
+    float* remainR;       // [P,Wb]
+    float* ratioR;        // [P,Wb]
 };
 using EmdVec = EmdWs;     // the same five pointers advanced to one pair
+
+// the carve of dpd_emd_workspace_bytes(P, Wa, Wb) = dpd_emd_pairs_workspace_bytes(P, Wa, Wb)
+inline EmdWs emd_carve(void* ws, int P, int Wa, int Wb) {
+    float* f = (float*)ws;
+    const size_t pa = (size_t)P * Wa, pb = (size_t)P * Wb;
+    return EmdWs{f, f + pa, f + 2 * pa, f + 3 * pa, f + 3 * pa + pb};
+}
 
 // stage `cnt` points of cloud p [cnt,3] with their vector entry v (or the constant c when v is NULL) as float4 {x,y,z,v}
 __device__ __forceinline__ void emd_stage(float4* s, const float* __restrict__ p, const float* __restrict__ v, float c, int cnt) {
@@ -207,6 +207,14 @@ __device__ __forceinline__ void emd_col_tile(float4* __restrict__ s1, float (*__
     for (int c = 0; c < (G ? 4 : 1); ++c) t[c] = (red[0][c][lane] + red[1][c][lane]) + (red[2][c][lane] + red[3][c][lane]);
     emd_col_finish<G>(t, first, (float)max(n, m) / (float)m, v.remainR[l], v.ratioR[l], G ? grad2 + l * 3 : nullptr, gs);
 }
+
+// ---- the 21 pass launches of the matching over the pairs (b, b) of two sets (host side; defined in emd.hip, next to the pass kernels;
+// dpd_emd_fwd and the per-pass form of emd_pairs.hip call it).  counts NULL: full sets.  g1 [P,Wa,3] / g2 [P,Wb,3] (either may be NULL)
+// receive the gradients of each pair's real rows, scaled by gs in the last launch; match [P,Wb,Wa] (or NULL) is taken with NULL counts
+// only (DPD_E_UNSUPPORTED otherwise); w.costk holds the per-point costs afterwards.
+constexpr int kEmdMaxGrid = 1 << 20;   // workgroups along the pairs per launch; the kernels stride over their pairs beyond it
+int emd_passes(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, const EmdWs& w, float* g1,
+               float* g2, float* match, float gs, hipStream_t s);
 
 // ---- the pairs (b, b) of two sets through the one-workgroup-per-pair kernel of emd_matrix.hip (host side; emd_pairs.hip calls them).
 // cost / dist [P] (either may be NULL); g1 [P,Wa,3] / g2 [P,Wb,3]: the unscaled d cost / d xyz of each pair's real rows (either may be NULL).

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(GROUPS* kEmdThreads) void emd_matrix_kernel(const f
     const long long pairs = diag ? (long long)Ca : (long long)Ca * Cb;
     for (long long p = blockIdx.x; p < pairs; p += gridDim.x) {   // 64-bit: the last stride may pass 2^31
         const int i = diag ? (int)p : (int)(p / Cb), j = diag ? (int)p : (int)(p % Cb);
-        const int n = em_count(countsA, i, Na), m = em_count(countsB, j, Nb);
+        const int n = ragged_count(countsA, i, Na), m = ragged_count(countsB, j, Nb);
         const float* a = A + (size_t)i * Na * 3;
         const float* b = B + (size_t)j * Nb * 3;
         float* g1 = G1 ? gw1 + (size_t)p * Na * 3 : nullptr;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void emd_matrix_fold_a_kernel(const float* __r
     const long long total = (long long)Ca * Na * 3, row = (long long)Na * 3;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int i = (int)(e / row), r = (int)(e % row);
-        const int n = em_count(countsA, i, Na);
+        const int n = ragged_count(countsA, i, Na);
         float acc = 0.f;
         if (r / 3 < n) {
             const float* g = gw1 + (size_t)i * Cb * row + r;
@@ -190,13 +190,13 @@ __global__ __launch_bounds__(256) void emd_matrix_fold_b_kernel(const float* __r
     const long long total = (long long)Cb * Nb * 3, row = (long long)Nb * 3;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int j = (int)(e / row), r = (int)(e % row);
-        const int m = em_count(countsB, j, Nb);
+        const int m = ragged_count(countsB, j, Nb);
         float acc = 0.f;
         if (r / 3 < m) {
             if (accumulate) acc = dB[e];
             const float* g = gw2 + (size_t)j * row + r;
             for (int i = 0; i < Ca; ++i) {
-                const float n = (float)em_count(countsA, i, Na);
+                const float n = (float)ragged_count(countsA, i, Na);
                 acc += (W[(size_t)i * Cb + j] / n) * g[(size_t)i * Cb * row];
             }
         }

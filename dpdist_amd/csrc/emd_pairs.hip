@@ -6,8 +6,9 @@
 // Two forms, the same bits:
 //   1  one launch     emd_matrix_kernel (emd_matrix.hip) over the pair map p -> (p, p): one workgroup owns a pair, a pass is a loop between
 //                     two barriers, the vectors live in LDS.  P workgroups; for the widths where 22 dependent launches bind.
-//   2  per pass       the counted twins of dpd_emd_fwd's kernels below: a pass is a launch, a workgroup takes one owner tile (64 points)
-//                     of one pair, the vectors live in the workspace with the padded width as their row stride.  P * ceil(W / 64)
+//   2  per pass       the pass kernels and the launch schedule of dpd_emd_fwd themselves (emd.hip: emd_passes), given the counts: a pass
+//                     is a launch, a workgroup takes one owner tile (64 points) of one pair, the vectors live in the workspace (the
+//                     carve of emd_int.h, shared with the dense entry) with the padded width as their row stride.  P * ceil(W / 64)
 //                     workgroups per launch: 16 pairs of 2048 points are 512 workgroups where form 1 has 16.  A tile wholly beyond its
 //                     pair's count leaves before the first barrier.
 // form 0 takes form 2 from the padded width DPD_EMD_PAIRS_PER_PASS_FROM on (the larger of Wa, Wb; the host never reads a count).
@@ -26,56 +27,12 @@
 
 namespace dpd {
 
-constexpr int kEpMaxGrid = 1 << 20;   // workgroups along the pairs per launch; the kernels stride over their pairs beyond it
-
-// the five vectors of pair b: rows of the padded widths
-__device__ __forceinline__ EmdVec ep_vec(const EmdWs& ws, long long b, int Wa, int Wb) {
-    const size_t ba = (size_t)b * Wa, bb = (size_t)b * Wb;
-    return EmdVec{ws.remainL + ba, ws.ratioL + ba, ws.costk + ba, ws.remainR + bb, ws.ratioR + bb};
-}
-
-// Counted twin of emd_row_kernel: grid (pairs, owner tiles of the padded width Wa); g1 = dA (or NULL), rows of stride Wa.
-template <bool W, bool R>
-__global__ __launch_bounds__(kEmdThreads) void emd_pairs_row_kernel(const float* __restrict__ A, const int32_t* __restrict__ countsA, int Wa,
-                                                                    const float* __restrict__ B, const int32_t* __restrict__ countsB, int Wb,
-                                                                    long long P, float lw, float lr, int first, EmdWs ws,
-                                                                    float* __restrict__ g1) {
-    __shared__ float4 s2[kEmdMax];                       // {x2, y2, z2, remainR[l]}
-    __shared__ float sR[W ? kEmdMax : 1];                // ratioR[l]
-    __shared__ float red[kEmdWaves][6][kWave];
-    const int tile = blockIdx.y;
-    for (long long b = blockIdx.x; b < P; b += gridDim.x) {
-        const int n = em_count(countsA, (int)b, Wa), m = em_count(countsB, (int)b, Wb);
-        if (tile * kWave >= n) continue;                 // a tile of padding: nothing to own (workgroup-uniform, ahead of every barrier)
-        __syncthreads();                                 // the pair before this one is done with the LDS
-        emd_row_tile<W, R>(s2, sR, red, A + (size_t)b * Wa * 3, B + (size_t)b * Wb * 3, n, m, tile, lw, lr, first, ep_vec(ws, b, Wa, Wb),
-                           g1 ? g1 + (size_t)b * Wa * 3 : nullptr, nullptr, 1.f);
-    }
-}
-
-// Counted twin of emd_col_kernel: grid (pairs, owner tiles of the padded width Wb); g2 = dB, rows of stride Wb (read only when G).
-template <bool G>
-__global__ __launch_bounds__(kEmdThreads) void emd_pairs_col_kernel(const float* __restrict__ A, const int32_t* __restrict__ countsA, int Wa,
-                                                                    const float* __restrict__ B, const int32_t* __restrict__ countsB, int Wb,
-                                                                    long long P, float lv, int first, EmdWs ws, float* __restrict__ g2) {
-    __shared__ float4 s1[kEmdMax];                       // {x1, y1, z1, ratioL[k]}
-    __shared__ float red[kEmdWaves][4][kWave];
-    const int tile = blockIdx.y;
-    for (long long b = blockIdx.x; b < P; b += gridDim.x) {
-        const int n = em_count(countsA, (int)b, Wa), m = em_count(countsB, (int)b, Wb);
-        if (tile * kWave >= m) continue;
-        __syncthreads();
-        emd_col_tile<G>(s1, red, A + (size_t)b * Wa * 3, B + (size_t)b * Wb * 3, n, m, tile, lv, first, ep_vec(ws, b, Wa, Wb),
-                        G ? g2 + (size_t)b * Wb * 3 : nullptr, 1.f);
-    }
-}
-
 // cost[b] = sum_k costk[b][k] in emd_finish_kernel's order (thread t sums k = t, t + 256, ..., then block_sum_256), dist[b] = cost[b] / n_b
 __global__ __launch_bounds__(256) void emd_pairs_finish_kernel(const float* __restrict__ costk, const int32_t* __restrict__ countsA, int Wa,
                                                                long long P, float* __restrict__ cost, float* __restrict__ dist) {
     __shared__ float red[4];
     for (long long b = blockIdx.x; b < P; b += gridDim.x) {
-        const int n = em_count(countsA, (int)b, Wa);
+        const int n = ragged_count(countsA, (int)b, Wa);
         float s = 0.f;
         for (int k = threadIdx.x; k < n; k += 256) s += costk[(size_t)b * Wa + k];
         s = block_sum_256(s, red);
@@ -96,7 +53,7 @@ __global__ __launch_bounds__(256) void emd_pairs_fold_kernel(float* __restrict__
         const long long b = e / row;
         const int r = (int)(e % row);
         float acc = 0.f;
-        if (r / 3 < em_count(countsX, (int)b, Wx)) acc += (W[b] / (float)em_count(countsA, (int)b, Wa)) * g[e];
+        if (r / 3 < ragged_count(countsX, (int)b, Wx)) acc += (W[b] / (float)ragged_count(countsA, (int)b, Wa)) * g[e];
         g[e] = acc;
     }
 }
@@ -110,44 +67,9 @@ static int ep_check(const void* A, const void* B, int Wa, int Wb, int P, int for
 
 static int ep_form(int form, int Wa, int Wb) { return form ? form : ((Wa > Wb ? Wa : Wb) >= DPD_EMD_PAIRS_PER_PASS_FROM ? 2 : 1); }
 
-static EmdWs ep_carve(void* ws, int P, int Wa, int Wb) {
-    float* f = (float*)ws;
-    const size_t pa = (size_t)P * Wa, pb = (size_t)P * Wb;
-    return EmdWs{f, f + pa, f + 2 * pa, f + 3 * pa, f + 3 * pa + pb};
-}
-
-// the 21 pass launches of dpd_emd_fwd over the counted kernels; g1 / g2 (either may be NULL) receive the unscaled per-pair gradients
-static int ep_passes(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, const EmdWs& w,
-                     float* g1, float* g2, hipStream_t s) {
-    const int px = P < kEpMaxGrid ? P : kEpMaxGrid;
-    const dim3 grow(px, (Wa + kWave - 1) / kWave), gcol(px, (Wb + kWave - 1) / kWave), blk(kEmdThreads);
-    const long long PP = P;
-    const EmdLevels levels = emd_levels();
-    const float* lv = levels.v;
-    DPD_LAUNCH((emd_pairs_row_kernel<false, true>), grow, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, 0.f, lv[0], 1, w, g1);
-    DPD_CHECK_LAUNCH();
-    for (int i = 0; i < kEmdLevels; ++i) {
-        const int first = i == 0;
-        if (g2)
-            DPD_LAUNCH((emd_pairs_col_kernel<true>), gcol, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, lv[i], first, w, g2);
-        else
-            DPD_LAUNCH((emd_pairs_col_kernel<false>), gcol, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, lv[i], first, w, g2);
-        DPD_CHECK_LAUNCH();
-        if (i != kEmdLevels - 1)
-            DPD_LAUNCH((emd_pairs_row_kernel<true, true>), grow, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, lv[i], lv[i + 1], first, w, g1);
-        else
-            DPD_LAUNCH((emd_pairs_row_kernel<true, false>), grow, blk, 0, s, A, countsA, Wa, B, countsB, Wb, PP, lv[i], 0.f, first, w, g1);
-        DPD_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
 }  // namespace dpd
 
-extern "C" size_t dpd_emd_pairs_workspace_bytes(int P, int Wa, int Wb) {
-    if (P < 1 || Wa < 1 || Wb < 1 || Wa > dpd::kEmdMax || Wb > dpd::kEmdMax) return 0;
-    return ((size_t)P * Wa * 3 + (size_t)P * Wb * 2) * sizeof(float);
-}
+extern "C" size_t dpd_emd_pairs_workspace_bytes(int P, int Wa, int Wb) { return dpd_emd_workspace_bytes(P, Wa, Wb); }
 
 extern "C" int dpd_emd_pairs_fwd(const float* A, const int32_t* countsA, int Wa, const float* B, const int32_t* countsB, int Wb, int P, int form,
                                  float* cost, float* dist, void* ws, size_t ws_bytes, void* stream) {
@@ -157,9 +79,9 @@ extern "C" int dpd_emd_pairs_fwd(const float* A, const int32_t* countsA, int Wa,
     if (!ws || ws_bytes < dpd_emd_pairs_workspace_bytes(P, Wa, Wb)) return DPD_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (ep_form(form, Wa, Wb) == 1) return em_diag_fwd(A, countsA, Wa, B, countsB, Wb, P, cost, dist, s);
-    const EmdWs w = ep_carve(ws, P, Wa, Wb);
-    if (const int rc = ep_passes(A, countsA, Wa, B, countsB, Wb, P, w, nullptr, nullptr, s)) return rc;
-    DPD_LAUNCH(emd_pairs_finish_kernel, dim3(P < kEpMaxGrid ? P : kEpMaxGrid), dim3(256), 0, s, (const float*)w.costk, countsA, Wa, (long long)P,
+    const EmdWs w = emd_carve(ws, P, Wa, Wb);
+    if (const int rc = emd_passes(A, countsA, Wa, B, countsB, Wb, P, w, nullptr, nullptr, nullptr, 1.f, s)) return rc;
+    DPD_LAUNCH(emd_pairs_finish_kernel, dim3(P < kEmdMaxGrid ? P : kEmdMaxGrid), dim3(256), 0, s, (const float*)w.costk, countsA, Wa, (long long)P,
                cost, dist);
     DPD_CHECK_LAUNCH();
     return 0;
@@ -175,14 +97,14 @@ extern "C" int dpd_emd_pairs_bwd(const float* A, const int32_t* countsA, int Wa,
     if (ep_form(form, Wa, Wb) == 1) {
         if (const int rc = em_diag_grads(A, countsA, Wa, B, countsB, Wb, P, dA, dB, s)) return rc;
     } else {
-        if (const int rc = ep_passes(A, countsA, Wa, B, countsB, Wb, P, ep_carve(ws, P, Wa, Wb), dA, dB, s)) return rc;
+        if (const int rc = emd_passes(A, countsA, Wa, B, countsB, Wb, P, emd_carve(ws, P, Wa, Wb), dA, dB, nullptr, 1.f, s)) return rc;
     }
     for (int side = 0; side < 2; ++side) {
         float* g = side ? dB : dA;
         if (!g) continue;
         const int Wx = side ? Wb : Wa;
         const long long blocks = ((long long)P * Wx * 3 + 255) / 256;
-        DPD_LAUNCH(emd_pairs_fold_kernel, dim3(blocks < kEpMaxGrid ? (int)blocks : kEpMaxGrid), dim3(256), 0, s, g, side ? countsB : countsA, Wx,
+        DPD_LAUNCH(emd_pairs_fold_kernel, dim3(blocks < kEmdMaxGrid ? (int)blocks : kEmdMaxGrid), dim3(256), 0, s, g, side ? countsB : countsA, Wx,
                    countsA, Wa, (long long)P, W);
         DPD_CHECK_LAUNCH();
     }

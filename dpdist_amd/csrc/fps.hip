@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_order_kernel(const float* __r
     __shared__ float s_xyz[2][kFpsWaves][4];
     const int c = blockIdx.x, t = threadIdx.x;
     const int lane = t & (kWave - 1), wave = t / kWave;
-    const int n = counts ? min(max(counts[c], 1), W) : W;
+    const int n = ragged_count(counts, c, W);
     const int kn = min(K, n);
     const float* p = pts + (size_t)c * W * 3;
     int32_t* ord = order + (size_t)c * K;

@@ -3,12 +3,11 @@
 //                          fill the cloud back to N points by repeating the survivors
 //   dpd_pose_trace         the bookkeeping of the no-stop loop (:321-378, :464-474): every iteration's accumulated transform and its
 //                          translation / rotation / convergence error, for all pairs and iterations in one launch
-//   dpd_chamfer_sqrt_fwd / _bwd   utils/tf_util_loss.py:35-39, PCRNet's --loss_type chamf: (mean sqrt d1 + mean sqrt d2) / 2
-// All three are tiny and latency bound; they exist to take the per-pair host round trips out of the evaluation and to give the
-// baseline the reference's form.  Deterministic: every sum has a fixed order, there are no atomics.
+// Both are tiny and latency bound; they exist to take the per-pair host round trips out of the evaluation.  Deterministic: every sum
+// has a fixed order, there are no atomics.  (The protocol's baseline loss, the square-rooted Chamfer distance dpd_chamfer_sqrt_fwd /
+// _bwd, is a form of the paired Chamfer unit and lives with it in chamfer.hip.)
 #include <float.h>
 
-#include "chamfer_scan.h"
 #include "common.h"
 #include "pose_math.h"
 
@@ -226,86 +225,6 @@ __global__ __launch_bounds__(64) void pose_trace_kernel(const float* __restrict_
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Square-rooted Chamfer.  The scan is chamfer.hip's (chamfer_scan.h): min_* / arg_* are what dpd_chamfer_fwd stores.
-
-__global__ __launch_bounds__(256) void chamfer_sqrt_min_kernel(const float* __restrict__ a, const float* __restrict__ b, int N, int M,
-                                                               float* __restrict__ min_a, int32_t* __restrict__ arg_a,
-                                                               float* __restrict__ min_b, int32_t* __restrict__ arg_b, int chunks_a,
-                                                               int chunks_b) {
-    extern __shared__ float s_y[];   // [ny][3]
-    chamfer_min_scan(a, b, N, M, min_a, arg_a, min_b, arg_b, chunks_a, chunks_b, s_y);
-}
-
-// loss = (mean(sqrt min_a) + mean(sqrt min_b)) / 2, fixed summation order (one workgroup)
-__global__ __launch_bounds__(256) void chamfer_sqrt_loss_kernel(const float* __restrict__ min_a, long na, const float* __restrict__ min_b,
-                                                                long nb, float* __restrict__ loss) {
-    __shared__ float red[2][256];
-    float sa = 0.f, sb = 0.f;
-    for (long i = threadIdx.x; i < na; i += 256) sa += sqrtf(min_a[i]);
-    for (long i = threadIdx.x; i < nb; i += 256) sb += sqrtf(min_b[i]);
-    red[0][threadIdx.x] = sa;
-    red[1][threadIdx.x] = sb;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + o];
-            red[1][threadIdx.x] += red[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (red[0][0] / (float)na + red[1][0] / (float)nb) / 2.0f;
-}
-
-// d sqrt(|x - y|^2) / d x = (x - y) / |x - y|; a coincident pair contributes exactly zero (the reference: inf * 0 = NaN)
-__device__ __forceinline__ void chamfer_sqrt_term(float w, float px, float py, float pz, const float* __restrict__ y, float& gx, float& gy,
-                                                  float& gz) {
-    const float d = chamfer_pair_sq(px, py, pz, y);      // the stored minimum, recomputed: the same bits
-    if (d > 0.f) {
-        const float s = w / sqrtf(d);
-        gx += s * (px - y[0]);
-        gy += s * (py - y[1]);
-        gz += s * (pz - y[2]);
-    }
-}
-
-// Gradient w.r.t. x (dir 0: a, dir 1: b) as a gather (deterministic, no atomics):
-//   dx_i = g * [ wx u(x_i, y_arg_x[i])  +  wy * sum_{j : arg_y[j] == i} u(x_i, y_j) ],  u(x, y) = (x - y) / |x - y|,  wx = 1/(2 B nx), wy = 1/(2 B ny)
-__global__ __launch_bounds__(256) void chamfer_sqrt_grad_kernel(const float* __restrict__ a, const float* __restrict__ b, int N, int M,
-                                                                const int32_t* __restrict__ arg_a, const int32_t* __restrict__ arg_b,
-                                                                float gscale, int B, float* __restrict__ da, float* __restrict__ db,
-                                                                int chunks_a, int chunks_b) {
-    extern __shared__ float s_buf[];   // [ny][3] then [ny] arg (as int)
-    const int per = chunks_a + chunks_b;
-    const int c = blockIdx.x / per, r = blockIdx.x % per;
-    const bool dir = r >= chunks_a;
-    const int chunk = dir ? r - chunks_a : r;
-    const int nx = dir ? M : N, ny = dir ? N : M;
-    float* dx = dir ? db : da;
-    if (!dx) return;
-    const float* x = (dir ? b : a) + (size_t)c * nx * 3;
-    const float* y = (dir ? a : b) + (size_t)c * ny * 3;
-    const int32_t* arg_x = (dir ? arg_b : arg_a) + (size_t)c * nx;
-    const int32_t* arg_y = (dir ? arg_a : arg_b) + (size_t)c * ny;
-    float* s_y = s_buf;
-    int* s_arg = reinterpret_cast<int*>(s_buf + ny * 3);
-    for (int e = threadIdx.x; e < ny * 3; e += 256) s_y[e] = y[e];
-    for (int e = threadIdx.x; e < ny; e += 256) s_arg[e] = arg_y[e];
-    __syncthreads();
-    const int i = chunk * 256 + threadIdx.x;
-    if (i >= nx) return;
-    const float wx = gscale / (2.0f * (float)B * (float)nx), wy = gscale / (2.0f * (float)B * (float)ny);
-    const float px = x[i * 3], py = x[i * 3 + 1], pz = x[i * 3 + 2];
-    const int j0 = min(max(arg_x[i], 0), ny - 1);        // (an index the forward wrote; the clamp keeps a foreign one inside LDS)
-    float gx = 0.f, gy = 0.f, gz = 0.f;
-    chamfer_sqrt_term(wx, px, py, pz, s_y + j0 * 3, gx, gy, gz);
-    for (int j = 0; j < ny; ++j)
-        if (s_arg[j] == i) chamfer_sqrt_term(wy, px, py, pz, s_y + j * 3, gx, gy, gz);
-    dx[((size_t)c * nx + i) * 3] = gx;
-    dx[((size_t)c * nx + i) * 3 + 1] = gy;
-    dx[((size_t)c * nx + i) * 3 + 2] = gz;
-}
-
 }  // namespace dpd
 
 extern "C" int dpd_occlude(const float* src, const int32_t* seed_idx, const float* order_key, int B, int N, int drop, float* out,
@@ -333,37 +252,6 @@ extern "C" int dpd_pose_trace(const float* pred, int L, int B, float lim_rot_deg
     if (L < 1 || B < 1) return DPD_E_DIM;
     DPD_LAUNCH(pose_trace_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred, L, B, lim_rad_of(lim_rot_deg),
                gt_pose, shift, T_all, te, re, ce);
-    DPD_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dpd_chamfer_sqrt_fwd(const float* a, const float* b, int B, int N, int M, float* min_a, int32_t* arg_a, float* min_b,
-                                    int32_t* arg_b, float* loss, void* stream) {
-    using namespace dpd;
-    if (!a || !b || !min_a || !arg_a || !min_b || !arg_b || !loss) return DPD_E_NULL;
-    if (B <= 0 || N <= 0 || M <= 0) return DPD_E_DIM;
-    if (N > 4096 || M > 4096) return DPD_E_UNSUPPORTED;   // the other cloud lives in LDS (48 KB)
-    const int ca = (N + 255) / 256, cb = (M + 255) / 256;
-    const size_t lds = (size_t)(N > M ? N : M) * 3 * sizeof(float);
-    DPD_LAUNCH(chamfer_sqrt_min_kernel, dim3(B * (ca + cb)), dim3(256), lds, (hipStream_t)stream, a, b, N, M, min_a, arg_a, min_b, arg_b,
-               ca, cb);
-    DPD_CHECK_LAUNCH();
-    DPD_LAUNCH(chamfer_sqrt_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)min_a, (long)B * N,
-               (const float*)min_b, (long)B * M, loss);
-    DPD_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dpd_chamfer_sqrt_bwd(const float* a, const float* b, int B, int N, int M, const int32_t* arg_a, const int32_t* arg_b,
-                                    float gscale, float* da, float* db, void* stream) {
-    using namespace dpd;
-    if (!a || !b || !arg_a || !arg_b || (!da && !db)) return DPD_E_NULL;
-    if (B <= 0 || N <= 0 || M <= 0) return DPD_E_DIM;
-    if (N > 4096 || M > 4096) return DPD_E_UNSUPPORTED;
-    const int ca = (N + 255) / 256, cb = (M + 255) / 256;
-    const size_t lds = (size_t)(N > M ? N : M) * 4 * sizeof(float);
-    DPD_LAUNCH(chamfer_sqrt_grad_kernel, dim3(B * (ca + cb)), dim3(256), lds, (hipStream_t)stream, a, b, N, M, arg_a, arg_b, gscale, B, da,
-               db, ca, cb);
     DPD_CHECK_LAUNCH();
     return 0;
 }

@@ -18,6 +18,7 @@ a workgroup per 64-point tile at large ones.
 import torch
 
 from . import lib as L
+from .baselines import _check, _prepare
 
 MAX_POINTS = 2048                # DPD_EMD_MAX_POINTS: both clouds of a pair live in LDS
 MAX_WS_BYTES = 1 << 30           # bound on the workspace of EMDMatrix's backward: above it the backward goes in chunks of rows of A
@@ -103,23 +104,13 @@ def match_cost(pcd1, pcd2, match):
     return _MatchCostFn.apply(pcd1.contiguous(), pcd2.contiguous(), match.contiguous())
 
 
-def _matrix_prepare(cloudsA, cloudsB, countsA, countsB):
-    from .baselines import _prepare
-    return _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS)
-
-
-def _matrix_check(rc, what):
-    from .baselines import _check
-    _check(rc, what)
-
-
 def _matrix_forward(A, B, cA, cB):
     """D [Ca,Cb] of prepared sets (B None: A against itself, all Ca^2 pairs -- the match is not symmetric)"""
     lib = L.load()
     Q, cQ = (A, cA) if B is None else (B, cB)
     D = torch.empty(A.shape[0], Q.shape[0], device=A.device, dtype=torch.float32)
     with torch.cuda.device(A.device):
-        _matrix_check(lib.dpd_emd_matrix_fwd(L.ptr(A), L.ptr(cA), A.shape[0], A.shape[1], L.ptr(Q), L.ptr(cQ), Q.shape[0], Q.shape[1], None,
+        _check(lib.dpd_emd_matrix_fwd(L.ptr(A), L.ptr(cA), A.shape[0], A.shape[1], L.ptr(Q), L.ptr(cQ), Q.shape[0], Q.shape[1], None,
                                              L.ptr(D), L.cur_stream()), "dpd_emd_matrix_fwd")
     return D
 
@@ -138,7 +129,7 @@ def _matrix_backward(A, B, cA, cB, W, needA, needB):
         s = L.cur_stream()
         for chunk, i0 in enumerate(range(0, Ca, rows)):
             r = min(rows, Ca - i0)
-            _matrix_check(lib.dpd_emd_matrix_bwd(L.ptr(A[i0:]), L.ptr(None if cA is None else cA[i0:]), r, Na, L.ptr(B), L.ptr(cB), Cb, Nb,
+            _check(lib.dpd_emd_matrix_bwd(L.ptr(A[i0:]), L.ptr(None if cA is None else cA[i0:]), r, Na, L.ptr(B), L.ptr(cB), Cb, Nb,
                                                  L.ptr(W[i0:]), L.ptr(None if dA is None else dA[i0:]), L.ptr(dB), int(chunk > 0), L.ptr(ws),
                                                  ws.numel(), s), "dpd_emd_matrix_bwd")
     return dA, dB
@@ -152,7 +143,7 @@ def emd_matrix(cloudsA, cloudsB=None, *, countsA=None, countsB=None):
     count per cloud, each in [1, width]) and copied once, an int32 device tensor is used as it is and clamped by the kernels; padding is
     never read.  ValueError for CPU tensors, a dtype other than float32, sets on two devices, bad counts, countsB without cloudsB and
     more than 2048 points per cloud -- before anything is launched.  Forward only: EMDMatrix is differentiable."""
-    return _matrix_forward(*_matrix_prepare(cloudsA, cloudsB, countsA, countsB))
+    return _matrix_forward(*_prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS))
 
 
 class _EMDMatrixFn(torch.autograd.Function):
@@ -194,16 +185,11 @@ class EMDMatrix(torch.nn.Module):
 
     def forward(self, cloudsA, cloudsB=None, *, countsA=None, countsB=None):
         want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (cloudsA, cloudsB))
-        A, B, cA, cB = _matrix_prepare(cloudsA, cloudsB, countsA, countsB)
+        A, B, cA, cB = _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS)
         if not want_grad:
             with torch.no_grad():
                 return _matrix_forward(A, B, cA, cB)
         return _EMDMatrixFn.apply(cloudsA, cloudsB, cA, cB)
-
-
-def _pairs_prepare(cloudsA, cloudsB, countsA, countsB):
-    from .baselines import _prepare
-    return _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS, pairs=True)
 
 
 def _pairs_workspace(lib, A, B):
@@ -216,7 +202,7 @@ def _pairs_forward(A, B, cA, cB, form=0):
     D = torch.empty(A.shape[0], device=A.device, dtype=torch.float32)
     with torch.cuda.device(A.device):
         ws = _pairs_workspace(lib, A, B)
-        _matrix_check(lib.dpd_emd_pairs_fwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], form, None, L.ptr(D),
+        _check(lib.dpd_emd_pairs_fwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], form, None, L.ptr(D),
                                             L.ptr(ws), ws.numel(), L.cur_stream()), "dpd_emd_pairs_fwd")
     return D
 
@@ -228,7 +214,7 @@ def _pairs_backward(A, B, cA, cB, W, needA, needB, form=0):
     dB = torch.empty_like(B) if needB else None
     with torch.cuda.device(A.device):
         ws = _pairs_workspace(lib, A, B)
-        _matrix_check(lib.dpd_emd_pairs_bwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], form, L.ptr(W),
+        _check(lib.dpd_emd_pairs_bwd(L.ptr(A), L.ptr(cA), A.shape[1], L.ptr(B), L.ptr(cB), B.shape[1], A.shape[0], form, L.ptr(W),
                                             L.ptr(dA), L.ptr(dB), L.ptr(ws), ws.numel(), L.cur_stream()), "dpd_emd_pairs_bwd")
     return dA, dB
 
@@ -241,7 +227,7 @@ def emd_pairs(cloudsA, cloudsB, *, countsA=None, countsB=None):
     cloud, each in [1, width]) and copied once, an int32 device tensor is used as it is and clamped by the kernels; padding is never
     read.  ValueError for sets of different lengths, CPU tensors, a dtype other than float32, sets on two devices, bad counts and more
     than 2048 points per cloud -- before anything is launched.  Forward only: EMDPairs is differentiable."""
-    return _pairs_forward(*_pairs_prepare(cloudsA, cloudsB, countsA, countsB))
+    return _pairs_forward(*_prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS, pairs=True))
 
 
 class _EMDPairsFn(torch.autograd.Function):
@@ -276,7 +262,7 @@ class EMDPairs(torch.nn.Module):
 
     def forward(self, cloudsA, cloudsB, *, countsA=None, countsB=None):
         want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (cloudsA, cloudsB))
-        A, B, cA, cB = _pairs_prepare(cloudsA, cloudsB, countsA, countsB)
+        A, B, cA, cB = _prepare(cloudsA, cloudsB, countsA, countsB, cap=MAX_POINTS, pairs=True)
         if not want_grad:
             with torch.no_grad():
                 return _pairs_forward(A, B, cA, cB)

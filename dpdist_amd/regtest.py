@@ -1,4 +1,4 @@
-"""The registration experiment's test protocol on the HIP kernels of csrc/regtest.hip: what the reference's run script ends every leg
+"""The registration experiment's test protocol on the HIP kernels of csrc/regtest.hip (its baseline loss: csrc/chamfer.hip): what the reference's run script ends every leg
 (EMD, Chamfer, ours) with, and what its paper reports.
 
 Restates (relative to the reference's pcrnet-registration/):
@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .baselines import _chamfer_paired
 
 # (name, rotation bound in degrees, translation bound or None), outermost first: results_itrPCRNet_no_stop.py:394-401
 BUCKETS = (("idxs_20_2", 20.0, 0.2), ("idxs_10_1", 10.0, 0.1), ("idxs_5_5", 5.0, 0.05), ("idxs_25_5", 2.5, None))
@@ -65,38 +66,10 @@ def add_noise(source, generator=None):
     return source + sigma * torch.randn(B, N, 3, device=source.device, generator=generator)
 
 
-class _ChamferSqrtFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        B, N = _cloud(a, "a")
-        B2, M = _cloud(b, "b")
-        if B != B2:
-            raise RuntimeError("a and b must hold the same number of clouds, got %d and %d" % (B, B2))
-        dev = a.device
-        min_a, min_b = torch.empty(B, N, device=dev), torch.empty(B, M, device=dev)
-        arg_a, arg_b = torch.empty(B, N, device=dev, dtype=torch.int32), torch.empty(B, M, device=dev, dtype=torch.int32)
-        loss = torch.empty(1, device=dev)
-        L.check(L.load().dpd_chamfer_sqrt_fwd(L.ptr(a), L.ptr(b), B, N, M, L.ptr(min_a), L.ptr(arg_a), L.ptr(min_b), L.ptr(arg_b),
-                                              L.ptr(loss), L.cur_stream()), "dpd_chamfer_sqrt_fwd")
-        ctx.save_for_backward(a, b, arg_a, arg_b)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b, arg_a, arg_b = ctx.saved_tensors
-        B, N, _ = a.shape
-        M = b.shape[1]
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        L.check(L.load().dpd_chamfer_sqrt_bwd(L.ptr(a), L.ptr(b), B, N, M, L.ptr(arg_a), L.ptr(arg_b), 1.0, L.ptr(da), L.ptr(db),
-                                              L.cur_stream()), "dpd_chamfer_sqrt_bwd")
-        return (None if da is None else da.mul_(g)), (None if db is None else db.mul_(g))
-
-
 def chamfer_sqrt(a, b):
     """chamfer(pcd1, pcd2) of utils/tf_util_loss.py:35-39: (mean sqrt(nearest squared distance a->b) + mean sqrt(... b->a)) / 2.
     A coincident pair contributes a zero gradient (the reference: NaN)."""
-    return _ChamferSqrtFn.apply(a.contiguous(), b.contiguous())
+    return _chamfer_paired(a, b, "sqrt")
 
 
 def pose_trace(pred, gt_pose, shift=None, lim_rot=45.0):

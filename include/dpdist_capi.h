@@ -945,7 +945,7 @@ int dpd_emd_matrix_bwd(const float* A, const int32_t* countsA, int Ca, int Na, c
  *   -- the bits of dpd_emd_matrix_bwd on the pair alone.  Either of dA, dB may be NULL (both: DPD_E_NULL), a skipped side is not
  *   computed; rows at or beyond a count are written +0.0.
  *   form: 0 = the library chooses by the padded widths, 1 = one launch (one workgroup per pair, the all-pairs kernel over the pair map
- *   p -> (p, p)), 2 = per pass (the counted twins of dpd_emd_fwd's kernels: a workgroup per 64-point owner tile of a pair, 22 launches).
+ *   p -> (p, p)), 2 = per pass (dpd_emd_fwd's own pass kernels, given the counts: a workgroup per 64-point owner tile of a pair, 22 launches).
  *   Both forms run the same pass bodies and give the same bits.  ws: dpd_emd_pairs_workspace_bytes(P, Wa, Wb) = P (3 Wa + 2 Wb) floats
  *   of device scratch (the vectors of form 2; required by every form, since form 0 does not tell; 0 for a refused shape).
  *

@@ -142,6 +142,29 @@ def test_autograd_function_agrees_with_the_entry_and_scales_with_the_upstream_gr
         assert np.abs(scaled[q].cpu().numpy() - ref).max() / np.abs(ref).max() <= BAR[q]
 
 
+@pytest.mark.parametrize("n,m", [(70, 130), (130, 70)])
+def test_a_batch_is_its_pairs_one_by_one(n, m):
+    """the batch plumbing of the entry (two to three owner tiles, tail lanes, uneven quarters): cost, grad1, grad2 and match of a batch of
+    three are, bit for bit, those of three calls with one pair each and a third of the gscale (3 / (3 n) and 1 / n are the same float),
+    with either gradient left out too; loss is the fixed-order float32 mean of cost[b] / n"""
+    rng = np.random.default_rng(n)
+    x1, x2 = cu(rng.uniform(-1, 1, (3, n, 3)).astype(np.float32)), cu(rng.uniform(-1, 1, (3, m, 3)).astype(np.float32))
+    batch = run_entry(x1, x2, True, gscale=3.0)
+    ones = [run_entry(x1[b:b + 1].contiguous(), x2[b:b + 1].contiguous(), True, gscale=1.0) for b in range(3)]
+    same = lambda u, v: torch.equal(u.view(torch.int32), v.view(torch.int32))      # noqa: E731
+    for q in ("cost", "grad1", "grad2", "match"):
+        assert same(batch[q], torch.cat([o[q] for o in ones])), q
+    tot = np.float32(0)
+    for c in batch["cost"].cpu().numpy():
+        tot = tot + c / np.float32(n)
+    assert batch["loss"].cpu().numpy().view(np.int32) == (tot / np.float32(3)).view(np.int32)
+    only1, only2 = run_entry(x1, x2, False, gscale=3.0, grads=(True, False)), run_entry(x1, x2, False, gscale=3.0, grads=(False, True))
+    assert "grad2" not in only1 and "grad1" not in only2
+    assert same(only1["grad1"], batch["grad1"]) and same(only2["grad2"], batch["grad2"])
+    for o in (only1, only2):
+        assert same(o["cost"], batch["cost"]) and same(o["loss"], batch["loss"])
+
+
 def test_far_clouds_get_the_uniform_match():
     """no exponential survives before level 0 (|dx| >= 38: exp(-0.25 d2) = 0 in fp32), so every pair receives max(n,m) / (n m)"""
     B, n, m = E.SHAPES["far"]
